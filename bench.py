@@ -7,12 +7,17 @@ supported (boundary id 0), uniform pressure 300 as nodal Fz.  With --gpus N the 
 row-partitioned over N ranks (strong scaling, as BASELINE.json's 1/2/4/8-GPU curve asks).
 
 A "step" is one full femshell_assemble of K and F (inputs resident in HBM; launch + status round trip).  After W warm-up
-steps (each an assembly + cg_iters CG iterations) the K timed assembly steps run, then K*cg_iters CG iterations (6x6
-block-Jacobi, the oracle's method) are timed the same way (barrier + synchronize on both sides, max over ranks).
+steps (each an assembly + cg_iters CG iterations) the K timed assembly steps run (barrier + synchronize on both sides, max
+over ranks): `value` and `ms_per_step`.  A plain run does that and nothing else, then prints ONE compact JSON line on stdout.
 
-Output: rank 0 prints ONE compact JSON line on stdout (< 4 KB: metric, value, ms_per_step, config, roofline, cpu_baseline,
-cg_iters_per_s, time_to_solution_s / _iterations, parity_max_rel) and writes everything else to bench_detail.json next to this
-script (and to gpurun_out/ when it exists).  At N=1 the detail record carries
+--dump-outputs DIR writes what the last timed step computed -- K and F as femshell_export_bsr hands them to a caller, a fixed
+seeded sample where they are larger than the budget (dump_outputs below) -- as DIR/<name>.npy in float64.
+
+--full adds everything else, as before: K*cg_iters CG iterations (6x6 block-Jacobi, the oracle's method) timed the same
+way, the async assembly steps, per-kernel HIP-event rooflines, the box's streaming rates.  Rank 0 then writes the whole
+record to bench_detail.json next to this script, and the compact line (< 4 KB: metric, value, ms_per_step, config,
+roofline, cpu_baseline, cg_iters_per_s, time_to_solution_s / _iterations, parity_max_rel) carries its summary.  At N=1
+the detail record carries
   time_to_solution  the same 4M-tri system solved to rtol 1e-10 with the multigrid preconditioner
   parity            the small panel against the oracle, BASELINE configs[1] at full size (Scordelis-Lo roof, 250,632 tri3,
                     rtol 1e-12) against the oracle's refined direct solve, configs[2] / [3] / [4] at full size
@@ -526,7 +531,7 @@ def compact_line(detail):
         "pc_setup_s": tts.get("pc_setup_seconds"),
         "first_solve_wall_s": tts.get("wall_seconds_first_solve"),
         "parity_max_rel": parity_max_rel(detail),
-        "detail_file": DETAIL_FILE,
+        "detail_file": detail.get("detail_file", DETAIL_FILE),
     }
     if detail.get("error"):
         line["error"] = str(detail["error"])[:300]
@@ -561,6 +566,40 @@ def emit(detail):
     write_detail(detail)
     sys.stdout.flush()
     print(compact_line(detail), flush=True)
+
+
+DUMP_SEED = 20240611
+DUMP_K_ENTRIES = 1 << 20  # sampled entries of K: values, rows, columns (8 MB each)
+DUMP_F_ENTRIES = 1 << 20  # sampled entries of F: values, indices (8 MB each)
+
+
+def _dump_sample(n, k, rng):
+    """Sorted flat indices of a fixed sample of k of n entries; all of them when n <= k."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(rng.choice(n, size=k, replace=False))
+
+
+def dump_outputs(fs, out_dir):
+    """What the last timed step computed, as a caller of femshell_assemble receives it (femshell_export_bsr: K as block CSR
+    with sorted columns in the caller's node numbering, F), written to out_dir as float64 .npy files, 40 MB at most:
+      K_values, K_rows, K_cols  entries of K with their dof row and column (6 * node + component)
+      F_values, F_index         entries of F with their dof index
+    The entries are all of them on small meshes and a sample drawn with the fixed seed DUMP_SEED otherwise, so that two
+    runs with the same arguments write the same entries.  A row-partitioned rank exports the rows it owns."""
+    rowptr, colidx, vals, F = fs.export_bsr()
+    owned = fs.owned_nodes().astype(np.int64)  # (the caller's ids of the exported rows, in their order)
+    rowptr, F = rowptr[:len(owned) + 1], F[:6 * len(owned)]
+    rng = np.random.default_rng(DUMP_SEED)
+    k = _dump_sample(vals.size, DUMP_K_ENTRIES, rng)
+    blk, within = k // 36, k % 36
+    node = owned[np.searchsorted(rowptr, blk, side="right") - 1]
+    f = _dump_sample(F.size, DUMP_F_ENTRIES, rng)
+    arrays = {"K_values": vals.reshape(-1)[k], "K_rows": 6 * node + within // 6, "K_cols": 6 * colidx[blk].astype(np.int64) + within % 6,
+              "F_values": F[f], "F_index": 6 * owned[f // 6] + f % 6}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def guarded_multi_rank_run():
@@ -652,8 +691,15 @@ def main():
     ap.add_argument("--no-fullsize-parity", action="store_true",
                     help="skip the 4M-triangle parity sections (oracle assembly of 14M blocks + manufactured solutions, panel and cylinder)")
     ap.add_argument("--profile", action="store_true",
-                    help="for rocprofv3 runs: only the timed 4M-tri phases (no parity probes, no CPU baseline, no multigrid solve)")
+                    help="with --full, for rocprofv3 runs: only the timed 4M-tri phases (no parity probes, no CPU baseline, no multigrid solve)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed assembly steps: CG phase, per-kernel rooflines, time to solution, parity, CPU baseline, "
+                         "the box's streaming rates; the whole record goes to " + DETAIL_FILE)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write K and F of the last timed step to DIR/<name>.npy (float64; a fixed sample of large outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.cpu_baseline_worker:  # child process of cpu_baseline(): host only, never touches the GPU
         cpu_baseline_worker(args.nx or 1414)
         return
@@ -719,7 +765,7 @@ def main():
         del a, b
         torch.cuda.empty_cache()
         return rate
-    copy_gbs = device_copy_rate()
+    copy_gbs = device_copy_rate() if args.full else None
 
     def box_stream_rates():
         """Streaming write / read / copy rates of this box by tools/lab/hbm_rw (plain 16-byte-per-lane kernels over 4.3 GB, a child
@@ -733,7 +779,7 @@ def main():
             return json.loads(r.stdout.strip().splitlines()[-1])
         except Exception as e:  # noqa: BLE001 (a yardstick, not a measurement the line depends on)
             return {"error": repr(e)}
-    stream = box_stream_rates() if not args.profile else None
+    stream = box_stream_rates() if args.full and not args.profile else None
 
     def device_alloc_ms():
         """Wall time of hipMalloc + hipFree of 4 GiB: a few ms on a fresh box, a hundred and more right after a run that
@@ -747,7 +793,7 @@ def main():
         del x
         torch.cuda.empty_cache()
         return 1e3 * (time.perf_counter() - t)
-    alloc_ms = device_alloc_ms()
+    alloc_ms = device_alloc_ms() if args.full else None
     t0 = time.perf_counter()
     fs.set_mesh(m.xyz, m.tri)
     setup_s = time.perf_counter() - t0
@@ -782,6 +828,25 @@ def main():
     fs.sync()
     barrier()
     t_asm = max_over_ranks(time.perf_counter() - t0)
+    workload = ({"panel": "configs[3] flat panel", "cylinder": "configs[2] pinched cylinder", "roof": "configs[1] Scordelis-Lo roof"}[args.workload]
+                + " %dx%d squares: %d tri3, %d dofs" % (args.nx, args.nx, n_elem, 6 * n_nodes))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(fs, args.dump_outputs)
+    if not args.full:
+        # a plain run: the headline figure and nothing else (no detail record)
+        if rank == 0:
+            print(compact_line({
+                "metric": METRIC, "value": n_elem * args.steps / t_asm, "unit": "elements/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * t_asm / args.steps,
+                "config": {"workload": workload, "parallelism": "row-partition x%d" % world, "rccl_ranks_seen": rccl_ranks,
+                           "assembly_step": "one femshell_assemble: launch + status round trip",
+                           "warmup_step": "one femshell_assemble + cg_iters CG iterations", "cg_iters_per_step": args.cg_iters},
+                "detail_file": None}), flush=True)
+        fs.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # beside it: the same K steps enqueued with femshell_assemble_async, the status of all of them collected by one
     # femshell_sync (`ms_per_step_async`: what a caller that assembles ahead of the device pays)
     barrier()
@@ -990,9 +1055,7 @@ def main():
             "ms_first_assembly_cold": cold_ms,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
-            "config": {"workload": {"panel": "configs[3] flat panel", "cylinder": "configs[2] pinched cylinder",
-                                    "roof": "configs[1] Scordelis-Lo roof"}[args.workload]
-                                   + " %dx%d squares: %d tri3, %d dofs" % (args.nx, args.nx, n_elem, 6 * n_nodes),
+            "config": {"workload": workload,
                        "workload_parameters": {"panel": "10x10, simply supported, uniform pressure 300, E=1e7 nu=0.3 t=0.5 (configs[2] has the same size)",
                                                "cylinder": "R=300 L=600 t=3, E=3e6 nu=0.3",
                                                "roof": "R=25 L=50 80deg t=0.25, E=4.32e8 nu=0"}[args.workload],

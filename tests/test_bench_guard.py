@@ -9,9 +9,9 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_parent_ends_a_rank_whose_peer_never_arrives():
+def test_bench_parent_ends_a_rank_whose_peer_never_arrives(tmp_path):
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29571",
-               FEMSHELL_BENCH_TIMEOUT="12")
+               FEMSHELL_BENCH_TIMEOUT="12", FEMSHELL_BENCH_DETAIL_DIR=str(tmp_path))  # (the error record: not in the tree)
     env.pop("FEMSHELL_BENCH_CHILD", None)
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--nx", "32",

@@ -414,7 +414,7 @@ def test_bench_runs_row_partitioned_under_the_launcher_the_driver_uses(tmp_path)
                MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--nx", "96",
-           "--cg-iters", "5", "--jacobi-probe-iters", "0", "--no-cpu-baseline", "--no-full-parity"]
+           "--cg-iters", "5", "--jacobi-probe-iters", "0", "--no-cpu-baseline", "--no-full-parity", "--full"]
     env["FEMSHELL_BENCH_DETAIL_DIR"] = str(tmp_path)
     out = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
     assert out.returncode == 0, out.stderr.decode(errors="replace")[-3000:]

@@ -1,5 +1,5 @@
 """One-screen summary of a bench run: the compact stdout line on stdin, the detail record beside it if present.
-usage: python3 bench.py ... | python3 tools/bench_summary.py [bench_detail.json]"""
+usage: python3 bench.py --full ... | python3 tools/bench_summary.py [bench_detail.json]"""
 import json
 import os
 import sys

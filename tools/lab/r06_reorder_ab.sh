@@ -4,7 +4,7 @@
 mkdir -p gpurun_out
 out=gpurun_out/r06_reorder_ab.txt
 : > $out
-q="--no-cpu-baseline --no-full-parity --no-fullsize-parity --jacobi-probe-iters 0"
+q="--full --no-cpu-baseline --no-full-parity --no-fullsize-parity --jacobi-probe-iters 0"
 for lap in 1 2; do
   for v in "" morton rcm; do
     echo "lap $lap reorder=${v:-none}" >> $out

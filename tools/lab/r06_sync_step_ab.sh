@@ -7,7 +7,7 @@
 mkdir -p gpurun_out
 out=gpurun_out/r06_sync_step_ab.txt
 : > $out
-q="--no-cpu-baseline --no-full-parity --no-fullsize-parity --jacobi-probe-iters 0 --profile"
+q="--full --no-cpu-baseline --no-full-parity --no-fullsize-parity --jacobi-probe-iters 0 --profile"
 for lap in 1 2 3; do
   for v in "1 1 1 1" "0 1 1 1" "0 0 1 1" "0 1 0 1" "0 1 1 0"; do
     set -- $v

@@ -6,7 +6,7 @@ set -e
 mkdir -p gpurun_out
 out=gpurun_out/r06_warmup_ab.txt
 : > $out
-q="--no-cpu-baseline --no-full-parity --no-fullsize-parity --jacobi-probe-iters 0"
+q="--full --no-cpu-baseline --no-full-parity --no-fullsize-parity --jacobi-probe-iters 0"
 for lap in 1 2 3; do
   for extra in 0 1; do
     echo "lap $lap extra_warmup=$extra" >> $out

@@ -52,7 +52,7 @@ def main():
             "WRITE_SIZE_KB_median": w_kb, "launches_WRITE_SIZE": len(wk[name]),
             "read_bytes_raw": f_kb * 1024.0, "read_bytes_x2_gfx950": 2.0 * f_kb * 1024.0, "write_bytes": w_kb * 1024.0,
         }
-    res["_meta"] = {"kernel_source_digest": kernel_source_digest(), "command": "bench.py --steps 3 --warmup 1 --profile"}
+    res["_meta"] = {"kernel_source_digest": kernel_source_digest(), "command": "bench.py --full --steps 3 --warmup 1 --profile"}
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
     res.pop("_meta")

@@ -17,13 +17,13 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 one() { find "$1" -name "$2" | head -1; }
 # ---- assembly + block-Jacobi CG kernels (bench.py --profile)
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -o s -- python3 bench.py --steps 40 --warmup 5 --profile > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_stats.err
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -o s -- python3 bench.py --full --steps 40 --warmup 5 --profile > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_stats.err
 cp $out/${tag}_stats/s_kernel_stats.csv $out/${tag}_kernel_stats.csv 2> /dev/null
-timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/${tag}_pmc_fetch -o f -- python3 bench.py --steps 3 --warmup 1 --profile > /dev/null 2> $out/${tag}_pmc_fetch.err
-timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/${tag}_pmc_write -o w -- python3 bench.py --steps 3 --warmup 1 --profile > /dev/null 2> $out/${tag}_pmc_write.err
+timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/${tag}_pmc_fetch -o f -- python3 bench.py --full --steps 3 --warmup 1 --profile > /dev/null 2> $out/${tag}_pmc_fetch.err
+timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/${tag}_pmc_write -o w -- python3 bench.py --full --steps 3 --warmup 1 --profile > /dev/null 2> $out/${tag}_pmc_write.err
 python3 tools/pmc_summary.py $out/${tag}_pmc_fetch/f_counter_collection.csv $out/${tag}_pmc_write/w_counter_collection.csv $out/${tag}_pmc_hbm_traffic.json
 for cnt in SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_ADD_F64; do
-  timeout 300 rocprofv3 --kernel-trace --pmc $cnt --output-format csv -d $out/${tag}_pmc_$cnt -o c -- python3 bench.py --steps 3 --warmup 1 --profile > /dev/null 2> $out/${tag}_pmc_$cnt.err
+  timeout 300 rocprofv3 --kernel-trace --pmc $cnt --output-format csv -d $out/${tag}_pmc_$cnt -o c -- python3 bench.py --full --steps 3 --warmup 1 --profile > /dev/null 2> $out/${tag}_pmc_$cnt.err
 done
 python3 tools/pmc_flops.py $out/${tag}_pmc_SQ_INSTS_VALU_FMA_F64/c_counter_collection.csv $out/${tag}_pmc_SQ_INSTS_VALU_MUL_F64/c_counter_collection.csv $out/${tag}_pmc_SQ_INSTS_VALU_ADD_F64/c_counter_collection.csv $out/${tag}_pmc_fp64.json
 rm -rf $out/${tag}_pmc_SQ_INSTS_VALU_FMA_F64 $out/${tag}_pmc_SQ_INSTS_VALU_MUL_F64 $out/${tag}_pmc_SQ_INSTS_VALU_ADD_F64 $out/${tag}_pmc_fetch $out/${tag}_pmc_write $out/${tag}_stats
@@ -45,10 +45,10 @@ rm -rf $out/${tag}_amg_stats $out/${tag}_amg_fetch $out/${tag}_amg_write $out/${
 # ---- the default bench run comes last and sees the summaries (bench.py attaches `traffic` and the per-level times only from a
 # profile taken with the same kernel sources; on the box the copies under profiles/ are scratch -- commit them from gpurun_out/)
 for f in pmc_hbm_traffic.json pmc_fp64.json amg_by_level.json pmc_mfma.json; do cp $out/${tag}_$f profiles/${tag}_$f 2> /dev/null; done
-timeout 1100 python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout 1100 python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 cp bench_detail.json $out/${tag}_bench_detail.json 2> /dev/null  # (the detail record of THIS run: the next one writes the same file)
 tail -c 600 $out/${tag}_bench.err
 # configs[1] at full size as a run of its own (configs[2], the cylinder, is part of the default bench line)
-timeout 400 python3 bench.py --workload roof --no-cpu-baseline --no-full-parity --jacobi-probe-iters 0 > $out/${tag}_bench_roof.json 2> $out/${tag}_bench_roof.err
+timeout 400 python3 bench.py --full --workload roof --no-cpu-baseline --no-full-parity --jacobi-probe-iters 0 > $out/${tag}_bench_roof.json 2> $out/${tag}_bench_roof.err
 cp bench_detail.json $out/${tag}_bench_roof_detail.json 2> /dev/null
 python3 tools/bench_summary.py < $out/${tag}_bench.json 2> /dev/null | head -12
