@@ -26,7 +26,7 @@ SYMBOLS = [
     "femshell_sync", "femshell_pc_defaults", "femshell_set_preconditioner", "femshell_amg_levels", "femshell_amg_level",
     "femshell_amg_export", "femshell_residual", "femshell_comm_ranks", "femshell_amg_setup_stats", "femshell_amg_dense_stats", "femshell_amg_partition_info", "femshell_assembly_kernel",
     "femshell_amg_cycle_bytes", "femshell_comm_selftest", "femshell_comm_counters", "femshell_owned_nodes", "femshell_comm_bytes", "femshell_set_initial_guess",
-    "femshell_amg_patch_info",
+    "femshell_amg_patch_info", "femshell_amg_symbolic_info", "femshell_pc_apply",
 ]
 
 
@@ -141,6 +141,8 @@ def load_library():
     L.femshell_amg_setup_stats.argtypes = [vp, dp]
     L.femshell_amg_dense_stats.argtypes = [vp, dp]
     L.femshell_amg_patch_info.argtypes = [vp, dp]
+    L.femshell_amg_symbolic_info.argtypes = [vp, ip]
+    L.femshell_pc_apply.argtypes = [vp, dp, dp]
     L.femshell_amg_partition_info.argtypes = [vp, dp]
     L.femshell_assembly_kernel.argtypes = [vp]
     L.femshell_comm_selftest.argtypes = [vp, dp]
@@ -274,6 +276,16 @@ class FemShell:
         _check(self._L.femshell_spmv(self._h, _d(x), _d(y)))
         return y
 
+    def pc_apply(self, r):
+        """z = M^-1 r, one application of the multigrid cycle (femshell_pc_apply): 6 values per node, the caller's numbering; on a
+        row-partitioned context the rank's owned rows in the order of owned_nodes() (collective)."""
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+        if len(r) != 6 * int(self._L.femshell_owned_nodes(self._h, None)):
+            raise ValueError("r needs 6 values per owned node")
+        z = np.zeros_like(r)
+        _check(self._L.femshell_pc_apply(self._h, _d(r), _d(z)))
+        return z
+
     def residual(self, x):
         """F - K x with double-double products and row sums."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
@@ -374,8 +386,7 @@ class FemShell:
     def amg_symbolic_info(self):
         """Coarsening steps of the last setup by where their patterns were built."""
         out = np.zeros(3, dtype=np.int32)
-        self._L.femshell_amg_symbolic_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        _check(self._L.femshell_amg_symbolic_info(self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        _check(self._L.femshell_amg_symbolic_info(self._h, _i(out)))
         return {"in_hbm": int(out[0]), "host_after_overflow": int(out[1]), "host_by_rule": int(out[2])}
 
     def assembly_kernel(self):

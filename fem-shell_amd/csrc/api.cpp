@@ -1131,6 +1131,54 @@ int64_t femshell_amg_export(femshell_ctx *c, int32_t level, int32_t which, void 
     }
 }
 
+// What a solve needs in HBM before its Krylov loop: K and F assembled (again, with FEMSHELL_REASSEMBLE_EACH_SOLVE), the
+// block-Jacobi inverse.  *asm_s / *setup_s: seconds of the assembly and of the block-Jacobi setup done here (0: none needed).
+static int prepare_system(femshell_ctx *c, double *asm_s, double *setup_s)
+{
+    int rc = FEMSHELL_OK;
+    *asm_s = *setup_s = 0.0;
+    if (!c->matrix_valid || (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)) {
+        rc = do_assemble(c);
+        if (rc) return rc;
+        *asm_s = c->last_assemble_s;
+    } else if (!c->rhs_valid) {
+        rc = do_rhs(c);
+        if (rc) return rc;
+    }
+    if (!c->jacobi_valid) {
+        rc = do_jacobi(c);
+        if (rc) return rc;
+        *setup_s = c->last_setup_s;
+    }
+    return rc;
+}
+
+// The multigrid hierarchy of the K in HBM, built where there is none (first solve, K changed, the all-FP64 rebuild): on one rank,
+// or row-partitioned and collective when the context has a communicator.  *pc_setup_s += its seconds.
+static int ensure_amg_hierarchy(femshell_ctx *c, double *pc_setup_s)
+{
+    if (c->amg && c->amg->valid) return FEMSHELL_OK;
+    int rc = FEMSHELL_OK;
+    if (c->comm.active()) {
+        const double t0 = wall_s();
+        // row-partitioned hierarchy (amg_dist.cpp); a failure only one rank sees must reach the others
+        rc = agree_status(c, amg_setup_dist(c), "multigrid setup", true);
+        if (rc) {
+            c->amg.reset();
+            return rc;
+        }
+        *pc_setup_s += wall_s() - t0;
+    } else {
+        rc = amg_setup(c);
+        if (rc) {
+            c->amg.reset();
+            return rc;
+        }
+        *pc_setup_s += c->amg->setup_seconds;
+    }
+    return rc;
+}
+
 int femshell_solve(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info)
 {
     if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: null context");
@@ -1145,21 +1193,9 @@ int femshell_solve(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, 
     CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_solve (halo exchanges and all-reduces of the solve)");
     int rc = select_device(c);
     if (rc) return rc;
-    double asm_s = 0.0;
-    if (!c->matrix_valid || (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)) {
-        rc = do_assemble(c);
-        if (rc) return rc;
-        asm_s = c->last_assemble_s;
-    } else if (!c->rhs_valid) {
-        rc = do_rhs(c);
-        if (rc) return rc;
-    }
-    double setup_s = 0.0;
-    if (!c->jacobi_valid) {
-        rc = do_jacobi(c);
-        if (rc) return rc;
-        setup_s = c->last_setup_s;
-    }
+    double asm_s = 0.0, setup_s = 0.0;
+    rc = prepare_system(c, &asm_s, &setup_s);
+    if (rc) return rc;
     double pc_setup_s = 0.0;
     const bool use_amg = c->pc.type == FEMSHELL_PC_AMG;
     hipStream_t st = c->stream;
@@ -1175,24 +1211,9 @@ int femshell_solve(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, 
     bool fp64_fallback = false;
     float ms_abandoned = 0.f; // device time of an attempt that ended in the breakdown below: part of solve_seconds
     for (int attempt = 0;; attempt++) {
-        if (use_amg && (!c->amg || !c->amg->valid)) {
-            if (c->comm.active()) {
-                const double t0 = wall_s();
-                // row-partitioned hierarchy (amg_dist.cpp); a failure only one rank sees must reach the others
-                rc = agree_status(c, amg_setup_dist(c), "multigrid setup", true);
-                if (rc) {
-                    c->amg.reset();
-                    return rc;
-                }
-                pc_setup_s += wall_s() - t0;
-            } else {
-                rc = amg_setup(c);
-                if (rc) {
-                    c->amg.reset();
-                    return rc;
-                }
-                pc_setup_s += c->amg->setup_seconds;
-            }
+        if (use_amg) {
+            rc = ensure_amg_hierarchy(c, &pc_setup_s);
+            if (rc) return rc;
         }
         // a previous solve leaves done = 1 behind; the reduction launch in front of an all-reduce carries no phase and
         // would skip its work on it (multi-rank re-solves, e.g. every coupling iteration)
@@ -1535,6 +1556,47 @@ int femshell_residual(femshell_ctx *c, const double *x, double *r)
     FS_HIP(hipMemcpyAsync(ri.empty() ? r : ri.data(), dr.p, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     FS_HIP(hipStreamSynchronize(c->stream));
     for (int32_t i = 0; i < p.n_own && !ri.empty(); i++) std::memcpy(r + 6ull * c->perm[i], &ri[6ull * i], 6 * sizeof(double));
+    return FEMSHELL_OK;
+}
+
+int femshell_pc_apply(femshell_ctx *c, const double *r, double *z)
+{
+    if (!c || !r || !z) return set_err(FEMSHELL_ERR_INVALID, "femshell_pc_apply: null argument");
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_pc_apply: no mesh set");
+    if (c->pc.type != FEMSHELL_PC_AMG)
+        return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_pc_apply: multigrid contexts only (block-Jacobi CG is followed iterate by iterate)");
+    if (c->assembly_pending) {
+        const int prc = finish_pending_assembly(c);
+        if (prc) return prc;
+    }
+    TraceRange trace("femshell_pc_apply");
+    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_pc_apply (halo exchanges and all-reduces of one cycle)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    double asm_s = 0.0, setup_s = 0.0, pc_setup_s = 0.0;
+    rc = prepare_system(c, &asm_s, &setup_s);
+    if (!rc) rc = ensure_amg_hierarchy(c, &pc_setup_s);
+    if (rc) return rc;
+    const Plan &p = c->plan;
+    // the owned rows in the internal numbering; padding (and the ghost space a halo product might read) zero
+    const bool mapped = !c->perm.empty() && !c->comm.active();
+    std::vector<double> ri, zi((size_t)p.n_own * 6);
+    if (mapped) {
+        ri.resize((size_t)p.n_own * 6);
+        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(&ri[6ull * i], r + 6ull * c->perm[i], 6 * sizeof(double));
+    }
+    DevBuf<double> dr, dz;
+    FS_HIP(dr.alloc((size_t)std::max(p.n_local_nodes(), p.n_pad) * 6));
+    FS_HIP(dz.alloc((size_t)p.n_pad * 6));
+    FS_HIP(dr.zero(c->stream));
+    FS_HIP(dz.zero(c->stream));
+    FS_HIP(hipMemcpyAsync(dr.p, mapped ? ri.data() : r, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    rc = amg_apply(c, dr.p, dz.p, nullptr, /*pre_started=*/false);
+    if (rc) return rc;
+    FS_HIP(hipMemcpyAsync(mapped ? zi.data() : z, dz.p, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(hipStreamSynchronize(c->stream));
+    if (mapped)
+        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(z + 6ull * c->perm[i], &zi[6ull * i], 6 * sizeof(double));
     return FEMSHELL_OK;
 }
 

@@ -213,6 +213,13 @@ enum { FEMSHELL_AMG_AGGREGATES = 0, /* int32 [n_nodes] */
  * the A_* / P_* / AGGREGATES arrays are kept for problems of up to 300,000 blocks of K (up to 2,000,000 with
  * FEMSHELL_AMG_KEEP_HOST=1 in the environment at setup): an inspection interface, not part of the solve */
 int64_t femshell_amg_export(femshell_ctx *ctx, int32_t level, int32_t which, void *out);
+/* z = M^-1 r: ONE application of the multigrid preconditioner (the V or K cycle femshell_solve applies once per iteration, from
+ * the unfused start of its level-0 smoothing), on the hierarchy of the current K -- built first, as femshell_solve builds it,
+ * when the context has none.  A test entry: it holds the cycle to a restatement evaluated on the exported hierarchy.  r, z: 6
+ * values per node, the caller's numbering (single rank: all nodes); on a row-partitioned context the call is collective and
+ * every rank passes and receives its owned rows in the order of femshell_owned_nodes.  A later solve is not affected.
+ * FEMSHELL_ERR_UNSUPPORTED with the block-Jacobi preconditioner. */
+int femshell_pc_apply(femshell_ctx *ctx, const double *r, double *z);
 /* the patch smoother of level 0 of the last setup (csrc/amg_patch.hpp; FEMSHELL_AMG_PATCH_TAU / _MAX in the environment): out[0] =
  * rigid edges found (sigma_max of the scaled coupling above tau), out[1] = clusters, out[2] = nodes in clusters, out[3] = clusters
  * whose diagonal block was not positive definite (they keep their point blocks), out[4] = tau, out[5] = nodes per cluster at most.

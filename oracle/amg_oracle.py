@@ -531,17 +531,24 @@ def setup(A, xyz, dmask, lams=None, coarsest_nodes=200, max_levels=12, eig_ratio
     return levels
 
 
+def smoothing_operator(L):
+    """The operator the smoother and the residual in front of a restriction multiply with: L.As where a level carries one (the
+    library's single-precision copy of the values, tests/helpers/cycle_ref.py), else L.A.  The K cycle's products read L.A."""
+    return getattr(L, "As", L.A)
+
+
 def smooth(L, b, x):
     """Chebyshev smoothing in D^-1 A; x None = zero initial guess."""
+    As = smoothing_operator(L)
     if x is None:
         r = b
         x = np.zeros_like(b)
     else:
-        r = b - L.A @ x
+        r = b - As @ x
     d = L.inv_theta * (L.Dm @ r)
     x = x + d
     for a, c in L.cheb:
-        r = r - L.A @ d
+        r = r - As @ d
         d = a * d + c * (L.Dm @ r)
         x = x + d
     return x
@@ -552,7 +559,7 @@ def cycle(levels, li, b, kcycle):
     if li == len(levels) - 1:
         return L.dense_inv @ b
     x = smooth(L, b, None)
-    bc = L.R @ (b - L.A @ x)
+    bc = L.R @ (b - smoothing_operator(L) @ x)
     if kcycle and li + 2 < len(levels):
         xc = kcycle_solve(levels, li + 1, bc)
     else:

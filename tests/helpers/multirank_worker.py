@@ -175,6 +175,19 @@ def main():
                 if arr is not None:
                     extra["amg_L%d_%s" % (li, name)] = arr
         extra["residual_history"] = fs.residual_history()
+    if os.environ.get("FEMSHELL_TEST_PC_APPLY") == "1":
+        # one multigrid cycle on the rank's owned rows (femshell_pc_apply, collective), behind the solve: a random vector without
+        # its Dirichlet dofs and the rank's rows of F; with the coarsest level and its inverse, which every rank holds
+        own = fs.owned_nodes()
+        mask = np.asarray(m.dirichlet_mask()).astype(np.int64)
+        free = ((mask[:, None] >> np.arange(6)) & 1) == 0
+        r = np.random.default_rng(11).standard_normal((len(mask), 6)) * free
+        rp, ci, vals, F = fs.export_bsr()
+        extra.update(pc_r=r, pc_z=fs.pc_apply(r[own]), pc_F=F[:6 * len(own)], pc_zF=fs.pc_apply(F[:6 * len(own)]))
+        last = len(fs.amg_levels()) - 1
+        for name, arr in fs.amg_export(last).items():
+            if arr is not None:
+                extra["amg_L%d_%s" % (last, name)] = arr
     # a second solve on the same context with doubled loads (the coupled program re-solves every coupling iteration)
     fs.set_loads(2.0 * m.loads)
     if world > 1:
