@@ -198,8 +198,9 @@ def aggregate_piece(rowptr, colidx, visit=None):
     return agg, na
 
 
-def tentative(agg, na, B):
-    """Per aggregate B_agg = Q R by modified Gram-Schmidt (two passes); dependent columns -> zero column of Q."""
+def tentative(agg, na, B, ratios=None):
+    """Per aggregate B_agg = Q R by modified Gram-Schmidt (two passes); dependent columns -> zero column of Q.
+    ratios: a list that receives nj / n0 of every column with n0 > 0 (how far each one is from the drop at 1e-8)."""
     n = len(agg)
     order = np.argsort(agg, kind="stable")
     ptr = np.concatenate([[0], np.cumsum(np.bincount(agg, minlength=na))])
@@ -217,6 +218,8 @@ def tentative(agg, na, B):
                     M[:, j] -= c * M[:, i]
                     R[i, j] += c
             nj = np.linalg.norm(M[:, j])
+            if ratios is not None and n0 > 0.0:
+                ratios.append(nj / n0)
             if n0 > 0.0 and nj > 1e-8 * n0:
                 R[j, j] = nj
                 M[:, j] /= nj
@@ -433,16 +436,52 @@ def coarsen(A, B, lam, bounds=None, patch=None):
     Q, Bc = tentative(agg, na, B)
     P0 = sp.bsr_matrix((Q, agg.astype(np.int32), np.arange(n + 1, dtype=np.int32)), shape=(6 * n, 6 * na))
     Dm = patch[1] if patch is not None else bd_matrix(block_diag_inverse(A))
-    P = (P0 - ((4.0 / 3.0) / lam) * (Dm @ (A @ P0))).tobsr((6, 6))
-    Ac = (P.T @ (A @ P)).tobsr((6, 6))
+    # (the library's patterns are structural -- csrc/amg_setup.cpp bsr_multiply, csrc/amg_symbolic.hip --: a block that comes out
+    #  zero, such as a row of P at a clamped node, stays in the pattern, and the next level's aggregation sees its edges; scipy drops
+    #  such blocks, so the products are put back onto the structural patterns)
+    SA = node_pattern(A)
+    SP = structural(node_pattern(Dm) @ SA @ node_pattern(P0))
+    P = on_pattern(P0 - ((4.0 / 3.0) / lam) * (Dm @ (A @ P0)), SP)
+    Ac = on_pattern(P.T @ (A @ P), structural(SP.T @ SA @ SP))
     # coarse dofs without fine support: unit diagonal
-    d = Ac.diagonal()
-    if np.any(d == 0.0):
-        fix = sp.diags((d == 0.0).astype(np.float64))
-        Ac = (Ac + fix).tobsr((6, 6))
+    rows = np.repeat(np.arange(na), np.diff(Ac.indptr))
+    for k in np.flatnonzero(Ac.indices == rows):
+        dk = np.diagonal(Ac.data[k]).copy()
+        Ac.data[k][np.diag_indices(6)] = np.where(dk == 0.0, 1.0, dk)
     if bounds is not None:
         return agg, P, Ac, Bc, cbounds
     return agg, P, Ac, Bc
+
+
+def node_pattern(M):
+    """The block pattern of M (6x6 blocks) as a CSR matrix of ones, one entry per block."""
+    M = M.tobsr((6, 6))
+    S = sp.csr_matrix((np.ones(len(M.indices)), M.indices, M.indptr), shape=(M.shape[0] // 6, M.shape[1] // 6))
+    S.sum_duplicates()
+    S.sort_indices()
+    return S
+
+
+def structural(S):
+    """A product of block patterns as a pattern again (entries set to one)."""
+    S = S.tocsr()
+    S.sort_indices()
+    S.data[:] = 1.0
+    return S
+
+
+def on_pattern(X, S):
+    """X (6x6 blocks) stored on the block pattern S (CSR, one entry per block): blocks of S that X lacks are explicit zeros."""
+    X = X.tobsr((6, 6))
+    X.sort_indices()
+    nbc = S.shape[1]
+    xkey = np.repeat(np.arange(X.shape[0] // 6, dtype=np.int64), np.diff(X.indptr)) * nbc + X.indices
+    skey = np.repeat(np.arange(S.shape[0], dtype=np.int64), np.diff(S.indptr)) * nbc + S.indices
+    pos = np.searchsorted(skey, xkey)
+    assert np.all(pos < len(skey)) and np.all(skey[np.minimum(pos, len(skey) - 1)] == xkey), "a block outside the structural pattern"
+    data = np.zeros((len(skey), 6, 6))
+    data[pos] = X.data
+    return sp.bsr_matrix((data, S.indices.astype(np.int32), S.indptr.astype(np.int32)), shape=X.shape)
 
 
 def lambda_max(A, Dm, iterations=30):
@@ -483,6 +522,7 @@ def setup(A, xyz, dmask, lams=None, coarsest_nodes=200, max_levels=12, eig_ratio
         L.A = A
         L.n = A.shape[0] // 6
         L.Dm = bd_matrix(block_diag_inverse(A))
+        L.B = B
         levels.append(L)
         li = len(levels) - 1
         L.patch = None
