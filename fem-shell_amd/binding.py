@@ -26,7 +26,7 @@ SYMBOLS = [
     "femshell_sync", "femshell_pc_defaults", "femshell_set_preconditioner", "femshell_amg_levels", "femshell_amg_level",
     "femshell_amg_export", "femshell_residual", "femshell_comm_ranks", "femshell_amg_setup_stats", "femshell_amg_dense_stats", "femshell_amg_partition_info", "femshell_assembly_kernel",
     "femshell_amg_cycle_bytes", "femshell_comm_selftest", "femshell_comm_counters", "femshell_owned_nodes", "femshell_comm_bytes", "femshell_set_initial_guess",
-    "femshell_amg_patch_info", "femshell_amg_symbolic_info", "femshell_pc_apply",
+    "femshell_amg_patch_info", "femshell_amg_symbolic_info", "femshell_pc_apply", "femshell_set_sections",
 ]
 
 
@@ -106,6 +106,7 @@ def load_library():
     L.femshell_set_mesh.argtypes = [vp, C.c_int32, dp, C.c_int32, ip, C.c_int32, ip]
     L.femshell_set_dirichlet.argtypes = [vp, C.c_int32, ip, bp]
     L.femshell_set_loads.argtypes = [vp, C.c_int32, ip, dp]
+    L.femshell_set_sections.argtypes = [vp, C.c_int32, dp, ip, ip]
     L.femshell_assemble.argtypes = [vp]
     L.femshell_assemble_async.argtypes = [vp]
     L.femshell_solve.argtypes = [vp, C.c_double, C.c_int32, dp, C.POINTER(SolveInfo)]
@@ -229,6 +230,22 @@ class FemShell:
         f6 = np.ascontiguousarray(f6, dtype=np.float64).reshape(-1, 6)
         ids = None if node_ids is None else np.ascontiguousarray(node_ids, dtype=np.int32)
         _check(self._L.femshell_set_loads(self._h, len(f6), _i(ids), _d(f6)))
+
+    def set_sections(self, sections, tri_section=None, quad_section=None):
+        """Shell sections: `sections` is an (n, 3) array-like of (nu, E, thickness), tri_section / quad_section give every
+        triangle / quadrilateral of the mesh (in the order of set_mesh) its row of it.  set_sections(None) returns to the
+        uniform material of the context.  K and the preconditioner are rebuilt at the next assemble / solve."""
+        if sections is None:
+            _check(self._L.femshell_set_sections(self._h, 0, None, None, None))
+            return
+        sec = np.ascontiguousarray(sections, dtype=np.float64).reshape(-1, 3)
+        ts = None if tri_section is None else np.ascontiguousarray(tri_section, dtype=np.int32).ravel()
+        qs = None if quad_section is None else np.ascontiguousarray(quad_section, dtype=np.int32).ravel()
+        if ts is not None and len(ts) != self.n_tri:
+            raise ValueError("tri_section needs one entry per triangle (%d), got %d" % (self.n_tri, len(ts)))
+        if qs is not None and len(qs) != self.n_quad:
+            raise ValueError("quad_section needs one entry per quadrilateral (%d), got %d" % (self.n_quad, len(qs)))
+        _check(self._L.femshell_set_sections(self._h, len(sec), _d(sec), _i(ts), _i(qs)))
 
     def assemble(self, wait=True):
         """wait=False: femshell_assemble_async -- enqueued only; sync(), solve() ... report a failed element."""

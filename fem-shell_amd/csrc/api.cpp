@@ -48,7 +48,9 @@ double bytes_assemble(const femshell_ctx *c)
     // (symmetric storage: only the stored blocks are computed and written -- the algorithmic bytes of that layout -- and of a
     //  diagonal block, symmetric itself, the 12 words of the upper triangle: 192 instead of 288 bytes per node)
     return 12.0 * p.n_ltri() + 16.0 * p.n_lquad() + 24.0 * (p.n_own + p.n_ghost) + 292.0 * (double)p.stored_blocks -
-           (c->dm.diag_upper ? 96.0 * p.n_own : 0.0) + 4.0 * (p.n_own + 1) + 48.0 * p.n_own;
+           (c->dm.diag_upper ? 96.0 * p.n_own : 0.0) + 4.0 * (p.n_own + 1) + 48.0 * p.n_own +
+           // sections: an index per element and every row of the table that is in use, once
+           (c->have_sections ? 4.0 * (p.n_ltri() + p.n_lquad()) + (double)sizeof(SecConst) * std::min<double>(c->n_sections, p.n_ltri() + p.n_lquad()) : 0.0);
 }
 double bytes_spmv(const femshell_ctx *c)
 {
@@ -247,7 +249,8 @@ int do_assemble(femshell_ctx *c, bool wait = true)
     if (events) FS_HIP(hipEventRecord(c->ev0, c->stream));
     c->dm.rhs_loads = c->loads.p;
     c->dm.rhs_F = c->F.p;
-    launch_assemble(c->dm, c->mc, c->stream); // K and F (k_rhs alone serves changes of the loads)
+    if (!launch_assemble(c->dm, c->mc, c->stream, c->sections_or_null())) // K and F (k_rhs alone serves changes of the loads)
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: the context's sections have no table in HBM");
     if (events) FS_HIP(hipEventRecord(c->ev1, c->stream));
     FS_HIP(hipGetLastError());
     if (wait) {
@@ -425,11 +428,17 @@ extern "C" {
 
 const char *femshell_last_error(void) { return last_err().c_str(); }
 
+// the one rule for a material, of a config (femshell_create) or of a section (femshell_set_sections)
+static bool material_ok(double nu, double E, double thickness)
+{
+    return (nu > -1.0 && nu < 0.5 + 1e-12) && (E > 0.0) && (thickness > 0.0);
+}
+
 int femshell_create(const femshell_config *cfg, femshell_ctx **out)
 {
     if (!cfg || !out) return set_err(FEMSHELL_ERR_INVALID, "femshell_create: null argument");
     *out = nullptr;
-    if (!(cfg->nu > -1.0 && cfg->nu < 0.5 + 1e-12) || !(cfg->E > 0.0) || !(cfg->thickness > 0.0))
+    if (!material_ok(cfg->nu, cfg->E, cfg->thickness))
         return set_err(FEMSHELL_ERR_INVALID, "femshell_create: need -1 < nu <= 0.5, E > 0, thickness > 0");
     if (cfg->world_size < 1 || cfg->rank < 0 || cfg->rank >= cfg->world_size)
         return set_err(FEMSHELL_ERR_INVALID, "femshell_create: invalid rank/world_size");
@@ -686,6 +695,12 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     }
     std::string e;
     c->have_mesh = false;
+    c->have_sections = false; // (the element count may change)
+    c->n_sections = 0;
+    c->ds = DeviceSections();
+    c->sec_table.release();
+    c->slice_elem_section.release();
+    c->elem_section.release();
     c->warm_next = false;
     c->amg_fp64_only = false;
     c->perm.clear();
@@ -792,6 +807,7 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     c->dm.item_flags = c->item_flags.p;
     c->dm.max_stage_rows = p.max_stage_rows;
     c->dm.pipe = p.pipe ? 1 : 0;
+    c->pipe_without_sections = p.pipe;
     c->dm.slice_elem_ptr_last = (int32_t)(p.slice_elem_nodes.size() / 4);
     {
         // LDS of k_assemble: element records + partial-sum staging
@@ -882,6 +898,139 @@ int femshell_set_dirichlet(femshell_ctx *c, int32_t n, const int32_t *node_ids, 
     rc = upload_node_data(c, kNodeMasks);
     if (rc) return rc;
     c->matrix_valid = c->rhs_valid = c->jacobi_valid = false;
+    return FEMSHELL_OK;
+}
+
+// the items of c->plan were packed anew (repack_assembly_items): upload them and point the device view at the new layout
+static int upload_item_layout(femshell_ctx *c, bool sections)
+{
+    const Plan &p = c->plan;
+    hipStream_t st = c->stream;
+    FS_HIP(hipStreamSynchronize(st)); // (nothing in flight may still read the buffers that are replaced)
+    FS_HIP(c->item_ptr.upload(p.item_ptr, st));
+    FS_HIP(c->slice_desc.upload(p.slice_desc, st));
+    FS_HIP(c->items.upload(p.items, st));
+    FS_HIP(c->item_flags.alloc(p.pipe ? 0 : p.items.size()));
+    c->dm.item_ptr = c->item_ptr.p;
+    c->dm.slice_desc = reinterpret_cast<const int4 *>(c->slice_desc.p);
+    c->dm.items = reinterpret_cast<const uint4 *>(c->items.p);
+    c->dm.item_flags = c->item_flags.p;
+    c->dm.max_stage_rows = p.max_stage_rows;
+    c->dm.pipe = p.pipe ? 1 : 0;
+    (void)assemble_lds_layout(c->dm, p.max_slice_elems, p.max_stage_rows, p.n_lquad() > 0, sections);
+    launch_item_flags(c->dm, (int64_t)p.items.size(), st); // the constraint words of the new items
+    FS_HIP(hipGetLastError());
+    FS_HIP(hipStreamSynchronize(st));
+    return FEMSHELL_OK;
+}
+
+int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_section *sections, const int32_t *tri_section,
+                          const int32_t *quad_section)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: null context");
+    if (c->assembly_pending) {
+        const int prc = finish_pending_assembly(c);
+        if (prc) return prc;
+    }
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: call femshell_set_mesh first");
+    if (n_sections < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: n_sections < 0");
+    Plan &p = c->plan;
+    // ---- everything that can be refused is looked at before anything changes
+    if (n_sections > 0) {
+        if (!sections) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: sections is null");
+        if (p.n_tri > 0 && !tri_section) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: tri_section is null and the mesh has triangles");
+        if (p.n_quad > 0 && !quad_section) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: quad_section is null and the mesh has quadrilaterals");
+        for (int32_t s = 0; s < n_sections; s++)
+            if (!material_ok(sections[s].nu, sections[s].E, sections[s].thickness))
+                return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: section " + std::to_string(s) + ": need -1 < nu <= 0.5, E > 0, thickness > 0");
+        auto first_bad = [&](const int32_t *idx, int64_t n) {
+            std::atomic<int64_t> bad{n};
+            if (n > 0) parallel_chunks(n, [&](int64_t b, int64_t e) {
+                for (int64_t q = b; q < e; q++)
+                    if (idx[q] < 0 || idx[q] >= n_sections) {
+                        int64_t seen = bad.load();
+                        while (q < seen && !bad.compare_exchange_weak(seen, q)) {}
+                        break;
+                    }
+            }, 1 << 18);
+            return bad.load();
+        };
+        int64_t bad = first_bad(tri_section, p.n_tri);
+        if (bad < p.n_tri)
+            return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: triangle " + std::to_string(bad) + " has section " + std::to_string(tri_section[bad]) + ", outside [0, " + std::to_string(n_sections) + ")");
+        bad = first_bad(quad_section, p.n_quad);
+        if (bad < p.n_quad)
+            return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: quadrilateral " + std::to_string(bad) + " has section " + std::to_string(quad_section[bad]) + ", outside [0, " + std::to_string(n_sections) + ")");
+    }
+    int rc = select_device(c);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    std::string err;
+    if (n_sections == 0) {
+        if (!c->have_sections) return FEMSHELL_OK; // nothing was set: nothing changes
+        if (c->pipe_without_sections && !p.pipe) { // back to the layout femshell_set_mesh chose: K is again what it was, bit for bit
+            if (!repack_assembly_items(&p, true, &err)) return set_err(FEMSHELL_ERR_MESH, "femshell_set_sections: " + err);
+            rc = upload_item_layout(c, false);
+            if (rc) return rc;
+        } else {
+            FS_HIP(hipStreamSynchronize(st));
+            (void)assemble_lds_layout(c->dm, p.max_slice_elems, p.max_stage_rows, p.n_lquad() > 0, false); // the uniform records' buffers
+        }
+        c->have_sections = false;
+        c->n_sections = 0;
+        c->ds = DeviceSections();
+        c->sec_table.release();
+        c->slice_elem_section.release();
+        c->elem_section.release();
+        c->matrix_valid = c->rhs_valid = c->jacobi_valid = false;
+        return FEMSHELL_OK;
+    }
+    // ---- the table, and the index of every local element and of every entry of the slices' element lists (ghost elements of a
+    //      row-partitioned context included: every rank has the full arrays).  Element arrays are in the caller's element order
+    //      whatever the node numbering is.
+    std::vector<SecConst> table((size_t)n_sections);
+    for (int32_t s = 0; s < n_sections; s++) {
+        const double nu = sections[s].nu, E = sections[s].E, t = sections[s].thickness;
+        const double cm = E / (1.0 - nu * nu); // (as femshell_create fills MatConst)
+        table[(size_t)s].tcm = t * cm;
+        table[(size_t)s].cp = E * t * t * t / (12.0 * (1.0 - nu * nu));
+        table[(size_t)s].nu = nu;
+        table[(size_t)s].g = (1.0 - nu) / 2.0;
+    }
+    const int32_t n_ltri = p.n_ltri(), n_lquad = p.n_lquad();
+    RawVec<int32_t> elem_sec((size_t)n_ltri + (size_t)n_lquad), slice_sec(p.slice_elems.size());
+    parallel_chunks((int64_t)elem_sec.size(), [&](int64_t b, int64_t e) {
+        for (int64_t le = b; le < e; le++)
+            elem_sec[(size_t)le] = le < n_ltri ? tri_section[p.tri_global_id[(size_t)le]] : quad_section[p.quad_global_id[(size_t)(le - n_ltri)]];
+    }, 1 << 16);
+    parallel_chunks((int64_t)slice_sec.size(), [&](int64_t b, int64_t e) {
+        for (int64_t q = b; q < e; q++) slice_sec[(size_t)q] = elem_sec[(size_t)p.slice_elems[(size_t)q]];
+    }, 1 << 16);
+    // The pipelined kernel's sectioned records of triangles are longer (kPipeMaxSliceElemsSections): a plan laid out for it whose
+    // slices exceed what two buffers of those hold is packed for the two-phase kernel, until the sections are cleared.
+    if (p.pipe && n_lquad == 0 && p.max_slice_elems > kPipeMaxSliceElemsSections) {
+        if (!repack_assembly_items(&p, false, &err)) return set_err(FEMSHELL_ERR_MESH, "femshell_set_sections: " + err);
+        DeviceMatrix probe = c->dm;
+        probe.pipe = 0;
+        if (assemble_lds_layout(probe, p.max_slice_elems, p.max_stage_rows, false, true) > 160 * 1024) {
+            (void)repack_assembly_items(&p, true, &err);
+            return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_set_sections: a 32-node slice touches too many elements for the LDS staging");
+        }
+        rc = upload_item_layout(c, true);
+        if (rc) return rc;
+    }
+    FS_HIP(hipStreamSynchronize(st)); // (an assembly in flight reads the arrays that are replaced)
+    (void)assemble_lds_layout(c->dm, p.max_slice_elems, p.max_stage_rows, n_lquad > 0, true); // record buffers of the sectioned kernels
+    FS_HIP(c->sec_table.upload(table, st));
+    FS_HIP(c->elem_section.upload(elem_sec, st));
+    FS_HIP(c->slice_elem_section.upload(slice_sec, st));
+    FS_HIP(hipStreamSynchronize(st)); // the host arrays go out of scope
+    c->ds.table = c->sec_table.p;
+    c->ds.elem_section = c->elem_section.p;
+    c->ds.slice_elem_section = c->slice_elem_section.p;
+    c->n_sections = n_sections;
+    c->have_sections = true;
+    c->matrix_valid = c->rhs_valid = c->jacobi_valid = false; // as a change of the Dirichlet set
     return FEMSHELL_OK;
 }
 
@@ -1407,7 +1556,7 @@ int femshell_element_matrices(femshell_ctx *c, int32_t first, int32_t count, dou
     DevBuf<double> out;
     const size_t per = quads ? 576 : 324;
     FS_HIP(out.alloc((size_t)count * per));
-    launch_element_matrices(c->dm, c->mc, first, count, out.p, c->stream);
+    launch_element_matrices(c->dm, c->mc, first, count, out.p, c->stream, c->sections_or_null());
     FS_HIP(hipGetLastError());
     rc = check_status(c, "femshell_element_matrices");
     if (rc) return rc;
@@ -1663,7 +1812,9 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
     double bytes = 0.0;
     if (which == FEMSHELL_KERNEL_ASSEMBLE) {
         FS_HIP(hipEventRecord(c->ev0, st));
-        for (int32_t i = 0; i < reps; i++) launch_assemble(c->dm, c->mc, st);
+        for (int32_t i = 0; i < reps; i++)
+            if (!launch_assemble(c->dm, c->mc, st, c->sections_or_null()))
+                return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: the context's sections have no table in HBM");
         FS_HIP(hipEventRecord(c->ev1, st));
         FS_HIP(hipStreamSynchronize(st));
         FS_HIP(hipGetLastError());

@@ -31,8 +31,12 @@ __device__ __forceinline__ void lds_barrier()
 // kAblate (profiling builds only, 0 in the product): 1 = skip global stores, 2 = every lane reads
 // record 0, 4 = skip the block math, 8 = skip the record math, 32 = s_memtime stamps at the phase boundaries
 // kHasQuads = false compiles the QUAD4 code out (meshes of triangles only: every BASELINE config)
-template <int kWavesPerSimd, int kAblate = 0, bool kHasQuads = false>
-__global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m, MatConst mc)
+// kSections = true: contexts with shell sections (femshell_set_sections).  Phase A reads the element's section index beside its
+// node ids (same prefetch distance) and the section's row of the table beside the coordinates, builds the record with that
+// material and leaves what phase B needs of it in the record (shell_element.hpp rec_put_section); phase B takes it from there.
+// kSections = false is the code without any of it: `ds` is never read.
+template <int kWavesPerSimd, int kAblate = 0, bool kHasQuads = false, bool kSections = false>
+__global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m, MatConst mc, DeviceSections ds)
 {
     // LDS: [element records | partial-sum staging] (assemble_lds_layout)
     extern __shared__ double lds[];
@@ -125,6 +129,14 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
     if (!kHasQuads && etid < ne) fetch_coords(nd, Xcur);
     int4 nd_n = make_int4(0, 0, 0, -1); // slice s+1
     if (etid < d1.ne) nd_n = m.slice_elem_nodes[d1.e0 + etid];
+    // sections: the index travels with the node ids, the table row with the coordinates
+    int sec = 0, sec_n = 0;
+    SecConst sc_cur = {0.0, 0.0, 0.0, 0.0};
+    if (kSections) {
+        if (etid < ne) sec = ds.slice_elem_section[e0 + etid];
+        if (etid < ne) sc_cur = fetch_section(ds.table, sec);
+        if (etid < d1.ne) sec_n = ds.slice_elem_section[d1.e0 + etid];
+    }
     // right-hand side of the slice (contribRHS, fem-shell.cpp:1118-1153: a masked copy of the nodal loads): loaded
     // one slice ahead in front of the coordinate prefetch, stored where phase A waits for the coordinates anyway
     double rhs_pre = 0.0;
@@ -166,6 +178,9 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
             const int4 c = (i == etid) ? nd : m.slice_elem_nodes[e0 + i];
             double rec[kRec];
             bool ok = false;
+            SecConst sc = sc_cur;
+            if (kSections && i != etid) sc = fetch_section(ds.table, ds.slice_elem_section[e0 + i]);
+            const MatConst me = kSections ? mat_of_section(sc, mc.flags) : mc; // the element's material
             if (!kHasQuads || c.w < 0) {
                 double X[9];
                 if (!kHasQuads && i == etid) {
@@ -179,7 +194,7 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
                     for (int q = 0; q < kRec; q++) rec[q] = 1.0 + 0.01 * q + X[q % 9] * 1e-9;
                     ok = true;
                 } else {
-                    ok = tri3_record(X, mc, rec);
+                    ok = tri3_record(X, me, rec);
                     if (kHasQuads) {
 #pragma unroll
                         for (int q = kRecDoubles; q < kRec; q++) rec[q] = 0.0;
@@ -195,8 +210,9 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
                     X[3 * q + 1] = pt[1];
                     X[3 * q + 2] = pt[2];
                 }
-                ok = quad4_record(X, mc, rec);
+                ok = quad4_record(X, me, rec);
             }
+            if (kSections && ok) rec_put_section<kHasQuads>(rec, sc, kHasQuads && c.w >= 0);
             if (!ok) report_status(m.status, e0 + i + 1);
             double2 *dst = reinterpret_cast<double2 *>(lds_rec + (size_t)i * kRec);
 #pragma unroll
@@ -215,11 +231,16 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
         ne = d1.ne;
         nd = nd_n;
         if (!kHasQuads && etid < ne) fetch_coords(nd, Xcur);
+        if (kSections) {
+            sec = sec_n;
+            if (etid < ne) sc_cur = fetch_section(ds.table, sec);
+        }
         if (tid < d1.ni) {
             item_next = m.items[d1.i0 + tid];
             flags_next = m.item_flags[d1.i0 + tid];
         }
         if (etid < d2.ne) nd_n = m.slice_elem_nodes[d2.e0 + etid];
+        if (kSections && etid < d2.ne) sec_n = ds.slice_elem_section[d2.e0 + etid];
 
         stamp(6); // issue of the prefetches
         // ---- phase B: one lane per work item (at most kItemPairs element contributions), in rounds of 256
@@ -255,7 +276,8 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
                 for (int q = 0; q < cnt; q++) {
                     const uint32_t pr = (q == 0) ? (item.y & 0xffffu) : (q == 1 ? (item.y >> 16) : (item.z & 0xffffu));
                     const double *rec = lds_rec + ((kAblate & 2) ? 0 : (size_t)(pr >> 4) * kRec);
-                    tri3_diag_add_rec(rec, (int)(pr & 3u), mc, blk);
+                    if (kSections) tri3_diag_add_rec(rec, (int)(pr & 3u), rec_material<kHasQuads>(rec, mc.flags), blk);
+                    else tri3_diag_add_rec(rec, (int)(pr & 3u), mc, blk);
                 }
             } else {
                 for (int q = 0; q < cnt; q++) {
@@ -264,6 +286,8 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
                     if (kAblate & 4) {
 #pragma unroll
                         for (int i = 0; i < 26; i++) blk[i] += rec[i];
+                    } else if (kSections) {
+                        block_add_rec<kHasQuads>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), rec_material<kHasQuads>(rec, mc.flags), blk);
                     } else {
                         block_add_rec<kHasQuads>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, blk);
                     }
@@ -430,12 +454,19 @@ constexpr int kPipeRecPasses = 3;    // record passes the producer wave runs at 
 
 // kHasQuads: meshes with quadrilaterals -- records in the full 66-double layout (tri3_record / quad4_record as in k_assemble),
 // every block through block_add_rec, diagonal blocks as full 6x6 blocks
-template <int kAblate = 0, bool kHasQuads = false>
-__global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatConst mc)
+// kSections: contexts with shell sections.  The producer fetches the section index of an element with its node ids and the
+// section's row of the table with its coordinates (the same distances), and leaves nu in the record for the consumers: triangles
+// in RecLeanSec records (38 doubles: RecLean, nu, padding up to the next odd multiple of a bank quad), meshes with
+// quadrilaterals in the unused words of the 66-double records (shell_element.hpp rec_put_section).
+template <int kAblate = 0, bool kHasQuads = false, bool kSections = false>
+__global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatConst mc, DeviceSections ds)
 {
+    // lab builds of the sectioned instantiation (FEMSHELL_SECTIONS_LAB, kernels.hip; wrong K, timing only): 256 = the consumers take
+    // the context's material instead of the record's, 512 = the producer neither loads section indices nor table rows
+    constexpr bool kSecConsume = kSections && !(kAblate & 256), kSecProduce = kSections && !(kAblate & 512);
     extern __shared__ double lds[];
     __shared__ int simd_of_wave[4];
-    constexpr int kRec = kHasQuads ? kRecDoublesQuad : RecLean::doubles;
+    constexpr int kRec = kHasQuads ? kRecDoublesQuad : (kSections ? RecLeanSec::doubles : RecLean::doubles);
     constexpr int kCoords = kHasQuads ? 12 : 9; // coordinates of an element
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // ---- roles: by the SIMD a wave runs on when the four waves sit on four SIMDs (they do; the order varies from
@@ -482,6 +513,7 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
         // Operands in flight: coordinates of the passes of the next iteration (fetched while this one computes), node ids
         // one iteration further, element ranges (first word of the descriptors) of four slices.
         const int4 *enodes = m.slice_elem_nodes;
+        const int32_t *esec = ds.slice_elem_section; // (kSections only)
         const int n_entries = m.slice_elem_ptr_last; // entries of slice_elem_nodes (clamp for idle lanes)
         struct Range {
             int e0, ne;
@@ -529,12 +561,19 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
         double X[kPipeRecPasses][kCoords];
         int4 ndn[kPipeRecPasses];
         bool is_quad[kPipeRecPasses]; // the element whose coordinates X[p] holds
+        // sections: the table row of the element whose coordinates X[p] holds, the index of the element ndn[p] names
+        SecConst scx[kPipeRecPasses] = {};
+        int secn[kPipeRecPasses] = {};
 #pragma unroll
         for (int p = 0; p < kPipeRecPasses; p++) {
             const int4 c0 = enodes[stream_elem(r0, ra, rb, p)];
             fetch_coords(c0, X[p]);
             is_quad[p] = kHasQuads && c0.w >= 0;
             ndn[p] = enodes[stream_elem(r0n, rb, rc, p)];
+            if (kSecProduce) {
+                scx[p] = fetch_section(ds.table, esec[stream_elem(r0, ra, rb, p)]);
+                secn[p] = esec[stream_elem(r0n, rb, rc, p)];
+            }
         }
         double held[kRec]; // a record of the next slice, lean layout
         int held_at = -1;  // its index there, -1: none
@@ -545,16 +584,18 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
 #pragma unroll
             for (int q = 0; q < kRec / 2; q++) dst[q] = make_double2(rec[2 * q], rec[2 * q + 1]);
         };
-        auto record_of = [&](const double Xp[kCoords], bool quad, double lean[kRec]) __attribute__((always_inline)) {
+        auto record_of = [&](const double Xp[kCoords], bool quad, const SecConst &sc, double lean[kRec]) __attribute__((always_inline)) {
+            const MatConst me = kSecProduce ? mat_of_section(sc, mc.flags) : mc; // the element's material
             if (kHasQuads) { // the record as k_assemble keeps it
                 bool okq;
                 if (quad) {
-                    okq = quad4_record(Xp, mc, lean);
+                    okq = quad4_record(Xp, me, lean);
                 } else {
-                    okq = tri3_record(Xp, mc, lean);
+                    okq = tri3_record(Xp, me, lean);
 #pragma unroll
                     for (int q = kRecDoubles; q < kRec; q++) lean[q] = 0.0;
                 }
+                if (kSections && okq) rec_put_section<true>(lean, sc, quad);
                 return okq;
             }
             double rec[kRecDoubles];
@@ -564,10 +605,15 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
                 for (int q = 0; q < kRecDoubles; q++) rec[q] = 1.0 + 0.01 * q + Xp[q % 9] * 1e-9;
                 ok = true;
             } else {
-                ok = tri3_record(Xp, mc, rec);
+                ok = tri3_record(Xp, me, rec);
             }
 #pragma unroll
-            for (int q = 0; q < kRec; q++) lean[q] = rec[lean_from_full(q)];
+            for (int q = 0; q < RecLean::doubles; q++) lean[q] = rec[lean_from_full(q)];
+            if (kSections) {
+#pragma unroll
+                for (int q = RecLean::doubles; q < kRec; q++) lean[q] = 0.0;
+                lean[RecLeanSec::nu] = ok ? me.nu : 0.0;
+            }
             return ok;
         };
         auto produce = [&](double *buf) {
@@ -578,7 +624,7 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
             for (int p = 0; p < kPipeRecPasses - 1; p++) { // full passes
                 if (p < np - 1) {
                     double lean[kRec];
-                    const bool ok = record_of(X[p], is_quad[p], lean);
+                    const bool ok = record_of(X[p], is_quad[p], scx[p], lean);
                     const int li = r0 + 64 * p + lane;
                     if (!ok) report_status(m.status, ra.e0 + li + 1);
                     write_lean(buf, li, lean);
@@ -587,9 +633,10 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
                 // counter its precision -- 0.62 against 0.55 ms with the second slot's nine loads skipped when unused)
                 fetch_coords(ndn[p], X[p]); // the next iteration's element of this lane and slot
                 is_quad[p] = kHasQuads && ndn[p].w >= 0;
+                if (kSecProduce) scx[p] = fetch_section(ds.table, secn[p]);
             }
             if (np > 0) { // last pass: the slice's last records, then the first of the next slice
-                const bool ok = record_of(X[kPipeRecPasses - 1], is_quad[kPipeRecPasses - 1], held);
+                const bool ok = record_of(X[kPipeRecPasses - 1], is_quad[kPipeRecPasses - 1], scx[kPipeRecPasses - 1], held);
                 const int li = r0 + 64 * (np - 1) + lane, li2 = li - ra.ne;
                 if (li < ra.ne) {
                     if (!ok) report_status(m.status, ra.e0 + li + 1);
@@ -604,6 +651,7 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
             }
             fetch_coords(ndn[kPipeRecPasses - 1], X[kPipeRecPasses - 1]);
             is_quad[kPipeRecPasses - 1] = kHasQuads && ndn[kPipeRecPasses - 1].w >= 0;
+            if (kSecProduce) scx[kPipeRecPasses - 1] = fetch_section(ds.table, secn[kPipeRecPasses - 1]);
             // roll the window
             const Range rd = range_of(dvec);
             const int r0nn = carry_of(r0n, rb, rc);
@@ -615,6 +663,10 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
             s_build += w.step;
 #pragma unroll
             for (int p = 0; p < kPipeRecPasses; p++) ndn[p] = enodes[stream_elem(r0n, rb, rc, p)];
+            if (kSecProduce) {
+#pragma unroll
+                for (int p = 0; p < kPipeRecPasses; p++) secn[p] = esec[stream_elem(r0n, rb, rc, p)];
+            }
             dvec = desc_a_of(s_build + 3 * w.step);
         };
         produce(lds);
@@ -703,14 +755,22 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
                 if (sym_item) {
                     for (int q = 0; q < cnt; q++) {
                         const uint32_t pr = (q == 0) ? (item.y & 0xffffu) : (q == 1 ? (item.y >> 16) : (item.z & 0xffffu));
-                        tri3_diag_add_rec<RecLean>(lds_rec + pipe_rec_offset((int)(pr >> 4), kRec), (int)(pr & 3u), mc, blk);
+                        const double *rec = lds_rec + pipe_rec_offset((int)(pr >> 4), kRec);
+                        if (kSecConsume) tri3_diag_add_rec<RecLean>(rec, (int)(pr & 3u), rec_material_lean(rec, mc.flags), blk);
+                        else tri3_diag_add_rec<RecLean>(rec, (int)(pr & 3u), mc, blk);
                     }
                 } else {
                     for (int q = 0; q < cnt; q++) {
                         const uint32_t pr = (q == 0) ? (item.y & 0xffffu) : (q == 1 ? (item.y >> 16) : (item.z & 0xffffu));
                         const double *rec = lds_rec + pipe_rec_offset((int)(pr >> 4), kRec);
-                        if (kHasQuads) block_add_rec<true>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, blk);
-                        else tri3_block_add_rec<RecLean>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, blk);
+                        if (kSecConsume) {
+                            if (kHasQuads) block_add_rec<true>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), rec_material<true>(rec, mc.flags), blk);
+                            else tri3_block_add_rec<RecLean>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), rec_material_lean(rec, mc.flags), blk);
+                        } else if (kHasQuads) {
+                            block_add_rec<true>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, blk);
+                        } else {
+                            tri3_block_add_rec<RecLean>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, blk);
+                        }
                     }
                 }
                 stamp(2);

@@ -503,6 +503,15 @@ struct femshell_ctx {
     femshell::DevBuf<femshell::Plan::Item> items;
     femshell::DevBuf<uint32_t> item_flags;
     femshell::DevBuf<uint8_t> dmask;
+    // shell sections (femshell_set_sections): table, index per entry of slice_elem_nodes and per local element, and the view of
+    // them the kernels get.  pipe_without_sections: what femshell_set_mesh decided for the uniform material (Plan::pipe) -- a
+    // context with sections packs its items for the two-phase kernel and goes back to that layout when they are cleared.
+    bool have_sections = false, pipe_without_sections = false;
+    int32_t n_sections = 0;
+    femshell::DevBuf<femshell::SecConst> sec_table;
+    femshell::DevBuf<int32_t> slice_elem_section, elem_section;
+    femshell::DeviceSections ds{};
+    const femshell::DeviceSections *sections_or_null() const { return have_sections ? &ds : nullptr; }
     // CG state
     femshell::DevBuf<double> x, r, z, p, q, sv, partials, hist, sendbuf, ufull;
     femshell::DevBuf<double> xacc, rres; // iterative refinement of the multigrid-preconditioned solve: accumulated solution, residual

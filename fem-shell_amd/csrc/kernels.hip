@@ -41,9 +41,17 @@ int slice_grid(const DeviceMatrix &m)
     return g < cap ? g : cap;
 }
 
-void launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st)
+// lab builds (-DFEMSHELL_SECTIONS_LAB=256|512|768, assemble_kernel.hpp): parts of the sectioned pipelined kernel of triangle
+// meshes switched off, to time them; 0 in the product
+#ifndef FEMSHELL_SECTIONS_LAB
+#define FEMSHELL_SECTIONS_LAB 0
+#endif
+constexpr int kSectionsLab = FEMSHELL_SECTIONS_LAB;
+
+bool launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st, const DeviceSections *sections)
 {
     const size_t lds = (size_t)m.lds_bytes;
+    const DeviceSections ds = sections ? *sections : DeviceSections();
     static const int variant = [] {
         const char *e = getenv("FEMSHELL_ASM_WAVES"); // tuning knob: waves per SIMD the kernel is compiled for
         return e ? atoi(e) : 2;
@@ -52,8 +60,9 @@ void launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st)
     auto launch = [&](auto kernel) {
         if (lds > 64 * 1024) // beyond the default dynamic-LDS limit
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(kernel, dim3(g), dim3(256), lds, st, m, mc);
+        hipLaunchKernelGGL(kernel, dim3(g), dim3(256), lds, st, m, mc, ds);
     };
+    if (sections && (!ds.table || !ds.slice_elem_section)) return false; // (nothing launched: the caller reports it)
     if (m.pipe) { // two workgroups per CU, b and b + G/2 on the same one: their roles complement each other
         static const int pipe_cap = [] { // two workgroups per CU of this device (FEMSHELL_ASM_PIPE_GRID overrides)
             const char *e = getenv("FEMSHELL_ASM_PIPE_GRID");
@@ -67,15 +76,26 @@ void launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st)
         auto launch_pipe = [&](auto kernel) {
             if (lds > 64 * 1024)
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL(kernel, dim3(gp), dim3(256), lds, st, m, mc);
+            hipLaunchKernelGGL(kernel, dim3(gp), dim3(256), lds, st, m, mc, ds);
         };
-        if (m.n_lquad > 0) launch_pipe(k_assemble_pipe<0, true>);
-        else launch_pipe(k_assemble_pipe<0, false>);
-        return;
+        if (sections) { // (the instantiations with sections: contexts without never launch them)
+            if (m.n_lquad > 0) launch_pipe(k_assemble_pipe<0, true, true>);
+            else launch_pipe(k_assemble_pipe<kSectionsLab, false, true>);
+        } else if (m.n_lquad > 0) {
+            launch_pipe(k_assemble_pipe<0, true>);
+        } else {
+            launch_pipe(k_assemble_pipe<0, false>);
+        }
+        return true;
+    }
+    if (sections) {
+        if (m.n_lquad > 0) launch(k_assemble<2, 0, true, true>);
+        else launch(k_assemble<2, 0, false, true>);
+        return true;
     }
     if (m.n_lquad > 0) {
         launch(k_assemble<2, 0, true>);
-        return;
+        return true;
     }
     switch (variant) {
     case 1: launch(k_assemble<1, 0, false>); break;
@@ -83,6 +103,7 @@ void launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st)
     case 4: launch(k_assemble<4, 0, false>); break;
     default: launch(k_assemble<2, 0, false>); break;
     }
+    return true;
 }
 
 // Constraint word of every assembly work item (DeviceMatrix::item_flags): the assembly kernel fetches it together
@@ -143,13 +164,15 @@ void launch_rhs(const DeviceMatrix &m, const double *loads, double *F, hipStream
 // Unconstrained element matrices in the reference's variable-major ordering
 // (fem-shell.cpp:1105-1109); one lane per node block.  Parity/debug export only.
 // Elements [0,n_ltri) are triangles (9 blocks each), the rest quads (16 blocks each).
-__global__ __launch_bounds__(128) void k_element_matrices(DeviceMatrix m, MatConst mc, int first, int count, double *out)
+__global__ __launch_bounds__(128) void k_element_matrices(DeviceMatrix m, MatConst mc_ctx, DeviceSections ds, int first, int count, double *out)
 {
     const bool quads = first >= m.n_ltri;
     const int nn = quads ? 4 : 3, nb = nn * nn;
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (int64_t)count * nb) return;
     const int e = (int)(t / nb), pr = (int)(t % nb), ia = pr / nn, ib = pr % nn;
+    // the element's own material where the context has sections
+    const MatConst mc = ds.elem_section ? mat_of_section(ds.table[ds.elem_section[first + e]], mc_ctx.flags) : mc_ctx;
     double rec[kRecDoublesQuad];
     bool ok;
     if (!quads) {
@@ -183,11 +206,11 @@ __global__ __launch_bounds__(128) void k_element_matrices(DeviceMatrix m, MatCon
 }
 
 void launch_element_matrices(const DeviceMatrix &m, const MatConst &mc, int32_t first, int32_t count,
-                             double *Ke_out, hipStream_t st)
+                             double *Ke_out, hipStream_t st, const DeviceSections *sections)
 {
     const int64_t n = (int64_t)count * (first >= m.n_ltri ? 16 : 9);
-    hipLaunchKernelGGL(k_element_matrices, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, m, mc, first,
-                       count, Ke_out);
+    hipLaunchKernelGGL(k_element_matrices, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, m, mc,
+                       sections ? *sections : DeviceSections(), first, count, Ke_out);
 }
 
 // =====================================================================================

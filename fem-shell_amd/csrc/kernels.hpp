@@ -91,11 +91,12 @@ __host__ __device__ constexpr int pipe_rec_offset(int i, int rec_doubles) { retu
 
 // LDS layout of k_assemble for a plan with at most max_slice_elems element records and max_stage_rows partial-sum
 // rows per slice: [records | partial sums].  Returns the dynamic LDS size in bytes.
-inline size_t assemble_lds_layout(DeviceMatrix &m, int32_t max_slice_elems, int32_t max_stage_rows, bool has_quads)
+inline size_t assemble_lds_layout(DeviceMatrix &m, int32_t max_slice_elems, int32_t max_stage_rows, bool has_quads,
+                                  bool sections = false)
 {
     if (m.pipe) { // k_assemble_pipe: two buffers of lean records, no staging
         // (+ two doubles of padding behind every 16 records: pipe_rec_offset)
-        m.lds_rec_off = pipe_rec_offset(max_slice_elems, has_quads ? kRecDoublesQuad : RecLean::doubles);
+        m.lds_rec_off = pipe_rec_offset(max_slice_elems, has_quads ? kRecDoublesQuad : (sections ? RecLeanSec::doubles : RecLean::doubles));
         m.lds_stage_off = 0;
         m.lds_bytes = (int32_t)(2 * (size_t)m.lds_rec_off * sizeof(double));
         return (size_t)m.lds_bytes;
@@ -159,7 +160,9 @@ enum CgPhase : int {
 
 int slice_grid(const DeviceMatrix &m); // workgroups of the per-slice kernels (multiple of 8, at most 2560)
 
-void launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st);
+// sections != nullptr: a context with shell sections (m.lds_* laid out for the sectioned records: assemble_lds_layout)
+// returns false, having launched nothing, when `sections` is given without its table or indices
+bool launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st, const DeviceSections *sections = nullptr);
 void launch_rhs(const DeviceMatrix &m, const double *loads /* n_pad x 6 */, double *F, hipStream_t st);
 // fills m.item_flags from cols / dmask / pair_ptr (after every change of the Dirichlet set)
 void launch_item_flags(const DeviceMatrix &m, int64_t n_items, hipStream_t st);
@@ -168,7 +171,7 @@ void launch_block_jacobi(const DeviceMatrix &m, hipStream_t st);
 // ranks of a row partition sum up after an assembly / block-Jacobi setup
 void launch_status_flags(const int32_t *status, double *agree, hipStream_t st);
 void launch_element_matrices(const DeviceMatrix &m, const MatConst &mc, int32_t first, int32_t count,
-                             double *Ke_out, hipStream_t st);
+                             double *Ke_out, hipStream_t st, const DeviceSections *sections = nullptr);
 
 // y = K x; when partials != nullptr also partials[wg] = sum over the workgroup's rows of x*y
 // (s != nullptr: no-op once s->done != 0)

@@ -378,6 +378,149 @@ static void pack_items_pipe(const std::vector<Plan::Item> &in, std::vector<Plan:
     }
 }
 
+// Work items of the assembly kernels (Plan::items, item_ptr, max_stage_rows) and the per-slice descriptors, from the gather
+// lists of the slots, in the layout Plan::pipe asks for.  build_plan runs it once; repack_assembly_items again when a context
+// has to change the kernel that assembles an unchanged plan.
+static int plan_item_pairs()
+{
+    // contributions per item (FEMSHELL_ITEM_PAIRS overrides): 3 fills the four waves of a full-storage slice evenly (256
+    // items); with symmetric storage a structured slice has 32 diagonal slots of 6 and 96 off-diagonal slots of 2
+    // contributions, and items of 2 (192 equal items, three full waves while the fourth builds records) were measured
+    // against items of 3 (160 items): 0.904 vs 0.875 ms -- fewer items and partial-sum rows win, 3 stays
+    static const int item_pairs_env = getenv("FEMSHELL_ITEM_PAIRS") ? atoi(getenv("FEMSHELL_ITEM_PAIRS")) : 0;
+    return (item_pairs_env >= 1 && item_pairs_env <= kItemPairs) ? item_pairs_env : kItemPairs;
+}
+
+static bool pack_assembly_items(Plan &p, std::string *err)
+{
+    auto fail = [&](const std::string &m) {
+        if (err) *err = m;
+        return false;
+    };
+    const int item_pairs = plan_item_pairs();
+    p.max_stage_rows = 0;
+    p.item_ptr.assign((size_t)p.n_slices + 1, 0);
+    {
+        // chunks of slices on the host threads, each into an item list of its own, joined in slice order afterwards
+        const int nchunks_t = plan_chunks(p.n_slices, 256);
+        std::vector<RawVec<Plan::Item>> part_items((size_t)nchunks_t);
+        std::vector<int32_t> part_stage((size_t)nchunks_t, 0), part_bad((size_t)nchunks_t, 0);
+        plan_parallel(p.n_slices, 256, [&](int t, int64_t s0, int64_t s1) {
+            std::vector<Plan::Item> tmp, sorted, packed;
+            RawVec<Plan::Item> out; // (the thread's own; handed over at the end)
+            int32_t most_stage = 0;
+            out.reserve((size_t)(s1 - s0) * 168);
+            // stable order by decreasing number of contributions (0..kItemPairs): a bucket pass, no allocation
+            auto order_by_work = [&](std::vector<Plan::Item> &v, size_t begin) {
+                sorted.clear();
+                for (int np = kItemPairs; np >= 0; np--)
+                    for (size_t i = begin; i < v.size(); i++)
+                        if ((int)(v[i].z >> 16) == np) sorted.push_back(v[i]);
+                std::copy(sorted.begin(), sorted.end(), v.begin() + begin);
+            };
+            for (int64_t s = s0; s < s1; s++) {
+                tmp.clear();
+                int32_t stage = 0;
+                const int w = p.slice_width[s];
+                for (int k = 0; k < w; k++)
+                    for (int n = 0; n < kSliceNodes; n++) {
+                        const int64_t idx = Plan::slot_index(p.slice_base[s], k, n);
+                        const int32_t q0 = p.pair_ptr[idx], cnt = p.pair_ptr[idx + 1] - q0;
+                        if (cnt == 0) continue; // padding slot: its zero block is written once, when K is allocated
+                        const int nchunks = (cnt + item_pairs - 1) / item_pairs;
+                        if (nchunks > 255) {
+                            part_bad[(size_t)t] = 1;
+                            return;
+                        }
+                        const int32_t stage0 = stage;
+                        for (int c = 0; c < nchunks; c++) {
+                            const int32_t b = q0 + c * item_pairs, e = std::min(q0 + cnt, b + item_pairs);
+                            const int np = std::max(0, e - b);
+                            uint32_t pr[3] = {0, 0, 0};
+                            for (int q = 0; q < np; q++) pr[q] = p.pairs16[b + q];
+                            Plan::Item it;
+                            it.x = (uint32_t)(k * kSliceNodes + n) | ((uint32_t)c << 16) | ((uint32_t)nchunks << 24);
+                            it.y = pr[0] | (pr[1] << 16);
+                            it.z = pr[2] | ((uint32_t)np << 16);
+                            it.w = (uint32_t)(c == 0 ? stage0 : stage0 + c - 1);
+                            tmp.push_back(it);
+                        }
+                        stage += nchunks - 1;
+                    }
+                if (p.pipe) {
+                    pack_items_pipe(tmp, &packed);
+                    tmp.swap(packed);
+                    stage = 0;
+                } else if (tmp.size() <= 256) {
+                    // one round: order by decreasing work so that the waves are uniform
+                    order_by_work(tmp, 0);
+                } else {
+                    // several rounds of 256 items: a slot's chunks must share a round (they meet in LDS),
+                    // so fill rounds greedily with whole slots, then order each round by work
+                    packed.clear();
+                    size_t i = 0;
+                    while (i < tmp.size()) {
+                        const size_t round_begin = packed.size();
+                        while (i < tmp.size()) {
+                            const size_t nch = tmp[i].x >> 24;
+                            if (packed.size() - round_begin + nch > 256) break;
+                            for (size_t c = 0; c < nch; c++) packed.push_back(tmp[i + c]);
+                            i += nch;
+                        }
+                        order_by_work(packed, round_begin);
+                        if (i < tmp.size()) {
+                            Plan::Item pad{0xffffu, 0, 0, 0}; // inert item: slot 0xffff, chunk 0, 0 chunks
+                            while (packed.size() - round_begin < 256) packed.push_back(pad);
+                        }
+                    }
+                    tmp.swap(packed);
+                }
+                most_stage = std::max(most_stage, stage);
+                out.insert(out.end(), tmp.begin(), tmp.end());
+                p.item_ptr[(size_t)s + 1] = (int32_t)tmp.size(); // count; prefix sums below
+            }
+            part_stage[(size_t)t] = most_stage;
+            part_items[(size_t)t].swap(out);
+        });
+        size_t total_items = 0;
+        for (int t = 0; t < nchunks_t; t++) {
+            if (part_bad[(size_t)t]) return fail("a block slot has more than 765 contributions");
+            p.max_stage_rows = std::max(p.max_stage_rows, part_stage[(size_t)t]);
+            total_items += part_items[(size_t)t].size();
+        }
+        if (total_items > (size_t)0x7fffffff) return fail("more than 2^31 assembly work items on one rank");
+        for (int32_t s = 0; s < p.n_slices; s++) p.item_ptr[(size_t)s + 1] += p.item_ptr[(size_t)s];
+        p.items.resize(total_items);
+        std::vector<size_t> off((size_t)nchunks_t + 1, 0);
+        for (int t = 0; t < nchunks_t; t++) off[(size_t)t + 1] = off[(size_t)t] + part_items[(size_t)t].size();
+        plan_parallel(nchunks_t, 1, [&](int, int64_t t0, int64_t t1) {
+            for (int64_t t = t0; t < t1; t++) {
+                std::copy(part_items[(size_t)t].begin(), part_items[(size_t)t].end(), p.items.begin() + off[(size_t)t]);
+                RawVec<Plan::Item>().swap(part_items[(size_t)t]);
+            }
+        });
+    }
+    // ---- per-slice descriptors of the assembly kernel
+    p.slice_desc.assign((size_t)p.n_slices * 8, 0);
+    for (int32_t s = 0; s < p.n_slices; s++) {
+        int32_t *d = &p.slice_desc[(size_t)s * 8];
+        d[0] = p.slice_elem_ptr[s];
+        d[1] = p.slice_elem_ptr[s + 1] - p.slice_elem_ptr[s];
+        d[2] = p.item_ptr[s];
+        d[3] = p.item_ptr[s + 1] - p.item_ptr[s];
+        d[4] = (int32_t)(uint32_t)((uint64_t)p.slice_base[s] & 0xffffffffu);
+        d[5] = (int32_t)(uint32_t)((uint64_t)p.slice_base[s] >> 32);
+        d[6] = p.slice_width[s];
+    }
+    return true;
+}
+
+bool repack_assembly_items(Plan *plan, bool pipe, std::string *err)
+{
+    plan->pipe = pipe;
+    return pack_assembly_items(*plan, err);
+}
+
 bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t *tri, int32_t n_quad,
                 const int32_t *quad, int rank, int world, Plan *P, std::string *err, bool symmetric, bool geometric_orientation)
 {
@@ -1075,12 +1218,7 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
 
     lap("assembly work items");
     // ---- assembly work items
-    // contributions per item (FEMSHELL_ITEM_PAIRS overrides): 3 fills the four waves of a full-storage slice evenly (256
-    // items); with symmetric storage a structured slice has 32 diagonal slots of 6 and 96 off-diagonal slots of 2
-    // contributions, and items of 2 (192 equal items, three full waves while the fourth builds records) were measured
-    // against items of 3 (160 items): 0.904 vs 0.875 ms -- fewer items and partial-sum rows win, 3 stays
-    static const int item_pairs_env = getenv("FEMSHELL_ITEM_PAIRS") ? atoi(getenv("FEMSHELL_ITEM_PAIRS")) : 0;
-    const int item_pairs = (item_pairs_env >= 1 && item_pairs_env <= kItemPairs) ? item_pairs_env : kItemPairs;
+    const int item_pairs = plan_item_pairs();
     // Item layout of the pipelined kernel (k_assemble_pipe, assemble_kernel.hpp): rounds of 192 lanes, the chunks of a
     // slot in neighbouring lanes of one wave, diagonal slots in waves of their own where the round has room.  For meshes of
     // triangles whose slices leave room for two record buffers per workgroup, two workgroups per CU; FEMSHELL_ASM_PIPE=0
@@ -1123,120 +1261,8 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
             if (20 * ragged > p.n_slices) p.pipe = false;
         }
     }
-    p.item_ptr.assign((size_t)p.n_slices + 1, 0);
-    {
-        // chunks of slices on the host threads, each into an item list of its own, joined in slice order afterwards
-        const int nchunks_t = plan_chunks(p.n_slices, 256);
-        std::vector<RawVec<Plan::Item>> part_items((size_t)nchunks_t);
-        std::vector<int32_t> part_stage((size_t)nchunks_t, 0), part_bad((size_t)nchunks_t, 0);
-        plan_parallel(p.n_slices, 256, [&](int t, int64_t s0, int64_t s1) {
-            std::vector<Plan::Item> tmp, sorted, packed;
-            RawVec<Plan::Item> out; // (the thread's own; handed over at the end)
-            int32_t most_stage = 0;
-            out.reserve((size_t)(s1 - s0) * 168);
-            // stable order by decreasing number of contributions (0..kItemPairs): a bucket pass, no allocation
-            auto order_by_work = [&](std::vector<Plan::Item> &v, size_t begin) {
-                sorted.clear();
-                for (int np = kItemPairs; np >= 0; np--)
-                    for (size_t i = begin; i < v.size(); i++)
-                        if ((int)(v[i].z >> 16) == np) sorted.push_back(v[i]);
-                std::copy(sorted.begin(), sorted.end(), v.begin() + begin);
-            };
-            for (int64_t s = s0; s < s1; s++) {
-                tmp.clear();
-                int32_t stage = 0;
-                const int w = p.slice_width[s];
-                for (int k = 0; k < w; k++)
-                    for (int n = 0; n < kSliceNodes; n++) {
-                        const int64_t idx = Plan::slot_index(p.slice_base[s], k, n);
-                        const int32_t q0 = p.pair_ptr[idx], cnt = p.pair_ptr[idx + 1] - q0;
-                        if (cnt == 0) continue; // padding slot: its zero block is written once, when K is allocated
-                        const int nchunks = (cnt + item_pairs - 1) / item_pairs;
-                        if (nchunks > 255) {
-                            part_bad[(size_t)t] = 1;
-                            return;
-                        }
-                        const int32_t stage0 = stage;
-                        for (int c = 0; c < nchunks; c++) {
-                            const int32_t b = q0 + c * item_pairs, e = std::min(q0 + cnt, b + item_pairs);
-                            const int np = std::max(0, e - b);
-                            uint32_t pr[3] = {0, 0, 0};
-                            for (int q = 0; q < np; q++) pr[q] = p.pairs16[b + q];
-                            Plan::Item it;
-                            it.x = (uint32_t)(k * kSliceNodes + n) | ((uint32_t)c << 16) | ((uint32_t)nchunks << 24);
-                            it.y = pr[0] | (pr[1] << 16);
-                            it.z = pr[2] | ((uint32_t)np << 16);
-                            it.w = (uint32_t)(c == 0 ? stage0 : stage0 + c - 1);
-                            tmp.push_back(it);
-                        }
-                        stage += nchunks - 1;
-                    }
-                if (p.pipe) {
-                    pack_items_pipe(tmp, &packed);
-                    tmp.swap(packed);
-                    stage = 0;
-                } else if (tmp.size() <= 256) {
-                    // one round: order by decreasing work so that the waves are uniform
-                    order_by_work(tmp, 0);
-                } else {
-                    // several rounds of 256 items: a slot's chunks must share a round (they meet in LDS),
-                    // so fill rounds greedily with whole slots, then order each round by work
-                    packed.clear();
-                    size_t i = 0;
-                    while (i < tmp.size()) {
-                        const size_t round_begin = packed.size();
-                        while (i < tmp.size()) {
-                            const size_t nch = tmp[i].x >> 24;
-                            if (packed.size() - round_begin + nch > 256) break;
-                            for (size_t c = 0; c < nch; c++) packed.push_back(tmp[i + c]);
-                            i += nch;
-                        }
-                        order_by_work(packed, round_begin);
-                        if (i < tmp.size()) {
-                            Plan::Item pad{0xffffu, 0, 0, 0}; // inert item: slot 0xffff, chunk 0, 0 chunks
-                            while (packed.size() - round_begin < 256) packed.push_back(pad);
-                        }
-                    }
-                    tmp.swap(packed);
-                }
-                most_stage = std::max(most_stage, stage);
-                out.insert(out.end(), tmp.begin(), tmp.end());
-                p.item_ptr[(size_t)s + 1] = (int32_t)tmp.size(); // count; prefix sums below
-            }
-            part_stage[(size_t)t] = most_stage;
-            part_items[(size_t)t].swap(out);
-        });
-        size_t total_items = 0;
-        for (int t = 0; t < nchunks_t; t++) {
-            if (part_bad[(size_t)t]) return fail("a block slot has more than 765 contributions");
-            p.max_stage_rows = std::max(p.max_stage_rows, part_stage[(size_t)t]);
-            total_items += part_items[(size_t)t].size();
-        }
-        if (total_items > (size_t)0x7fffffff) return fail("more than 2^31 assembly work items on one rank");
-        for (int32_t s = 0; s < p.n_slices; s++) p.item_ptr[(size_t)s + 1] += p.item_ptr[(size_t)s];
-        p.items.resize(total_items);
-        std::vector<size_t> off((size_t)nchunks_t + 1, 0);
-        for (int t = 0; t < nchunks_t; t++) off[(size_t)t + 1] = off[(size_t)t] + part_items[(size_t)t].size();
-        plan_parallel(nchunks_t, 1, [&](int, int64_t t0, int64_t t1) {
-            for (int64_t t = t0; t < t1; t++) {
-                std::copy(part_items[(size_t)t].begin(), part_items[(size_t)t].end(), p.items.begin() + off[(size_t)t]);
-                RawVec<Plan::Item>().swap(part_items[(size_t)t]);
-            }
-        });
-    }
+    if (!pack_assembly_items(p, err)) return false;
     lap("slice descriptors");
-    // ---- per-slice descriptors of the assembly kernel
-    p.slice_desc.assign((size_t)p.n_slices * 8, 0);
-    for (int32_t s = 0; s < p.n_slices; s++) {
-        int32_t *d = &p.slice_desc[(size_t)s * 8];
-        d[0] = p.slice_elem_ptr[s];
-        d[1] = p.slice_elem_ptr[s + 1] - p.slice_elem_ptr[s];
-        d[2] = p.item_ptr[s];
-        d[3] = p.item_ptr[s + 1] - p.item_ptr[s];
-        d[4] = (int32_t)(uint32_t)((uint64_t)p.slice_base[s] & 0xffffffffu);
-        d[5] = (int32_t)(uint32_t)((uint64_t)p.slice_base[s] >> 32);
-        d[6] = p.slice_width[s];
-    }
 
     lap("halo exchange lists");
     // ---- halo exchange lists

@@ -67,6 +67,10 @@ constexpr int kItemPairs = 3;                // element contributions per assemb
 // workgroups in the 160 KiB of a CU
 constexpr int kPipeMaxSliceElems = 150;
 constexpr int kPipeMaxSliceElemsQuad = 77; // meshes with quadrilaterals: 66-double records
+// contexts with shell sections: 38-double records (RecLeanSec, shell_element.hpp), 4 * 134 * 304 B = 162,944 of 163,840 B;
+// the 66-double records carry the section in words they do not use.  A plan laid out for the pipelined kernel whose slices
+// exceed this is packed anew for the two-phase kernel when sections are set (femshell_set_sections).
+constexpr int kPipeMaxSliceElemsSections = 134;
 
 struct HaloPeer {
     int rank = -1;
@@ -181,6 +185,10 @@ void partition_bounds(int32_t n_nodes, int32_t n_tri, const int32_t *tri, int32_
 bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t *tri, int32_t n_quad,
                 const int32_t *quad, int rank, int world, Plan *plan, std::string *err, bool symmetric = false,
                 bool geometric_orientation = false);
+// Packs the assembly work items of an existing plan anew, for the pipelined kernel (pipe) or the two-phase one: items,
+// item_ptr, slice_desc, max_stage_rows and Plan::pipe change, nothing else.  The packing is deterministic, so going back
+// gives the items build_plan made.  (Contexts with shell sections whose slices exceed what the sectioned kernels take.)
+bool repack_assembly_items(Plan *plan, bool pipe, std::string *err);
 // the library's default storage: symmetric unless FEMSHELL_SYMMETRIC=0
 bool default_symmetric_storage();
 

@@ -36,6 +36,44 @@ struct MatConst {
     uint32_t pad;
 };
 
+// Shell sections (femshell_set_sections): one material per element.  A row of the section table in HBM holds what the element
+// math takes from a material -- the behaviour flags stay the context's -- and every element carries an index into the table.
+struct SecConst {
+    double tcm; // t E/(1-nu^2)
+    double cp;  // E t^3 / (12 (1-nu^2))
+    double nu;
+    double g;   // (1-nu)/2
+};
+// one row of the table: two 16-byte loads
+__device__ __forceinline__ SecConst fetch_section(const SecConst *table, int idx)
+{
+    const double2 *row = reinterpret_cast<const double2 *>(table + idx);
+    const double2 a = row[0], b = row[1];
+    SecConst r;
+    r.tcm = a.x; r.cp = a.y; r.nu = b.x; r.g = b.y;
+    return r;
+}
+// what the record builders and the block functions read of a MatConst, with t folded into cm (they use the product only)
+__host__ __device__ __forceinline__ MatConst mat_of_section(const SecConst &s, uint32_t flags)
+{
+    MatConst m;
+    m.cm = s.tcm;
+    m.cp = s.cp;
+    m.nu = s.nu;
+    m.g = s.g;
+    m.t = 1.0;
+    m.flags = flags;
+    m.pad = 0;
+    return m;
+}
+// the section table and the indices of a sectioned context as the kernels get them (a kernel argument of its own: the
+// instantiations without sections never look at it)
+struct DeviceSections {
+    const SecConst *table = nullptr;            // n_sections
+    const int32_t *slice_elem_section = nullptr; // per entry of DeviceMatrix::slice_elem_nodes
+    const int32_t *elem_section = nullptr;       // per local element (triangles, then quadrilaterals)
+};
+
 __device__ __forceinline__ double sel3(int i, double a, double b, double c)
 {
     return i == 0 ? a : (i == 1 ? b : c);
@@ -653,6 +691,59 @@ __device__ __forceinline__ void quad4_block_add_rec(const double *rec, int ia, i
             acc[6 * (3 + r) + 3 + s] += ex[r] * d_x + ey[r] * d_y + ez[r] * d_z;
         }
     }
+}
+
+// ---- records of sectioned contexts: the block functions need the element's own nu and g (and t*cm, cp for QUAD4) while
+// they walk the records in LDS, and must not fetch them from the section table (a dependent global load in the hot loop).
+// The record length stays what it is (kRecDoubles is tuned to the LDS banks, see above):
+//   meshes of triangles       nu in the kind word [16], which nothing reads when the QUAD4 code is compiled out
+//   meshes with quadrilaterals  TRI3: nu at [38], the first of the words a triangle leaves unused in a 66-double record;
+//                               QUAD4: nu, t*cm, cp at [9..11], between the frame and the kind word
+// g = (1 - nu)/2 is derived (the same expression as on the host: the same bits).
+constexpr int kSecNuTri = kRecKind, kSecNuTriWide = kRecDoubles, kSecNuQuad = 9, kSecTcmQuad = 10, kSecCpQuad = 11;
+template <bool kHasQuads> __device__ __forceinline__ void rec_put_section(double *rec, const SecConst &s, bool quad)
+{
+    if (!kHasQuads) {
+        rec[kSecNuTri] = s.nu;
+    } else if (quad) {
+        rec[kSecNuQuad] = s.nu;
+        rec[kSecTcmQuad] = s.tcm;
+        rec[kSecCpQuad] = s.cp;
+    } else {
+        rec[kSecNuTriWide] = s.nu;
+    }
+}
+template <bool kHasQuads> __device__ __forceinline__ MatConst rec_material(const double *rec, uint32_t flags)
+{
+    SecConst s;
+    if (!kHasQuads) {
+        s.nu = rec[kSecNuTri];
+        s.tcm = 0.0; // (TRI3 blocks take t*cm from the record's membrane scale and cp from its Gram tables)
+        s.cp = 0.0;
+    } else {
+        const bool quad = rec[kRecKind] == 2.0;
+        s.nu = rec[quad ? kSecNuQuad : kSecNuTriWide];
+        s.tcm = rec[kSecTcmQuad];
+        s.cp = rec[kSecCpQuad];
+    }
+    s.g = (1.0 - s.nu) / 2.0;
+    return mat_of_section(s, flags);
+}
+
+// The lean record of the pipelined kernel with sections: RecLean and nu behind it.  38 doubles = 4*19 dwords: an odd multiple of
+// a bank quad again (36 = 4*18 would put the same field of records 8 apart into the same quad, the two-way version of the
+// 40-double layout that measured 50 % slower above), and the stride k_assemble's records have.
+struct RecLeanSec {
+    static constexpr int doubles = 38, nu = RecLean::doubles;
+};
+__device__ __forceinline__ MatConst rec_material_lean(const double *rec, uint32_t flags)
+{
+    SecConst s;
+    s.nu = rec[RecLeanSec::nu];
+    s.g = (1.0 - s.nu) / 2.0;
+    s.tcm = 0.0;
+    s.cp = 0.0;
+    return mat_of_section(s, flags);
 }
 
 // dispatch on the record's element kind

@@ -312,6 +312,8 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
     out << "Read command-line arguments.......OK" << std::endl;
     try {
         ShellMesh mesh = read_mesh(p.in_filename);
+        SectionTable section_table;
+        if (p.sections_requested()) section_table = read_sections(p, mesh);
         clock.done("read mesh");
         int dims = 2;
         const InProcessCoupling::Scheme scheme = scheme_from_xml(config, &dims);
@@ -344,6 +346,7 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
         clock.done("coupling set-up, context (device, ranks)");
         mesh.loads.assign((size_t)mesh.n_nodes() * 6, 0.0);
         system.set_mesh(mesh);
+        if (p.sections_requested()) system.set_sections(section_table);
         clock.done("symbolic phase, boundary conditions");
         const std::array<int, 2> ax = dead_axis_components(deadAxis == '0' ? 'z' : deadAxis);
         int32_t probe = ifn[0];

@@ -3,7 +3,9 @@
 // users need to move between the two libMesh formats fem-shell.cpp:35-37 reads.  usage: meshConvert in out [digits]
 // An output named *.e is an ExodusII file of the mesh (write_exodus, the format of the solver's -out file) with zero
 // nodal fields, or, with a third argument "ramp", the fields u_v(node) = 1e-3 (node + 1)(v + 1): what the CPU test of
-// the writer reads back.
+// the writer reads back.  An output named *.pvtu is the VTK XML file the coupled program writes per time step (write_pvtu:
+// index + piece <stem>_0.vtu) of the undisplaced mesh, with the element tags the programs' -sections option goes by
+// (ShellMesh::elem_tag) as the cell array "section": to look at a mesh's sections, and what the CPU test of that writer parses.
 #include <cstdlib>
 #include <iostream>
 #include <string>
@@ -30,7 +32,12 @@ int main(int argc, char **argv)
                     for (int v = 0; v < 6; v++) u[6 * (size_t)n + v] = 1e-3 * (n + 1) * (v + 1);
             femshell_host::write_exodus(m, u, out);
         }
-        else throw std::runtime_error("output must be *.xda, *.xdr or *.e");
+        else if (ends_with(".pvtu")) {
+            femshell_host::ShellMesh tagged = m;
+            tagged.sections_in_use = true;
+            femshell_host::write_pvtu(tagged, std::vector<double>((size_t)m.n_nodes() * 6, 0.0), out);
+        }
+        else throw std::runtime_error("output must be *.xda, *.xdr, *.e or *.pvtu");
     } catch (const std::exception &e) {
         std::cerr << "ERROR: " << e.what() << "\n";
         return -1;

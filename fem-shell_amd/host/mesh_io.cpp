@@ -245,9 +245,11 @@ ShellMesh read_msh(const std::string &path)
                 if (!in) throw std::runtime_error(path + ": bad element line " + std::to_string(i));
                 if (nn == 3) {
                     m.order.push_back({'t', m.n_tri()});
+                    m.elem_tag.push_back((int32_t)phys);
                     for (int k = 0; k < 3; k++) m.tri.push_back(node_index(ids[k]));
                 } else if (nn == 4) {
                     m.order.push_back({'q', m.n_quad()});
+                    m.elem_tag.push_back((int32_t)phys);
                     for (int k = 0; k < 4; k++) m.quad.push_back(node_index(ids[k]));
                 } else {
                     Low l{nn, {node_index(ids[0]), nn == 2 ? node_index(ids[1]) : -1}, (int32_t)phys};
@@ -296,9 +298,9 @@ ShellMesh read_msh(const std::string &path)
 ShellMesh read_mesh(const std::string &path)
 {
     auto ends_with = [&](const char *ext) { const std::string e(ext); return path.size() >= e.size() && path.compare(path.size() - e.size(), e.size(), e) == 0; };
-    if (ends_with(".msh")) return read_msh(path);
-    if (ends_with(".xdr")) return read_xdr(path);
-    return read_xda(path);
+    ShellMesh m = ends_with(".msh") ? read_msh(path) : (ends_with(".xdr") ? read_xdr(path) : read_xda(path));
+    m.elem_tag.resize(m.order.size(), 0); // (XDA / XDR: no tags, all zero)
+    return m;
 }
 
 // ---- binary XDR: the records of the XDA file in Sun XDR encoding (RFC 4506) -----------------------------------------
@@ -664,6 +666,10 @@ void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::stri
         os << "SCALARS " << names[v] << " double 1\nLOOKUP_TABLE default\n";
         for (int32_t n = 0; n < nn; n++) os << u[6 * (size_t)n + v] << "\n";
     }
+    if (m.sections_in_use) { // (runs with -sections / -section_ids only: everything above is the file of a run without)
+        os << "CELL_DATA " << ne << "\nSCALARS section int 1\nLOOKUP_TABLE default\n";
+        for (long e = 0; e < ne; e++) os << m.tag_of((int32_t)e) << "\n";
+    }
 }
 
 // VTK XML output as libMesh's VTKIO names it (fem-shell_precice.cpp:1552-1559: <out>_NNN.pvtu per converged time step of a
@@ -681,7 +687,9 @@ void write_pvtu(const ShellMesh &m, const std::vector<double> &u, const std::str
         os << "<?xml version=\"1.0\"?>\n<VTKFile type=\"PUnstructuredGrid\" version=\"0.1\" byte_order=\"LittleEndian\">\n"
            << "  <PUnstructuredGrid GhostLevel=\"0\">\n    <PPointData>\n";
         for (const char *nm : names) os << "      <PDataArray type=\"Float64\" Name=\"" << nm << "\"/>\n";
-        os << "    </PPointData>\n    <PPoints>\n      <PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n    </PPoints>\n"
+        os << "    </PPointData>\n";
+        if (m.sections_in_use) os << "    <PCellData>\n      <PDataArray type=\"Int32\" Name=\"section\"/>\n    </PCellData>\n";
+        os << "    <PPoints>\n      <PDataArray type=\"Float64\" NumberOfComponents=\"3\"/>\n    </PPoints>\n"
            << "    <Piece Source=\"" << piece_name << "\"/>\n  </PUnstructuredGrid>\n</VTKFile>\n";
     }
     std::ofstream os(piece);
@@ -696,7 +704,13 @@ void write_pvtu(const ShellMesh &m, const std::vector<double> &u, const std::str
         for (int32_t n = 0; n < nn; n++) os << u[6 * (size_t)n + v] << "\n";
         os << "        </DataArray>\n";
     }
-    os << "      </PointData>\n      <Points>\n        <DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
+    os << "      </PointData>\n";
+    if (m.sections_in_use) {
+        os << "      <CellData>\n        <DataArray type=\"Int32\" Name=\"section\" format=\"ascii\">\n";
+        for (long e = 0; e < ne; e++) os << m.tag_of((int32_t)e) << "\n";
+        os << "        </DataArray>\n      </CellData>\n";
+    }
+    os << "      <Points>\n        <DataArray type=\"Float64\" NumberOfComponents=\"3\" format=\"ascii\">\n";
     for (int32_t n = 0; n < nn; n++)
         os << m.xyz[3 * n] + u[6 * (size_t)n] << " " << m.xyz[3 * n + 1] + u[6 * (size_t)n + 1] << " " << m.xyz[3 * n + 2] + u[6 * (size_t)n + 2] << "\n";
     os << "        </DataArray>\n      </Points>\n      <Cells>\n        <DataArray type=\"Int32\" Name=\"connectivity\" format=\"ascii\">\n";

@@ -32,6 +32,12 @@ struct ShellMesh {
     std::vector<SideBC> bcs;
     std::vector<std::pair<int32_t, int32_t>> node_bcs; // (node, boundary id): Gmsh point elements (doc/implementation.tex:103-124)
     std::vector<double> loads;    // n_nodes x 6 (already scaled by the file's factor)
+    // file order, parallel to `order`: the first tag of a Gmsh triangle / quadrangle (its physical entity: what libMesh's GmshIO
+    // makes the element's subdomain_id()); zeros from the other formats and generators (an empty vector stands for zeros).
+    // The programs' -sections option maps these tags to shell sections; -section_ids replaces them.
+    std::vector<int32_t> elem_tag;
+    bool sections_in_use = false; // the VTK writers add the tags as the integer cell array "section"
+    int32_t tag_of(int32_t e) const { return (size_t)e < elem_tag.size() ? elem_tag[(size_t)e] : 0; }
 
     int32_t n_nodes() const { return (int32_t)(xyz.size() / 3); }
     int32_t n_tri() const { return (int32_t)(tri.size() / 3); }

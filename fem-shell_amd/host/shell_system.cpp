@@ -5,7 +5,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <fstream>
+#include <sstream>
 #include <iostream>
 #include <stdexcept>
 #include <thread>
@@ -55,7 +57,9 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-d:\t Additional (debug) messages (1=on, 0=off (default))\n"
             << "-tol:\t relative residual tolerance of the CG solve (optional, default 1e-12)\n"
             << "-max_it:\t iteration limit of the CG solve (optional, default 5000)\n"
-            << "-pc_type:\t gamg (multigrid, default) | bjacobi (6x6 block-Jacobi)\n";
+            << "-pc_type:\t gamg (multigrid, default) | bjacobi (6x6 block-Jacobi)\n"
+            << "-sections:\t file of lines 'tag nu E t': material of the elements with that tag (optional; others: -nu -e -t)\n"
+            << "-section_ids:\t file with one tag per element, in place of the mesh file's tags (optional)\n";
         return false;
     }
     bool failed = false;
@@ -95,6 +99,8 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
     } else {
         p.isOutfileSet = false;
     }
+    if (const char *v = arg_after(argc, argv, "-sections")) p.sections_file = v;
+    if (const char *v = arg_after(argc, argv, "-section_ids")) p.section_ids_file = v;
     if (const char *v = arg_after(argc, argv, "-tol")) p.tol = std::atof(v);
     if (const char *v = arg_after(argc, argv, "-max_it")) p.max_it = std::atoi(v);
     // PETSc-style options the reference's users pass on the same command line (doc/implementation.tex:68-72)
@@ -266,6 +272,75 @@ void ShellSystem::set_mesh(const ShellMesh &m)
     if (!m.loads.empty()) set_forces(m.loads);
 }
 
+void ShellSystem::set_sections(const SectionTable &t)
+{
+    check(femshell_set_sections(ctx_, (int32_t)t.sections.size(), t.sections.data(), t.tri_section.empty() ? nullptr : t.tri_section.data(),
+                                t.quad_section.empty() ? nullptr : t.quad_section.data()),
+          "femshell_set_sections");
+}
+
+SectionTable read_sections(const Parameters &p, ShellMesh &mesh)
+{
+    SectionTable t;
+    t.sections.push_back({p.nu, p.em, p.thickness}); // section 0: every element whose tag is not listed
+    std::vector<int32_t> listed; // tag of section 1 + i
+    auto strip = [](std::string line) {
+        const size_t h = line.find('#');
+        if (h != std::string::npos) line.erase(h);
+        return line;
+    };
+    if (!p.sections_file.empty()) {
+        std::ifstream in(p.sections_file);
+        if (!in) throw std::runtime_error("cannot open " + p.sections_file);
+        std::string line;
+        for (int no = 1; std::getline(in, line); no++) {
+            std::istringstream is(strip(line));
+            std::string first;
+            if (!(is >> first)) continue; // blank or comment
+            char *end = nullptr;
+            const long tag = std::strtol(first.c_str(), &end, 10);
+            femshell_section s{};
+            std::string rest;
+            if (*end != '\0' || !(is >> s.nu >> s.E >> s.thickness) || (is >> rest))
+                throw std::runtime_error(p.sections_file + ": line " + std::to_string(no) + ": expected 'tag nu E t'");
+            if (std::find(listed.begin(), listed.end(), (int32_t)tag) != listed.end())
+                throw std::runtime_error(p.sections_file + ": line " + std::to_string(no) + ": tag " + std::to_string(tag) + " is listed twice");
+            listed.push_back((int32_t)tag);
+            t.sections.push_back(s);
+        }
+    }
+    const size_t ne = mesh.order.size();
+    if (!p.section_ids_file.empty()) {
+        std::ifstream in(p.section_ids_file);
+        if (!in) throw std::runtime_error("cannot open " + p.section_ids_file);
+        std::vector<int32_t> ids;
+        std::string line;
+        for (int no = 1; std::getline(in, line); no++) {
+            std::istringstream is(strip(line));
+            std::string tok;
+            while (is >> tok) {
+                char *end = nullptr;
+                const long v = std::strtol(tok.c_str(), &end, 10);
+                if (*end != '\0') throw std::runtime_error(p.section_ids_file + ": line " + std::to_string(no) + ": '" + tok + "' is not an integer");
+                ids.push_back((int32_t)v);
+            }
+        }
+        if (ids.size() != ne)
+            throw std::runtime_error(p.section_ids_file + ": " + std::to_string(ids.size()) + " ids for " + std::to_string(ne) + " elements");
+        mesh.elem_tag.swap(ids);
+    }
+    mesh.elem_tag.resize(ne, 0);
+    mesh.sections_in_use = true;
+    t.tri_section.assign((size_t)mesh.n_tri(), 0);
+    t.quad_section.assign((size_t)mesh.n_quad(), 0);
+    for (size_t e = 0; e < ne; e++) {
+        const auto it = std::find(listed.begin(), listed.end(), mesh.elem_tag[e]);
+        const int32_t s = it == listed.end() ? 0 : (int32_t)(it - listed.begin()) + 1;
+        (mesh.order[e].first == 't' ? t.tri_section : t.quad_section)[(size_t)mesh.order[e].second] = s;
+    }
+    return t;
+}
+
 void ShellSystem::set_forces(const std::vector<double> &f6)
 {
     if ((int)(f6.size() / 6) != n_nodes_) throw std::runtime_error("set_forces: need one row of 6 per mesh node");
@@ -352,11 +427,14 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         } catch (const std::exception &) {
             mesh.loads.assign((size_t)mesh.n_nodes() * 6, 0.0);
         }
+        SectionTable section_table;
+        if (p.sections_requested()) section_table = read_sections(p, mesh);
         clock.done("read mesh and loads");
         const Launch launch = Launch::from_environment();
         ShellSystem system(p, launch);
         clock.done("context (device, ranks)");
         system.set_mesh(mesh);
+        if (p.sections_requested()) system.set_sections(section_table);
         clock.done("symbolic phase, boundary conditions, loads");
         const SolveResult res = system.solve(p.tol, p.max_it);
         clock.done("assembly, preconditioner setup, solve");

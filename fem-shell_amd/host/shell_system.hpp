@@ -49,7 +49,21 @@ struct Parameters {
     // default: the multigrid.  The reference's default (PETSc's GMRES + ILU) is a stronger preconditioner than point-block
     // Jacobi, whose iteration count grows with the element count (no convergence at 4M triangles); -pc_type bjacobi opts in
     std::string pc_type = "gamg";
+    // shell sections (extension): -sections FILE, lines "tag nu E t" ('#' starts a comment): elements whose tag (Gmsh physical
+    // entity, ShellMesh::elem_tag) is listed get that material, all others -nu -e -t.  -section_ids FILE: one integer per
+    // element in file order, used in place of the mesh's tags (XDA / XDR meshes carry none).
+    std::string sections_file, section_ids_file;
+    bool sections_requested() const { return !sections_file.empty() || !section_ids_file.empty(); }
 };
+
+// what femshell_set_sections takes, from the files above: section 0 is the command line's material, the listed ones follow
+struct SectionTable {
+    std::vector<femshell_section> sections;
+    std::vector<int32_t> tri_section, quad_section;
+};
+// Reads the files (std::runtime_error with file name and line number on a malformed line), gives every element its section
+// and leaves the tags that were used in mesh.elem_tag (the output files show them as the cell array "section").
+SectionTable read_sections(const Parameters &p, ShellMesh &mesh);
 
 // One process per GPU.  How a rank learns its place: FEMSHELL_RANK / FEMSHELL_WORLD_SIZE, else the
 // launcher's variables (torchrun: RANK / WORLD_SIZE / LOCAL_RANK; Open MPI: OMPI_COMM_WORLD_*; MPICH/Slurm: PMI_RANK /
@@ -104,6 +118,7 @@ class ShellSystem {
     // mesh + boundary ids + nodal forces (what main() sets up before init(), SA:35-125)
     void set_mesh(const ShellMesh &m);
     void set_forces(const std::vector<double> &f6); // n_nodes x 6, replaces the `forces` global
+    void set_sections(const SectionTable &t);       // after set_mesh (femshell_set_mesh forgets the sections)
     // the assembly callback (SA:1160-1233); the name argument is checked like SA:1163
     void assemble_elasticity(const std::string &system_name = "Elasticity");
     // equation_systems.solve(): runs the callback if K is not current, then the Krylov solve

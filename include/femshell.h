@@ -83,6 +83,23 @@ const char *femshell_last_error(void);
 int femshell_set_mesh(femshell_ctx *ctx, int32_t n_nodes, const double *xyz, int32_t n_tri,
                       const int32_t *tri, int32_t n_quad, const int32_t *quad);
 
+typedef struct femshell_section { double nu, E, thickness; } femshell_section;
+/* extends: the global nu / em / thickness of the reference (SA:217-233, initMaterialMatrices SA:273-294) to one
+ * set per element ("shell sections": flanges thicker than the web, a doubler on a skin, an insert of another metal, a
+ * tapered thickness).  sections[n_sections]; tri_section[n_tri] / quad_section[n_quad]: index into `sections` for
+ * every element of the mesh last passed to femshell_set_mesh, in the caller's element order (NULL allowed only
+ * where that count is 0).  Every rank passes the same full arrays (as for femshell_set_mesh).  n_sections == 0
+ * returns the context to the uniform material of its femshell_config.  Only values change: the plan and the
+ * sparsity are kept, K and the multigrid hierarchy are rebuilt at the next assemble / solve.  femshell_set_mesh
+ * forgets the sections (the element count may have changed).  The behaviour flags stay the context's.
+ * FEMSHELL_ERR_INVALID (no mesh, a null array, an index outside [0, n_sections), a section that femshell_create
+ * would refuse as a config) leaves the sections that were in force untouched.
+ * A context with sections runs the sectioned instantiation of the kernel its mesh was laid out for; the pipelined one takes
+ * slices of at most 134 triangles then (longer records), and a mesh between that and the uniform limit of 150 is assembled by
+ * the two-phase kernel while it has sections.  femshell_assembly_kernel reports what a context will in fact launch. */
+int femshell_set_sections(femshell_ctx *ctx, int32_t n_sections, const femshell_section *sections,
+                          const int32_t *tri_section, const int32_t *quad_section);
+
 /* replaces: DirichletBoundary {0,20}->u,v,w and {1,21}->all six (SA:90-120).  mask6 bit v
  * fixes dof v of the node to 0.  node_ids == NULL: mask6 has one byte per node (n == n_nodes).
  * Calling it again replaces the previous set. */

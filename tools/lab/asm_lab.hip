@@ -15,11 +15,11 @@ template <int W, int F> float run(const DeviceMatrix &m, const MatConst &mc, int
     hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
     // the first ~20 launches of a process run ~12 % slow (clocks, TLBs): warm up before timing
     static bool warm = false;
-    for (int i = 0; i < (warm ? 2 : 25); i++) hipLaunchKernelGGL((k_assemble<W, F>), dim3(grid), dim3(256), m.lds_bytes, 0, m, mc);
+    for (int i = 0; i < (warm ? 2 : 25); i++) hipLaunchKernelGGL((k_assemble<W, F>), dim3(grid), dim3(256), m.lds_bytes, 0, m, mc, DeviceSections());
     warm = true;
     CK(hipDeviceSynchronize());
     CK(hipEventRecord(a));
-    for (int i = 0; i < reps; i++) hipLaunchKernelGGL((k_assemble<W, F>), dim3(grid), dim3(256), m.lds_bytes, 0, m, mc);
+    for (int i = 0; i < reps; i++) hipLaunchKernelGGL((k_assemble<W, F>), dim3(grid), dim3(256), m.lds_bytes, 0, m, mc, DeviceSections());
     CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
     float ms; CK(hipEventElapsedTime(&ms, a, b));
     return ms / reps;
@@ -82,11 +82,11 @@ int main(int argc, char **argv)
         assemble_lds_layout(m, p.max_slice_elems, 0, false);
         auto runp = [&](auto kernel, int g, int reps) {
             CK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, m.lds_bytes));
-            for (int i = 0; i < 25; i++) hipLaunchKernelGGL(kernel, dim3(g), dim3(256), m.lds_bytes, 0, m, mc);
+            for (int i = 0; i < 25; i++) hipLaunchKernelGGL(kernel, dim3(g), dim3(256), m.lds_bytes, 0, m, mc, DeviceSections());
             CK(hipDeviceSynchronize());
             hipEvent_t a, b; CK(hipEventCreate(&a)); CK(hipEventCreate(&b));
             CK(hipEventRecord(a));
-            for (int i = 0; i < reps; i++) hipLaunchKernelGGL(kernel, dim3(g), dim3(256), m.lds_bytes, 0, m, mc);
+            for (int i = 0; i < reps; i++) hipLaunchKernelGGL(kernel, dim3(g), dim3(256), m.lds_bytes, 0, m, mc, DeviceSections());
             CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
             float ms; CK(hipEventElapsedTime(&ms, a, b));
             return ms / reps;
