@@ -16,6 +16,7 @@ REORDER_MORTON = 0x10
 REORDER_RCM = 0x20
 
 KERNEL_ASSEMBLE, KERNEL_SPMV, KERNEL_CG_UPDATE, KERNEL_CG_DIRECTION = 0, 1, 2, 3
+KERNEL_LUMPED_MASS, KERNEL_MASS_SHIFT, KERNEL_NEWMARK_RHS, KERNEL_NEWMARK_UPDATE = 4, 5, 6, 7
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -27,6 +28,8 @@ SYMBOLS = [
     "femshell_amg_export", "femshell_residual", "femshell_comm_ranks", "femshell_amg_setup_stats", "femshell_amg_dense_stats", "femshell_amg_partition_info", "femshell_assembly_kernel",
     "femshell_amg_cycle_bytes", "femshell_comm_selftest", "femshell_comm_counters", "femshell_owned_nodes", "femshell_comm_bytes", "femshell_set_initial_guess",
     "femshell_amg_patch_info", "femshell_amg_symbolic_info", "femshell_pc_apply", "femshell_set_sections",
+    "femshell_set_density", "femshell_lumped_mass", "femshell_dynamics_defaults", "femshell_dynamics_begin", "femshell_dynamics_step",
+    "femshell_dynamics_accept", "femshell_dynamics_state", "femshell_dynamics_energy", "femshell_dynamics_end",
 ]
 
 
@@ -59,6 +62,10 @@ class PcOptions(C.Structure):
 class AmgLevelInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("n_coarse", C.c_int32), ("nnz_blocks", C.c_int64), ("p_blocks", C.c_int64),
                 ("lambda_max", C.c_double)]
+
+
+class DynamicsOptions(C.Structure):
+    _fields_ = [("dt", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("alpha", C.c_double)]
 
 
 PC_BLOCK_JACOBI, PC_AMG = 0, 1
@@ -151,6 +158,15 @@ def load_library():
     L.femshell_comm_bytes.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]
     L.femshell_amg_cycle_bytes.argtypes = [vp, dp, C.c_int32]
     L.femshell_amg_cycle_bytes.restype = C.c_int32
+    L.femshell_set_density.argtypes = [vp, C.c_double, C.c_int32, dp]
+    L.femshell_lumped_mass.argtypes = [vp, dp]
+    L.femshell_dynamics_defaults.argtypes = [C.POINTER(DynamicsOptions)]
+    L.femshell_dynamics_begin.argtypes = [vp, C.POINTER(DynamicsOptions), dp, dp]
+    L.femshell_dynamics_step.argtypes = [vp, C.c_double, C.c_int32, C.POINTER(SolveInfo)]
+    L.femshell_dynamics_accept.argtypes = [vp]
+    L.femshell_dynamics_state.argtypes = [vp, C.c_int32, dp, dp, dp]
+    L.femshell_dynamics_energy.argtypes = [vp, C.c_int32, dp]
+    L.femshell_dynamics_end.argtypes = [vp]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -246,6 +262,58 @@ class FemShell:
         if qs is not None and len(qs) != self.n_quad:
             raise ValueError("quad_section needs one entry per quadrilateral (%d), got %d" % (self.n_quad, len(qs)))
         _check(self._L.femshell_set_sections(self._h, len(sec), _d(sec), _i(ts), _i(qs)))
+
+    def set_density(self, rho, section_rho=None):
+        """Mass density: one value for the whole shell, or section_rho with one density per section of set_sections."""
+        if section_rho is None:
+            _check(self._L.femshell_set_density(self._h, float(rho), 0, None))
+            return
+        sr = np.ascontiguousarray(section_rho, dtype=np.float64).ravel()
+        _check(self._L.femshell_set_density(self._h, 0.0, len(sr), _d(sr)))
+
+    def lumped_mass(self):
+        """The diagonal of the lumped mass matrix, (n_nodes, 6) in the caller's numbering (not masked by the Dirichlet set)."""
+        m = np.zeros((self.n_nodes, 6))
+        _check(self._L.femshell_lumped_mass(self._h, _d(m)))
+        return m
+
+    def _node_vector(self, x, name):
+        if x is None:
+            return None
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if len(x) != 6 * self.n_nodes:
+            raise ValueError("%s needs n_nodes x 6 entries" % name)
+        return x
+
+    def dynamics_begin(self, dt, beta=0.25, gamma=0.5, alpha=0.0, u0=None, v0=None):
+        """Newmark time stepping with damping alpha M from the state (u0, v0) (None: zero) under the loads in force; while it is
+        active the matrix in HBM (export_bsr, spmv) is K + (a0 + alpha a1) M on the free dofs."""
+        o = DynamicsOptions(float(dt), float(beta), float(gamma), float(alpha))
+        _check(self._L.femshell_dynamics_begin(self._h, C.byref(o), _d(self._node_vector(u0, "u0")), _d(self._node_vector(v0, "v0"))))
+
+    def dynamics_step(self, rtol=1e-10, max_it=10000):
+        """One step from the committed state under the loads in force: the candidate state; returns the solve's info."""
+        info = SolveInfo()
+        _check(self._L.femshell_dynamics_step(self._h, float(rtol), int(max_it), C.byref(info)))
+        return {f[0]: getattr(info, f[0]) for f in SolveInfo._fields_}
+
+    def dynamics_accept(self):
+        _check(self._L.femshell_dynamics_accept(self._h))
+
+    def dynamics_state(self, candidate=False):
+        """(u, v, a), each (n_nodes, 6), of the committed state or of the candidate of the last step."""
+        u, v, a = (np.zeros((self.n_nodes, 6)) for _ in range(3))
+        _check(self._L.femshell_dynamics_state(self._h, 1 if candidate else 0, _d(u), _d(v), _d(a)))
+        return u, v, a
+
+    def dynamics_energy(self, candidate=False):
+        """(kinetic, strain) energy of the committed state or of the candidate."""
+        out = np.zeros(2)
+        _check(self._L.femshell_dynamics_energy(self._h, 1 if candidate else 0, _d(out)))
+        return float(out[0]), float(out[1])
+
+    def dynamics_end(self):
+        _check(self._L.femshell_dynamics_end(self._h))
 
     def assemble(self, wait=True):
         """wait=False: femshell_assemble_async -- enqueued only; sync(), solve() ... report a failed element."""

@@ -228,6 +228,14 @@ int finish_pending_assembly(femshell_ctx *c)
     return FEMSHELL_OK;
 }
 
+// femshell_set_mesh and femshell_set_sections forget the densities (and with them the mass matrix in HBM)
+void forget_density(femshell_ctx *c)
+{
+    c->have_density = c->mass_valid = false;
+    c->rho = 0.0;
+    c->sec_rho.clear();
+}
+
 int do_assemble(femshell_ctx *c, bool wait = true)
 {
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: no mesh set");
@@ -251,6 +259,8 @@ int do_assemble(femshell_ctx *c, bool wait = true)
     c->dm.rhs_F = c->F.p;
     if (!launch_assemble(c->dm, c->mc, c->stream, c->sections_or_null())) // K and F (k_rhs alone serves changes of the loads)
         return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: the context's sections have no table in HBM");
+    // (dynamics is active: the matrix in HBM is K_eff = K + shift M, also when K is built again -- FEMSHELL_REASSEMBLE_EACH_SOLVE)
+    if (c->dyn.active) launch_mass_shift(c->dm, c->mass.p, c->dyn.k.shift, c->stream);
     if (events) FS_HIP(hipEventRecord(c->ev1, c->stream));
     FS_HIP(hipGetLastError());
     if (wait) {
@@ -697,6 +707,9 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     c->have_mesh = false;
     c->have_sections = false; // (the element count may change)
     c->n_sections = 0;
+    c->sec_thickness.clear();
+    forget_density(c);
+    c->dyn.reset(); // (a new mesh ends dynamics)
     c->ds = DeviceSections();
     c->sec_table.release();
     c->slice_elem_section.release();
@@ -883,6 +896,7 @@ int femshell_set_dirichlet(femshell_ctx *c, int32_t n, const int32_t *node_ids, 
         if (prc) return prc;
     }
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: call femshell_set_mesh first");
+    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: not while dynamics is active (femshell_dynamics_end first)");
     const int32_t nn = c->plan.n_nodes;
     if (!node_ids && n != nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: dense form needs n == n_nodes");
     std::vector<uint8_t> m((size_t)nn, 0);
@@ -933,6 +947,7 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
         if (prc) return prc;
     }
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: call femshell_set_mesh first");
+    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: not while dynamics is active (femshell_dynamics_end first)");
     if (n_sections < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: n_sections < 0");
     Plan &p = c->plan;
     // ---- everything that can be refused is looked at before anything changes
@@ -967,7 +982,8 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
     hipStream_t st = c->stream;
     std::string err;
     if (n_sections == 0) {
-        if (!c->have_sections) return FEMSHELL_OK; // nothing was set: nothing changes
+        forget_density(c);
+        if (!c->have_sections) return FEMSHELL_OK; // nothing was set: nothing else changes
         if (c->pipe_without_sections && !p.pipe) { // back to the layout femshell_set_mesh chose: K is again what it was, bit for bit
             if (!repack_assembly_items(&p, true, &err)) return set_err(FEMSHELL_ERR_MESH, "femshell_set_sections: " + err);
             rc = upload_item_layout(c, false);
@@ -978,6 +994,7 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
         }
         c->have_sections = false;
         c->n_sections = 0;
+        c->sec_thickness.clear();
         c->ds = DeviceSections();
         c->sec_table.release();
         c->slice_elem_section.release();
@@ -1030,6 +1047,9 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
     c->ds.slice_elem_section = c->slice_elem_section.p;
     c->n_sections = n_sections;
     c->have_sections = true;
+    c->sec_thickness.resize((size_t)n_sections);
+    for (int32_t s = 0; s < n_sections; s++) c->sec_thickness[(size_t)s] = sections[s].thickness;
+    forget_density(c); // (paired with the sections that were replaced)
     c->matrix_valid = c->rhs_valid = c->jacobi_valid = false; // as a change of the Dirichlet set
     return FEMSHELL_OK;
 }
@@ -1328,7 +1348,16 @@ static int ensure_amg_hierarchy(femshell_ctx *c, double *pc_setup_s)
     return rc;
 }
 
+// dynamic: the solve of a Newmark step -- the right-hand side is F_eff, built from the F of the loads in force and the
+// committed state by k_newmark_rhs behind the (re)assembly, instead of F itself
+static int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic);
+
 int femshell_solve(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info)
+{
+    return solve_system(c, rtol, max_it, u_out, info, false);
+}
+
+static int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic)
 {
     if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: null context");
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: no mesh set");
@@ -1352,6 +1381,12 @@ int femshell_solve(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, 
     FS_HIP(c->hist.alloc((size_t)std::min<int64_t>(std::max(max_it, 1), 1 << 22))); // history of the first 4M iterations
     CgVectors v = cg_vectors(c);
     const DeviceMatrix &m = c->dm;
+    if (dynamic) {
+        femshell_ctx::Dynamics &d = c->dyn;
+        launch_newmark_rhs(m, d.k, c->mass.p, c->F.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.b.p, st);
+        FS_HIP(hipGetLastError());
+        v.b = d.b.p;
+    }
     const bool single_reduction = !use_amg && use_single_reduction(c);
     const double *x0 = c->warm_next ? c->x0.p : nullptr; // femshell_set_initial_guess: this solve's, and only this one's
     c->warm_next = false;
@@ -1490,28 +1525,36 @@ int femshell_set_initial_guess(femshell_ctx *c, const double *u0)
     return FEMSHELL_OK;
 }
 
+// a vector of the owned rows in HBM (6 per node, internal numbering) as n_nodes x 6 in the caller's numbering, on every rank
+static int gather_node_vector(femshell_ctx *c, const double *owned, double *u_out);
+
 int femshell_get_solution(femshell_ctx *c, double *u_out)
 {
     if (!c || !u_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_get_solution: null argument");
     if (!c->have_solution) return set_err(FEMSHELL_ERR_INVALID, "femshell_get_solution: no solve has run");
     int rc = select_device(c);
     if (rc) return rc;
+    return gather_node_vector(c, c->x.p, u_out);
+}
+
+static int gather_node_vector(femshell_ctx *c, const double *owned, double *u_out)
+{
     const Plan &p = c->plan;
     if (!c->comm.active()) {
         if (c->perm.empty()) {
-            FS_HIP(hipMemcpyAsync(u_out, c->x.p, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            FS_HIP(hipMemcpyAsync(u_out, owned, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             FS_HIP(hipStreamSynchronize(c->stream));
             return FEMSHELL_OK;
         }
         std::vector<double> h((size_t)p.n_own * 6); // internal numbering -> the caller's
-        FS_HIP(hipMemcpyAsync(h.data(), c->x.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(hipMemcpyAsync(h.data(), owned, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         FS_HIP(hipStreamSynchronize(c->stream));
         for (int32_t i = 0; i < p.n_own; i++) std::memcpy(u_out + 6ull * c->perm[i], &h[6ull * i], 6 * sizeof(double));
         return FEMSHELL_OK;
     }
     FS_HIP(c->ufull.alloc((size_t)p.n_nodes * 6));
     std::string e;
-    if (!comm_gather_rows(c->comm, c->x.p, c->ufull.p, c->all_begin, c->all_end, c->stream, &e))
+    if (!comm_gather_rows(c->comm, owned, c->ufull.p, c->all_begin, c->all_end, c->stream, &e))
         return set_err(FEMSHELL_ERR_COMM, e);
     if (c->perm.empty()) {
         FS_HIP(hipMemcpyAsync(u_out, c->ufull.p, (size_t)p.n_nodes * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1749,6 +1792,279 @@ int femshell_pc_apply(femshell_ctx *c, const double *r, double *z)
     return FEMSHELL_OK;
 }
 
+// ---- structural dynamics ------------------------------------------------------------------------------------------------
+
+// the diagonal of the lumped mass matrix of the owned rows in HBM (c->mass), computed where it is not there yet
+static int ensure_mass(femshell_ctx *c)
+{
+    if (c->mass_valid) return FEMSHELL_OK;
+    const Plan &p = c->plan;
+    hipStream_t st = c->stream;
+    FS_HIP(c->mass.alloc((size_t)p.n_pad * 6));
+    const double2 *sec = nullptr;
+    if (c->have_sections) {
+        std::vector<double2> table((size_t)c->n_sections);
+        for (int32_t s = 0; s < c->n_sections; s++) {
+            const double rho = c->sec_rho.empty() ? c->rho : c->sec_rho[(size_t)s], t = c->sec_thickness[(size_t)s];
+            table[(size_t)s] = make_double2(rho * t, rho * t * t * t / 12.0);
+        }
+        FS_HIP(c->sec_mass.upload(table, st));
+        FS_HIP(hipStreamSynchronize(st)); // the host table goes out of scope
+        sec = c->sec_mass.p;
+    }
+    const double t = c->cfg.thickness;
+    launch_lumped_mass(c->dm, make_double2(c->rho * t, c->rho * t * t * t / 12.0), sec, c->ds.slice_elem_section, c->mass.p, st);
+    FS_HIP(hipGetLastError());
+    c->mass_valid = true;
+    return FEMSHELL_OK;
+}
+
+// the rank's own rows of a whole vector in the caller's numbering (n_nodes x 6) into dst (n_pad x 6, padding zero)
+static int upload_owned_rows(femshell_ctx *c, const double *full, double *dst)
+{
+    const Plan &p = c->plan;
+    std::vector<double> h((size_t)p.n_pad * 6, 0.0);
+    for (int32_t i = 0; i < p.n_own; i++) {
+        const int32_t row = p.row_begin + i, node = c->perm.empty() ? row : c->perm[(size_t)row];
+        std::memcpy(&h[6ull * (size_t)i], full + 6ull * (size_t)node, 6 * sizeof(double));
+    }
+    FS_HIP(hipMemcpyAsync(dst, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(hipStreamSynchronize(c->stream)); // (h goes out of scope)
+    return FEMSHELL_OK;
+}
+
+static bool all_finite(const double *x, int64_t n)
+{
+    std::atomic<int> bad{0};
+    parallel_chunks(n, [&](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; i++)
+            if (!std::isfinite(x[i])) bad.store(1);
+    }, 1 << 18);
+    return bad.load() == 0;
+}
+
+int femshell_set_density(femshell_ctx *c, double rho, int32_t n_sections, const double *section_rho)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: null context");
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: call femshell_set_mesh first");
+    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: not while dynamics is active (femshell_dynamics_end first)");
+    if (n_sections < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: n_sections < 0");
+    if (n_sections == 0) {
+        if (!(std::isfinite(rho) && rho > 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: need a finite rho > 0");
+        c->rho = rho;
+        c->sec_rho.clear();
+    } else {
+        if (!c->have_sections || n_sections != c->n_sections)
+            return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: n_sections must be the context's section count (" +
+                                                     std::to_string(c->have_sections ? c->n_sections : 0) + ")");
+        if (!section_rho) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: section_rho is null");
+        for (int32_t s = 0; s < n_sections; s++)
+            if (!(std::isfinite(section_rho[s]) && section_rho[s] > 0.0))
+                return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: section " + std::to_string(s) + ": need a finite density > 0");
+        c->sec_rho.assign(section_rho, section_rho + n_sections);
+        c->rho = 0.0;
+    }
+    c->have_density = true;
+    c->mass_valid = false;
+    return FEMSHELL_OK;
+}
+
+int femshell_lumped_mass(femshell_ctx *c, double *m6_out)
+{
+    if (!c || !m6_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_lumped_mass: null argument");
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_lumped_mass: no mesh set");
+    if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_lumped_mass: no density set (femshell_set_density)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    rc = ensure_mass(c);
+    if (rc) return rc;
+    return gather_node_vector(c, c->mass.p, m6_out);
+}
+
+int femshell_dynamics_defaults(femshell_dynamics_options *out)
+{
+    if (!out) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_defaults: null argument");
+    out->dt = 0.0;
+    out->beta = 0.25;
+    out->gamma = 0.5;
+    out->alpha = 0.0;
+    return FEMSHELL_OK;
+}
+
+int femshell_dynamics_begin(femshell_ctx *c, const femshell_dynamics_options *opt, const double *u0, const double *v0)
+{
+    if (!c || !opt) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: null argument");
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: no mesh set");
+    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: dynamics is active already (femshell_dynamics_end first)");
+    if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: no density set (femshell_set_density)");
+    const double dt = opt->dt, beta = opt->beta, gamma = opt->gamma, alpha = opt->alpha;
+    if (!(std::isfinite(dt) && dt > 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need a finite dt > 0");
+    if (!(std::isfinite(gamma) && gamma >= 0.5)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need gamma >= 1/2");
+    // (the limit itself is allowed as written in decimals: beta 0.3025 with gamma 0.6, where 0.25 * 1.1 * 1.1 rounds upwards)
+    if (!(std::isfinite(beta) && beta * (1.0 + 1e-12) >= 0.25 * (gamma + 0.5) * (gamma + 0.5)))
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need beta >= (gamma + 1/2)^2 / 4 (the unconditionally stable schemes)");
+    if (!(std::isfinite(alpha) && alpha >= 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need a finite alpha >= 0");
+    const Plan &p = c->plan;
+    if (u0 && !all_finite(u0, 6ll * p.n_nodes)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: non-finite entry in u0");
+    if (v0 && !all_finite(v0, 6ll * p.n_nodes)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: non-finite entry in v0");
+    if (c->assembly_pending) {
+        const int prc = finish_pending_assembly(c);
+        if (prc) return prc;
+    }
+    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_dynamics_begin (assembly, halo exchange of K u0)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    rc = ensure_mass(c);
+    if (rc) return rc;
+    if (!c->matrix_valid) rc = do_assemble(c); // K itself: dynamics is not active yet
+    else if (!c->rhs_valid) rc = do_rhs(c);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    femshell_ctx::Dynamics &d = c->dyn;
+    const size_t n6 = (size_t)p.n_pad * 6;
+    for (int i = 0; i < 2; i++) {
+        FS_HIP(d.u[i].alloc(n6));
+        FS_HIP(d.v[i].alloc(n6));
+        FS_HIP(d.a[i].alloc(n6));
+    }
+    FS_HIP(d.b.alloc(n6));
+    FS_HIP(d.e_partials.alloc(3 * (size_t)kEnergyGrid));
+    FS_HIP(d.e_sums.alloc(3));
+    // the caller's vectors land in the candidate's buffers; K u0 with the K in HBM, before the shift
+    if (u0) {
+        rc = upload_owned_rows(c, u0, d.u[1].p);
+        if (rc) return rc;
+        FS_HIP(hipMemcpyAsync(c->p.p, d.u[1].p, n6 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        rc = halo_exchange(c, c->p.p, st);
+        if (rc) return rc;
+        launch_spmv(c->dm, c->p.p, c->q.p, nullptr, nullptr, st);
+    }
+    if (v0) {
+        rc = upload_owned_rows(c, v0, d.v[1].p);
+        if (rc) return rc;
+    }
+    launch_newmark_init(c->dm, c->mass.p, c->F.p, u0 ? c->q.p : nullptr, u0 ? d.u[1].p : nullptr, v0 ? d.v[1].p : nullptr, alpha, d.u[0].p,
+                        d.v[0].p, d.a[0].p, st);
+    d.k.a0 = 1.0 / (beta * dt * dt);
+    d.k.a1 = gamma / (beta * dt);
+    d.k.a2 = 1.0 / (beta * dt);
+    d.k.a3 = 1.0 / (2.0 * beta) - 1.0;
+    d.k.a4 = gamma / beta - 1.0;
+    d.k.a5 = 0.5 * dt * (gamma / beta - 2.0);
+    d.k.alpha = alpha;
+    d.k.dt = dt;
+    d.k.gamma = gamma;
+    d.k.shift = d.k.a0 + alpha * d.k.a1;
+    launch_mass_shift(c->dm, c->mass.p, d.k.shift, st); // the matrix in HBM is K_eff from here on
+    FS_HIP(hipGetLastError());
+    FS_HIP(hipStreamSynchronize(st));
+    d.cur = 0;
+    d.have_candidate = false;
+    d.active = true;
+    c->jacobi_valid = false; // block-Jacobi and the multigrid hierarchy: from K_eff, at the first step
+    c->amg.reset();
+    c->warm_next = false;
+    return FEMSHELL_OK;
+}
+
+int femshell_dynamics_step(femshell_ctx *c, double rtol, int32_t max_it, femshell_solve_info *info)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_step: null context");
+    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_step: call femshell_dynamics_begin first");
+    int rc = select_device(c);
+    if (rc) return rc;
+    femshell_ctx::Dynamics &d = c->dyn;
+    const size_t n6 = (size_t)c->plan.n_pad * 6;
+    // the solve starts from the committed u (the hand-over of femshell_set_initial_guess)
+    FS_HIP(c->x0.alloc(n6));
+    FS_HIP(hipMemcpyAsync(c->x0.p, d.u[d.cur].p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    c->warm_next = true;
+    rc = solve_system(c, rtol, max_it, nullptr, info, true);
+    if (rc) return rc;
+    launch_newmark_update(c->dm, d.k, c->x.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.u[d.cur ^ 1].p, d.v[d.cur ^ 1].p, d.a[d.cur ^ 1].p,
+                          c->stream);
+    FS_HIP(hipGetLastError());
+    FS_HIP(hipStreamSynchronize(c->stream));
+    d.have_candidate = true;
+    return FEMSHELL_OK;
+}
+
+int femshell_dynamics_accept(femshell_ctx *c)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_accept: null context");
+    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_accept: call femshell_dynamics_begin first");
+    if (!c->dyn.have_candidate) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_accept: no candidate (femshell_dynamics_step first)");
+    c->dyn.cur ^= 1; // the candidate's buffers become the committed ones: no copy
+    c->dyn.have_candidate = false;
+    return FEMSHELL_OK;
+}
+
+int femshell_dynamics_state(femshell_ctx *c, int32_t which, double *u, double *v, double *a)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_state: null context");
+    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_state: call femshell_dynamics_begin first");
+    if (which != 0 && which != 1) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_state: which must be 0 (committed) or 1 (candidate)");
+    if (which == 1 && !c->dyn.have_candidate) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_state: no candidate (femshell_dynamics_step first)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    const femshell_ctx::Dynamics &d = c->dyn;
+    const int i = which == 0 ? d.cur : d.cur ^ 1;
+    if (u) rc = gather_node_vector(c, d.u[i].p, u);
+    if (!rc && v) rc = gather_node_vector(c, d.v[i].p, v);
+    if (!rc && a) rc = gather_node_vector(c, d.a[i].p, a);
+    return rc;
+}
+
+int femshell_dynamics_energy(femshell_ctx *c, int32_t which, double out[2])
+{
+    if (!c || !out) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_energy: null argument");
+    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_energy: call femshell_dynamics_begin first");
+    if (which != 0 && which != 1) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_energy: which must be 0 (committed) or 1 (candidate)");
+    if (which == 1 && !c->dyn.have_candidate) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_energy: no candidate (femshell_dynamics_step first)");
+    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_dynamics_energy (halo exchange and all-reduce)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    if (!c->matrix_valid) {
+        rc = do_assemble(c);
+        if (rc) return rc;
+    }
+    femshell_ctx::Dynamics &d = c->dyn;
+    const int i = which == 0 ? d.cur : d.cur ^ 1;
+    hipStream_t st = c->stream;
+    // q = K_eff u through the SpMV kernel, whose input carries the ghost entries (the CG vectors are free between solves);
+    // u.K u = u.q - shift u.M u: u is zero on the constrained dofs, where K_eff has no shift
+    FS_HIP(hipMemcpyAsync(c->p.p, d.u[i].p, (size_t)c->plan.n_pad * 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    rc = halo_exchange(c, c->p.p, st);
+    if (rc) return rc;
+    launch_spmv(c->dm, c->p.p, c->q.p, nullptr, nullptr, st);
+    launch_newmark_energy(c->dm, c->mass.p, d.u[i].p, d.v[i].p, c->q.p, d.e_partials.p, d.e_sums.p, st);
+    FS_HIP(hipGetLastError());
+    if (c->comm.active()) {
+        std::string e;
+        if (!comm_allreduce_sum(c->comm, d.e_sums.p, 3, st, &e)) return set_err(FEMSHELL_ERR_COMM, e);
+    }
+    double h[3] = {0.0, 0.0, 0.0};
+    FS_HIP(hipMemcpyAsync(h, d.e_sums.p, sizeof h, hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    out[0] = 0.5 * h[0];
+    out[1] = 0.5 * h[1] - 0.5 * d.k.shift * h[2];
+    return FEMSHELL_OK;
+}
+
+int femshell_dynamics_end(femshell_ctx *c)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_end: null context");
+    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_end: dynamics is not active");
+    int rc = select_device(c);
+    if (rc) return rc;
+    FS_HIP(hipStreamSynchronize(c->stream));
+    c->dyn.reset();
+    c->matrix_valid = c->rhs_valid = c->jacobi_valid = false; // K and F again at the next use
+    c->amg.reset();
+    c->warm_next = false;
+    return FEMSHELL_OK;
+}
+
 int32_t femshell_owned_nodes(femshell_ctx *c, int32_t *ids_out)
 {
     if (!c || !c->have_mesh) return 0;
@@ -1775,6 +2091,50 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
     if (!c->have_mesh || reps <= 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no mesh or reps <= 0");
     int rc = select_device(c);
     if (rc) return rc;
+    if (which >= FEMSHELL_KERNEL_LUMPED_MASS && which <= FEMSHELL_KERNEL_NEWMARK_UPDATE) {
+        // the kernels of the dynamics, back to back between one event pair (they stream vectors only; k_lumped_mass and
+        // k_mass_shift run once per mesh and per dt)
+        if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no density set");
+        if (which != FEMSHELL_KERNEL_LUMPED_MASS && !c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: dynamics is not active");
+        rc = ensure_mass(c);
+        if (rc) return rc;
+        hipStream_t st = c->stream;
+        femshell_ctx::Dynamics &d = c->dyn;
+        const Plan &p = c->plan;
+        const double t = c->cfg.thickness;
+        FS_HIP(hipStreamSynchronize(st));
+        FS_HIP(hipEventRecord(c->ev0, st));
+        for (int32_t i = 0; i < reps; i++) {
+            if (which == FEMSHELL_KERNEL_LUMPED_MASS)
+                launch_lumped_mass(c->dm, make_double2(c->rho * t, c->rho * t * t * t / 12.0), c->have_sections ? c->sec_mass.p : nullptr,
+                                   c->ds.slice_elem_section, c->mass.p, st);
+            else if (which == FEMSHELL_KERNEL_MASS_SHIFT) launch_mass_shift(c->dm, c->mass.p, d.k.shift, st);
+            else if (which == FEMSHELL_KERNEL_NEWMARK_RHS) launch_newmark_rhs(c->dm, d.k, c->mass.p, c->F.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.b.p, st);
+            else launch_newmark_update(c->dm, d.k, c->x.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.u[d.cur ^ 1].p, d.v[d.cur ^ 1].p, d.a[d.cur ^ 1].p, st);
+        }
+        FS_HIP(hipEventRecord(c->ev1, st));
+        FS_HIP(hipStreamSynchronize(st));
+        FS_HIP(hipGetLastError());
+        float ms = 0.f;
+        FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *mean_ms_out = (double)ms / reps;
+        if (which == FEMSHELL_KERNEL_MASS_SHIFT) {
+            c->matrix_valid = c->jacobi_valid = false; // (the shift was added `reps` times)
+            c->amg.reset();
+        }
+        if (which == FEMSHELL_KERNEL_NEWMARK_UPDATE) d.have_candidate = false;
+        if (bytes_out) {
+            const double n = p.n_own, ne = p.n_ltri() + p.n_lquad();
+            // mass: node ids of the slices' element lists (16 B per entry, about six entries per element on a structured mesh:
+            // counted as listed), coordinates once per node, 48 B written; shift: 48 B of M, the six diagonal words read and
+            // written, the mask; right-hand side: M, F, u, v, a read, b written; update: x, u, v, a read, u', v', a' written
+            *bytes_out = which == FEMSHELL_KERNEL_LUMPED_MASS ? 16.0 * (double)p.slice_elem_nodes.size() / 4.0 + 24.0 * n + 48.0 * n + (c->have_sections ? 4.0 * ne : 0.0)
+                         : which == FEMSHELL_KERNEL_MASS_SHIFT ? (48.0 + 96.0 + 1.0) * n
+                         : which == FEMSHELL_KERNEL_NEWMARK_RHS ? (6.0 * 48.0 + 1.0) * n
+                                                                : (7.0 * 48.0 + 1.0) * n;
+        }
+        return FEMSHELL_OK;
+    }
     if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->matrix_valid) {
         rc = do_assemble(c);
         if (rc) return rc;

@@ -512,6 +512,34 @@ struct femshell_ctx {
     femshell::DevBuf<int32_t> slice_elem_section, elem_section;
     femshell::DeviceSections ds{};
     const femshell::DeviceSections *sections_or_null() const { return have_sections ? &ds : nullptr; }
+    // structural dynamics (femshell_set_density, femshell_dynamics_*).  The densities are the caller's; the diagonal of the lumped
+    // mass matrix lies in HBM (owned rows, internal numbering) once it has been asked for, until mesh, sections or density change.
+    std::vector<double> sec_thickness; // thickness of every section (the table in HBM keeps products only)
+    bool have_density = false, mass_valid = false;
+    double rho = 0.0;
+    std::vector<double> sec_rho;       // per section, or empty: rho for every element
+    femshell::DevBuf<double> mass;
+    femshell::DevBuf<double2> sec_mass; // {rho t, rho t^3 / 12} per section
+    struct Dynamics {
+        bool active = false, have_candidate = false;
+        femshell::NewmarkCoef k{};
+        int cur = 0; // u[cur], v[cur], a[cur]: committed; [cur ^ 1]: candidate (femshell_dynamics_accept swaps)
+        femshell::DevBuf<double> u[2], v[2], a[2], b, e_partials, e_sums;
+        void reset() // drops the state and gives its buffers back
+        {
+            for (int i = 0; i < 2; i++) {
+                u[i].release();
+                v[i].release();
+                a[i].release();
+            }
+            b.release();
+            e_partials.release();
+            e_sums.release();
+            active = have_candidate = false;
+            k = femshell::NewmarkCoef{};
+            cur = 0;
+        }
+    } dyn;
     // CG state
     femshell::DevBuf<double> x, r, z, p, q, sv, partials, hist, sendbuf, ufull;
     femshell::DevBuf<double> xacc, rres; // iterative refinement of the multigrid-preconditioned solve: accumulated solution, residual

@@ -258,6 +258,36 @@ void launch_cgcg_init(const DeviceMatrix &m, const CgVectors &v, hipStream_t st)
 // rows add the transposed products of their in-lists
 void launch_cgcg_update(const DeviceMatrix &m, const CgVectors &v, hipStream_t st, int step = -1, bool gather = false);
 
+// ---- structural dynamics (femshell_dynamics_*): lumped mass and the vector kernels of a Newmark step.  One lane per node, 48
+// bytes per node and vector, no LDS, no barriers; every kernel is row-local (owned rows of the rank).
+struct NewmarkCoef {
+    double a0, a1, a2, a3, a4, a5; // include/femshell.h
+    double alpha, dt, gamma;
+    double shift;                  // a0 + alpha a1: K_eff = K + shift M on the free dofs
+};
+// mass[n_pad][6]: the diagonal of the lumped mass matrix of the owned rows (0 on the padding rows).  rho_t = {rho t, rho t^3/12} of
+// the uniform material; sec_mass != nullptr: one such pair per section, the element's index from slice_elem_section (where the
+// sectioned assembly kernels take it)
+void launch_lumped_mass(const DeviceMatrix &m, double2 rho_t, const double2 *sec_mass, const int32_t *slice_elem_section, double *mass,
+                        hipStream_t st);
+// vals(diagonal slot of row a)(i, i) += shift * mass[a][i] on the free dofs of the owned rows (both storages: the diagonal block is
+// slot 0 of its row and its diagonal words belong to the upper triangle)
+void launch_mass_shift(const DeviceMatrix &m, const double *mass, double shift, hipStream_t st);
+// begin: u = mask(u0), v = mask(v0) (nullptr: 0), a = mask((F - alpha M v - Ku) / M) with Ku = K u0 (nullptr: 0)
+void launch_newmark_init(const DeviceMatrix &m, const double *mass, const double *F, const double *Ku, const double *u0, const double *v0,
+                         double alpha, double *u, double *v, double *a, hipStream_t st);
+// b = mask(F + M [(a0 u + a2 v + a3 a) + alpha (a1 u + a4 v + a5 a)]): the dynamic sibling of k_rhs (F is its output)
+void launch_newmark_rhs(const DeviceMatrix &m, const NewmarkCoef &k, const double *mass, const double *F, const double *u, const double *v,
+                        const double *a, double *b, hipStream_t st);
+// candidate state from the solve's x: u' = mask(x), a' = a0 (u' - u) - a2 v - a3 a, v' = v + dt [(1 - gamma) a + gamma a']
+void launch_newmark_update(const DeviceMatrix &m, const NewmarkCoef &k, const double *x, const double *u, const double *v, const double *a,
+                           double *u1, double *v1, double *a1, hipStream_t st);
+constexpr int kEnergyGrid = 256; // workgroups (= partial sums per quantity) of launch_newmark_energy
+// partials[3][kEnergyGrid]: per workgroup the sums of v.Mv, u.q (q = K_eff u) and u.Mu over its stretch of the owned rows, then
+// out3[j] = the partials of quantity j added in index order by one lane (fixed order: the result is reproducible)
+void launch_newmark_energy(const DeviceMatrix &m, const double *mass, const double *u, const double *v, const double *q, double *partials,
+                           double *out3, hipStream_t st);
+
 // halo: gather owned entries of p into a contiguous send buffer (width doubles per node: 6 for the vectors of the solve;
 // the multigrid setup of row-partitioned contexts sends rows of 1, 36 and more doubles the same way)
 void launch_pack(const double *p, const int32_t *send_nodes, int32_t count, double *sendbuf, hipStream_t st, int width = 6);

@@ -288,7 +288,11 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
             << "-axis:\t (preCICE) dead axis ([x,y,z] optional)\n"
             << "-steps:\t stop after this many time steps (optional)\n"
             << "-fluid:\t dummy fluid geometry: tower (fluid_solver.cpp, default) or edge (forces on the interface's\n"
-            << "\t\t minimal-first-coordinate edge, for other meshes)\n";
+            << "\t\t minimal-first-coordinate edge, for other meshes)\n"
+            << "-rho:\t mass density: every time step is a Newmark step of length -dt (structural dynamics; optional,\n"
+            << "\t\t without it every step is a static solve)\n"
+            << "-newmark:\t beta gamma of Newmark's method (with -rho; default 0.25 0.5)\n"
+            << "-damping:\t mass-proportional damping C = A M (with -rho; default 0)\n";
         out << "Read command-line arguments.......FAILED" << std::endl;
         return -1;
     }
@@ -347,6 +351,11 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
         mesh.loads.assign((size_t)mesh.n_nodes() * 6, 0.0);
         system.set_mesh(mesh);
         if (p.sections_requested()) system.set_sections(section_table);
+        if (p.dynamics_requested()) {
+            system.dynamics_begin(p, deltaT); // from rest, no loads yet
+            out << "Structural dynamics: Newmark steps of dt = " << deltaT << " (beta = " << p.newmark_beta << ", gamma = " << p.newmark_gamma
+                << ", damping = " << p.damping << ", rho = " << p.rho << ")" << std::endl;
+        }
         clock.done("symbolic phase, boundary conditions");
         const std::array<int, 2> ax = dead_axis_components(deadAxis == '0' ? 'z' : deadAxis);
         int32_t probe = ifn[0];
@@ -375,11 +384,11 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
             precice::SolverInterface real("STRUCTURE", config, launch.rank, launch.world_size);
             out << "preCICE configured..." << std::endl;
             log = run_coupled_structure(real, system, mesh, deadAxis, deltaT, p.tol, p.max_it, probe, ax[0],
-                                        stepsv ? std::atoi(stepsv) : -1, launch.rank == 0 ? out : quiet, p.debug, write_step);
+                                        stepsv ? std::atoi(stepsv) : -1, launch.rank == 0 ? out : quiet, p.debug, write_step, p.dynamics_requested());
         } else
 #endif
             log = run_coupled_structure(interface, system, mesh, deadAxis, deltaT, p.tol, p.max_it, probe, ax[0],
-                                        stepsv ? std::atoi(stepsv) : -1, launch.rank == 0 ? out : quiet, p.debug, write_step);
+                                        stepsv ? std::atoi(stepsv) : -1, launch.rank == 0 ? out : quiet, p.debug, write_step, p.dynamics_requested());
         if (launch.rank != 0) return 0;
         clock.done("coupling loop (assembly, preconditioner setup, solves, per-step output)");
         {
@@ -395,6 +404,12 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
             << " s, solves " << log.solve_seconds << " s" << std::endl;
         for (size_t i = 0; i < log.tip_displacement.size(); i++)
             out << "tip[" << i << "] node " << probe << " = " << log.tip_displacement[i] << "\n";
+        if (p.dynamics_requested()) // (the dynamic history with every digit: what a comparison with another driver of the library needs)
+            for (size_t i = 0; i < log.tip_displacement.size(); i++) {
+                char line[96];
+                snprintf(line, sizeof line, "tip_dynamic[%zu] node %d = %.17g\n", i, (int)probe, log.tip_displacement[i]);
+                out << line;
+            }
         if (p.isOutfileSet) {
             const std::vector<double> sols = system.build_solution_vector();
             write_exodus(mesh, sols, p.out_filename + ".e");

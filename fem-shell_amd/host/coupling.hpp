@@ -143,7 +143,8 @@ template <class Interface>
 CoupledRunLog run_coupled_structure(Interface &interface, ShellSystem &system, const ShellMesh &mesh, char deadAxis,
                                     double deltaT, double tol, int max_it, int32_t probe_node, int probe_dof,
                                     int max_time_steps, std::ostream &out, bool debug = false,
-                                    const std::function<void(int, const std::vector<double> &)> &on_time_step = nullptr)
+                                    const std::function<void(int, const std::vector<double> &)> &on_time_step = nullptr,
+                                    bool dynamic = false)
 {
     CoupledStructure cs;
     cs.init(mesh, interface.getDimensions(), deadAxis);
@@ -166,10 +167,13 @@ CoupledRunLog run_coupled_structure(Interface &interface, ShellSystem &system, c
     int t = 0;
     while (interface.isCouplingOngoing() && (max_time_steps < 0 || t < max_time_steps)) {
         if (interface.isActionRequired(actionWriteIterationCheckpoint()))
-            interface.fulfilledAction(actionWriteIterationCheckpoint()); // quasi-static: nothing to save (PC:260-265)
+            interface.fulfilledAction(actionWriteIterationCheckpoint()); // quasi-static: nothing to save (PC:260-265);
+                                                                         // dynamic: the library keeps the committed state
         // "the magic": new displacements for the current interface forces (PC:271)
         system.set_forces(cs.loads_from_forces(mesh.n_nodes()));
-        const SolveResult res = system.solve(tol, max_it);
+        // (dynamic, -rho: one Newmark step of length deltaT from the committed state; a coupling iteration that repeats
+        //  computes the step again from that state, the converged one commits it below)
+        const SolveResult res = dynamic ? system.dynamics_step(tol, max_it) : system.solve(tol, max_it);
         log.solve_seconds += res.info.solve_seconds;
         log.assemble_seconds += res.info.assemble_seconds;
         log.assemblies += res.info.assemble_seconds > 0.0 ? 1 : 0;
@@ -187,6 +191,7 @@ CoupledRunLog run_coupled_structure(Interface &interface, ShellSystem &system, c
             interface.fulfilledAction(actionReadIterationCheckpoint());
         } else {
             out << "Advancing in time, finished timestep: " << t << std::endl;
+            if (dynamic) system.dynamics_accept();
             if (on_time_step) on_time_step(t, sols); // write output files (if desired), PC:392-393
             t++;
             cs.accept_time_step(sols);

@@ -2,6 +2,7 @@
 #include "shell_system.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -59,7 +60,14 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-max_it:\t iteration limit of the CG solve (optional, default 5000)\n"
             << "-pc_type:\t gamg (multigrid, default) | bjacobi (6x6 block-Jacobi)\n"
             << "-sections:\t file of lines 'tag nu E t': material of the elements with that tag (optional; others: -nu -e -t)\n"
-            << "-section_ids:\t file with one tag per element, in place of the mesh file's tags (optional)\n";
+            << "-section_ids:\t file with one tag per element, in place of the mesh file's tags (optional)\n"
+            << "-rho:\t mass density: structural dynamics, -steps Newmark steps of length -dt under the force file's loads as a\n"
+            << "\t step load at t = 0; writes <out>_history.txt, lines 't u v w' of the probe node (optional)\n"
+            << "-dt:\t time step length (with -rho)\n"
+            << "-steps:\t number of time steps (with -rho)\n"
+            << "-probe:\t node of the history (optional, default: the node of largest load)\n"
+            << "-newmark:\t beta gamma of Newmark's method (optional, default 0.25 0.5)\n"
+            << "-damping:\t mass-proportional damping C = A M (optional, default 0)\n";
         return false;
     }
     bool failed = false;
@@ -127,6 +135,55 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             p.pc_type = "pbjacobi";
         } else if (!ok) {
             err << "ERROR: -pc_type " << p.pc_type << " is not available (jacobi|bjacobi|pbjacobi -> 6x6 block-Jacobi, gamg|amg|ml|hypre|mg -> multigrid)\n";
+            failed = true;
+        }
+    }
+    // structural dynamics: everything that can be refused is refused here, before any device is touched
+    if (has_flag(argc, argv, "-rho")) {
+        const char *v = arg_after(argc, argv, "-rho");
+        p.rho = v ? std::atof(v) : 0.0;
+        if (!(std::isfinite(p.rho) && p.rho > 0.0)) {
+            err << "ERROR: -rho must be a density > 0!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-dt")) {
+        const char *v = arg_after(argc, argv, "-dt");
+        p.dt = v ? std::atof(v) : 0.0;
+        if (!(std::isfinite(p.dt) && p.dt > 0.0)) {
+            err << "ERROR: -dt must be a time step length > 0!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-steps")) {
+        const char *v = arg_after(argc, argv, "-steps");
+        p.steps = v ? std::atoi(v) : 0;
+        if (!has_flag(argc, argv, "-dt")) {
+            err << "ERROR: -steps needs a time step length, -dt!\n";
+            failed = true;
+        }
+    }
+    if (const char *v = arg_after(argc, argv, "-probe")) p.probe = std::atoi(v);
+    if (has_flag(argc, argv, "-newmark")) {
+        const char *b = nullptr, *g = nullptr;
+        for (int i = 1; i + 2 < argc; i++)
+            if (std::strcmp(argv[i], "-newmark") == 0) {
+                b = argv[i + 1];
+                g = argv[i + 2];
+            }
+        p.newmark_beta = b ? std::atof(b) : 0.0;
+        p.newmark_gamma = g ? std::atof(g) : 0.0;
+        // (the unconditionally stable schemes; the limit itself as written in decimals, e.g. 0.3025 0.6)
+        if (!(p.newmark_gamma >= 0.5) || !(p.newmark_beta * (1.0 + 1e-12) >= 0.25 * (p.newmark_gamma + 0.5) * (p.newmark_gamma + 0.5))) {
+            err << "ERROR: -newmark beta gamma needs gamma >= 1/2 and beta >= (gamma + 1/2)^2 / 4!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-damping")) {
+        const char *v = arg_after(argc, argv, "-damping");
+        p.damping = v ? std::atof(v) : -1.0;
+        if (!(std::isfinite(p.damping) && p.damping >= 0.0)) {
+            err << "ERROR: -damping must be >= 0!\n";
             failed = true;
         }
     }
@@ -373,6 +430,33 @@ SolveResult ShellSystem::solve(double tol, int max_it)
 
 const std::vector<double> &ShellSystem::build_solution_vector() { return sols_; }
 
+void ShellSystem::dynamics_begin(const Parameters &p, double dt)
+{
+    check(femshell_set_density(ctx_, p.rho, 0, nullptr), "femshell_set_density");
+    femshell_dynamics_options o;
+    check(femshell_dynamics_defaults(&o), "femshell_dynamics_defaults");
+    o.dt = dt;
+    o.beta = p.newmark_beta;
+    o.gamma = p.newmark_gamma;
+    o.alpha = p.damping;
+    check(femshell_dynamics_begin(ctx_, &o, nullptr, nullptr), "femshell_dynamics_begin");
+    sols_.assign((size_t)n_nodes_ * 6, 0.0);
+}
+
+SolveResult ShellSystem::dynamics_step(double tol, int max_it)
+{
+    SolveResult r;
+    check(femshell_dynamics_step(ctx_, tol, max_it, &r.info), "femshell_dynamics_step");
+    sols_.assign((size_t)n_nodes_ * 6, 0.0);
+    check(femshell_dynamics_state(ctx_, 1, sols_.data(), nullptr, nullptr), "femshell_dynamics_state");
+    r.iterations = (unsigned)r.info.iterations;
+    r.final_residual = r.info.rel_residual;
+    r.converged = r.info.converged == 1;
+    return r;
+}
+
+void ShellSystem::dynamics_accept() { check(femshell_dynamics_accept(ctx_), "femshell_dynamics_accept"); }
+
 namespace {
 double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 } // namespace
@@ -416,6 +500,17 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         out << "Read command-line arguments.......FAILED" << std::endl;
         return -1;
     }
+    // the stand-alone program's dynamics needs all three of -rho -dt -steps (still before any device is touched)
+    if (p.dynamics_requested() && (p.dt <= 0.0 || p.steps <= 0)) {
+        err << "ERROR: -rho needs -dt and -steps (a number of time steps > 0)!\n";
+        out << "Read command-line arguments.......FAILED" << std::endl;
+        return -1;
+    }
+    if (!p.dynamics_requested() && (has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps"))) {
+        err << "ERROR: -dt / -steps need a density, -rho!\n";
+        out << "Read command-line arguments.......FAILED" << std::endl;
+        return -1;
+    }
     try {
         ShellMesh mesh = read_mesh(p.in_filename);
         out << " Mesh Information:\n  n_nodes()=" << mesh.n_nodes() << "\n  n_elem()=" << mesh.n_tri() + mesh.n_quad()
@@ -436,7 +531,56 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         system.set_mesh(mesh);
         if (p.sections_requested()) system.set_sections(section_table);
         clock.done("symbolic phase, boundary conditions, loads");
-        const SolveResult res = system.solve(p.tol, p.max_it);
+        SolveResult res;
+        if (p.dynamics_requested()) {
+            // the force file's loads as a step load at t = 0, from rest: p.steps Newmark steps, the probe node's history
+            int32_t probe = p.probe;
+            if (probe < 0) { // the node of largest load (the force's norm; the first of equals)
+                probe = 0;
+                double best = -1.0;
+                for (int32_t n = 0; n < mesh.n_nodes(); n++) {
+                    const double *f = &mesh.loads[6 * (size_t)n];
+                    const double norm = std::sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
+                    if (norm > best) {
+                        best = norm;
+                        probe = n;
+                    }
+                }
+            }
+            if (probe >= mesh.n_nodes()) throw std::runtime_error("-probe: the mesh has no node " + std::to_string(probe));
+            system.dynamics_begin(p, p.dt);
+            std::ofstream hist;
+            if (launch.rank == 0) {
+                hist.open((p.isOutfileSet ? p.out_filename : std::string("out")) + "_history.txt");
+                if (!hist) throw std::runtime_error("cannot write the history file");
+            }
+            long cg_iterations = 0;
+            bool all_converged = true;
+            for (int n = 1; n <= p.steps; n++) {
+                const SolveResult step = system.dynamics_step(p.tol, p.max_it);
+                system.dynamics_accept();
+                cg_iterations += step.iterations;
+                all_converged = all_converged && step.converged;
+                if (n == 1) res = step; // (assembly and preconditioner setup happen in the first step)
+                else res.info.solve_seconds += step.info.solve_seconds;
+                res.iterations = step.iterations;
+                res.final_residual = step.final_residual;
+                if (launch.rank == 0) {
+                    const double *s = &system.build_solution_vector()[6 * (size_t)probe];
+                    char line[160];
+                    snprintf(line, sizeof line, "%.17g %.17g %.17g %.17g\n", n * p.dt, s[0], s[1], s[2]);
+                    hist << line;
+                }
+            }
+            res.converged = all_converged;
+            if (launch.rank == 0)
+                out << "Structural dynamics: " << p.steps << " Newmark steps of dt = " << p.dt << " (beta = " << p.newmark_beta << ", gamma = "
+                    << p.newmark_gamma << ", damping = " << p.damping << ", rho = " << p.rho << "), " << cg_iterations
+                    << " CG iterations, history of node " << probe << " in " << (p.isOutfileSet ? p.out_filename : std::string("out"))
+                    << "_history.txt" << std::endl;
+        } else {
+            res = system.solve(p.tol, p.max_it);
+        }
         clock.done("assembly, preconditioner setup, solve");
         {
             char note[160];

@@ -54,6 +54,14 @@ struct Parameters {
     // element in file order, used in place of the mesh's tags (XDA / XDR meshes carry none).
     std::string sections_file, section_ids_file;
     bool sections_requested() const { return !sections_file.empty() || !section_ids_file.empty(); }
+    // structural dynamics (extension): -rho R turns the time loop into Newmark steps of the library (femshell_dynamics_*) with
+    // -newmark B G (default 1/4 1/2) and mass-proportional damping -damping A; -dt / -steps: length and number of the steps
+    // (the coupled program's own -dt / -steps).  -probe NODE: the node whose history the stand-alone program writes.
+    double rho = 0.0; // 0: no dynamics
+    double dt = 0.0;
+    int steps = 0, probe = -1;
+    double newmark_beta = 0.25, newmark_gamma = 0.5, damping = 0.0;
+    bool dynamics_requested() const { return rho > 0.0; }
 };
 
 // what femshell_set_sections takes, from the files above: section 0 is the command line's material, the listed ones follow
@@ -125,6 +133,12 @@ class ShellSystem {
     SolveResult solve(double tol, int max_it);
     // sols[6*node + var] on every rank (SA:141, 163-169)
     const std::vector<double> &build_solution_vector();
+    // structural dynamics: density -rho, then Newmark steps of length dt from rest under the loads in force.  dynamics_step
+    // computes the candidate of the step (again from the same committed state when it is called twice: a repeated coupling
+    // iteration) and leaves its displacements in build_solution_vector(); dynamics_accept commits it.
+    void dynamics_begin(const Parameters &p, double dt);
+    SolveResult dynamics_step(double tol, int max_it);
+    void dynamics_accept();
     femshell_ctx *handle() { return ctx_; }
 
   private:

@@ -300,6 +300,56 @@ int femshell_set_initial_guess(femshell_ctx *ctx, const double *u0);
 /* ||r||/||b|| after each iteration of the last solve; returns the count written (<= cap) */
 int32_t femshell_residual_history(femshell_ctx *ctx, double *hist, int32_t cap);
 
+/* ---- structural dynamics: lumped mass and Newmark time stepping ------------------------
+ * extends: the reference treats every load as static (its thesis names a mass matrix, a damping matrix and nodal velocities and
+ * accelerations as future development; the coupled adapter's time loop, PC:271, is a fresh static solve per step).
+ *
+ * Mass density.  n_sections == 0: `rho` is the density of the whole shell (paired with the thickness of the femshell_config, or with
+ * every section's own thickness when the context has sections).  Otherwise n_sections must equal the section count of the context
+ * and section_rho[s] is the density of section s.  Every density must be finite and > 0; FEMSHELL_ERR_INVALID leaves the densities
+ * that were in force untouched.  femshell_set_mesh and femshell_set_sections forget the densities.
+ *
+ * The mass matrix M is LUMPED (diagonal): a TRI3 element of area A = |(b-a) x (c-a)| / 2 gives each of its three nodes
+ * rho t A / 3 on u, v, w and rho t^3/12 A / 3 on tx, ty, tz; a QUAD4 with diagonals d1, d2 has A = |d1 x d2| / 2 and gives a quarter
+ * of rho t A and of rho t^3/12 A to each of its four nodes.  Both parts are multiples of the identity per node: M needs no
+ * local-to-global rotation and is positive definite on every dof, rotations and drilling included.  The sums run over the
+ * elements in a fixed order without atomics: M is bitwise reproducible, like K. */
+int femshell_set_density(femshell_ctx *ctx, double rho, int32_t n_sections, const double *section_rho);
+/* m6_out[n_nodes][6]: the diagonal of M in the caller's numbering, NOT masked by the Dirichlet set; on a row-partitioned context
+ * every rank receives all rows (gathered like the solution). */
+int femshell_lumped_mass(femshell_ctx *ctx, double *m6_out);
+
+/* Newmark's method with mass-proportional damping C = alpha M:  M a + C v + K u = F(t).
+ *   a0 = 1/(beta dt^2), a1 = gamma/(beta dt), a2 = 1/(beta dt), a3 = 1/(2 beta) - 1, a4 = gamma/beta - 1, a5 = dt/2 (gamma/beta - 2)
+ *   K_eff = K + (a0 + alpha a1) M on the free dofs (constrained rows keep what the assembly wrote)
+ *   F_eff = mask(F_{n+1} + M [(a0 u + a2 v + a3 a) + alpha (a1 u + a4 v + a5 a)]),  K_eff u' = F_eff
+ *   a' = a0 (u' - u) - a2 v - a3 a,  v' = v + dt [(1 - gamma) a + gamma a']
+ *   initial acceleration on the free dofs: M^-1 (F_0 - alpha M v_0 - K u_0);  u, v, a are 0 on constrained dofs.
+ * Only the unconditionally stable schemes are accepted: dt > 0, gamma >= 1/2, beta >= (gamma + 1/2)^2 / 4, alpha >= 0.
+ *
+ * femshell_dynamics_begin (u0, v0: n_nodes x 6 in the caller's numbering, every rank passes the whole vectors; NULL = 0) assembles
+ * K if needed, computes the initial acceleration from the loads in force and adds the shift to the diagonal of K in HBM.
+ * WHILE DYNAMICS IS ACTIVE THE MATRIX IN HBM IS K_eff: femshell_export_bsr, femshell_spmv, femshell_residual and femshell_solve
+ * see K_eff; block-Jacobi and the multigrid hierarchy are built from it at the first step (once per dt).  femshell_set_loads
+ * stays allowed (F_{n+1} of the next step); femshell_set_dirichlet, femshell_set_sections, femshell_set_density and a second
+ * femshell_dynamics_begin return FEMSHELL_ERR_INVALID; femshell_set_mesh ends dynamics.
+ *
+ * femshell_dynamics_step solves for the CANDIDATE state (u', v', a') of the step from the committed state to t + dt, the solve
+ * started from the committed u; calling it again without femshell_dynamics_accept recomputes the candidate from the same committed
+ * state (the iteration checkpoint of an implicit coupling), bit for bit when nothing changed.  femshell_dynamics_accept commits
+ * the candidate.  femshell_get_solution returns the last candidate u.  femshell_dynamics_state copies out u, v, a (each
+ * n_nodes x 6 or NULL; which = 0: committed, 1: candidate), gathered to every rank like the solution.  femshell_dynamics_energy:
+ * out[0] = v.M v / 2, out[1] = u.K u / 2 (the K without the shift), sums in a fixed order.  femshell_dynamics_end drops the
+ * state; K and F are assembled again at the next use and a static solve is what a fresh context gives. */
+typedef struct femshell_dynamics_options { double dt, beta, gamma, alpha; } femshell_dynamics_options;
+int femshell_dynamics_defaults(femshell_dynamics_options *out); /* beta 1/4, gamma 1/2, alpha 0, dt 0 (to be set) */
+int femshell_dynamics_begin(femshell_ctx *ctx, const femshell_dynamics_options *opt, const double *u0, const double *v0);
+int femshell_dynamics_step(femshell_ctx *ctx, double rtol, int32_t max_it, femshell_solve_info *info);
+int femshell_dynamics_accept(femshell_ctx *ctx);
+int femshell_dynamics_state(femshell_ctx *ctx, int32_t which, double *u, double *v, double *a);
+int femshell_dynamics_energy(femshell_ctx *ctx, int32_t which, double out[2]);
+int femshell_dynamics_end(femshell_ctx *ctx);
+
 /* ---- parity / debug exports (single-rank contexts) --------------------------------- */
 
 /* element matrices in the reference's variable-major element ordering Ke(n*alpha+i, n*beta+j)
@@ -364,7 +414,12 @@ typedef enum femshell_kernel {
     FEMSHELL_KERNEL_ASSEMBLE = 0, /* element stiffness + block-row gather into K */
     FEMSHELL_KERNEL_SPMV = 1,     /* q = K p with fused p.q */
     FEMSHELL_KERNEL_CG_UPDATE = 2,/* x,r update + block-Jacobi apply + dots */
-    FEMSHELL_KERNEL_CG_DIRECTION = 3 /* p = z + beta p */
+    FEMSHELL_KERNEL_CG_DIRECTION = 3, /* p = z + beta p */
+    /* structural dynamics (a density must be set; the last three need femshell_dynamics_begin): launched back to back */
+    FEMSHELL_KERNEL_LUMPED_MASS = 4,  /* k_lumped_mass */
+    FEMSHELL_KERNEL_MASS_SHIFT = 5,   /* k_mass_shift (the shifts add up: K is assembled again at the next use) */
+    FEMSHELL_KERNEL_NEWMARK_RHS = 6,  /* k_newmark_rhs */
+    FEMSHELL_KERNEL_NEWMARK_UPDATE = 7 /* k_newmark_update (a candidate from whatever the solution vector holds; not committed) */
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
