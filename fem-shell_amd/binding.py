@@ -17,6 +17,7 @@ REORDER_RCM = 0x20
 
 KERNEL_ASSEMBLE, KERNEL_SPMV, KERNEL_CG_UPDATE, KERNEL_CG_DIRECTION = 0, 1, 2, 3
 KERNEL_LUMPED_MASS, KERNEL_MASS_SHIFT, KERNEL_NEWMARK_RHS, KERNEL_NEWMARK_UPDATE = 4, 5, 6, 7
+KERNEL_SPMM, KERNEL_GRAM, KERNEL_BLOCK_COMBINE = 8, 9, 10
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -30,6 +31,7 @@ SYMBOLS = [
     "femshell_amg_patch_info", "femshell_amg_symbolic_info", "femshell_pc_apply", "femshell_set_sections",
     "femshell_set_density", "femshell_lumped_mass", "femshell_dynamics_defaults", "femshell_dynamics_begin", "femshell_dynamics_step",
     "femshell_dynamics_accept", "femshell_dynamics_state", "femshell_dynamics_energy", "femshell_dynamics_end",
+    "femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram",
 ]
 
 
@@ -66,6 +68,18 @@ class AmgLevelInfo(C.Structure):
 
 class DynamicsOptions(C.Structure):
     _fields_ = [("dt", C.c_double), ("beta", C.c_double), ("gamma", C.c_double), ("alpha", C.c_double)]
+
+
+class ModalOptions(C.Structure):
+    _fields_ = [("n_modes", C.c_int32), ("guard", C.c_int32), ("max_it", C.c_int32), ("reserved", C.c_int32),
+                ("tol", C.c_double), ("shift", C.c_double)]
+
+
+class ModalInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("block", C.c_int32), ("restarts", C.c_int32),
+                ("fused_product", C.c_int32), ("pc_type", C.c_int32), ("residual_max", C.c_double),
+                ("seconds_total", C.c_double), ("seconds_product", C.c_double), ("seconds_precond", C.c_double),
+                ("seconds_gram", C.c_double), ("seconds_update", C.c_double), ("pc_setup_seconds", C.c_double)]
 
 
 PC_BLOCK_JACOBI, PC_AMG = 0, 1
@@ -167,6 +181,10 @@ def load_library():
     L.femshell_dynamics_state.argtypes = [vp, C.c_int32, dp, dp, dp]
     L.femshell_dynamics_energy.argtypes = [vp, C.c_int32, dp]
     L.femshell_dynamics_end.argtypes = [vp]
+    L.femshell_modal_defaults.argtypes = [C.POINTER(ModalOptions)]
+    L.femshell_modes.argtypes = [vp, C.POINTER(ModalOptions), dp, dp, dp, C.POINTER(ModalInfo)]
+    L.femshell_spmm.argtypes = [vp, C.c_int32, dp, dp]
+    L.femshell_modal_gram.argtypes = [vp, C.c_int32, dp, C.c_int32, dp, C.c_int32, dp]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -314,6 +332,41 @@ class FemShell:
 
     def dynamics_end(self):
         _check(self._L.femshell_dynamics_end(self._h))
+
+    def modes(self, n_modes, tol=1e-6, shift=0.0, guard=4, max_it=500, want_modes=True):
+        """The n_modes lowest pairs of K x = lambda M x on the free dofs (femshell_modes; a density must be set): returns
+        (lam[n_modes] ascending, modes (n_modes, n_nodes, 6) M-orthonormal or None, residuals[n_modes], info dict).  shift > 0
+        solves with K + shift M (an unconstrained shell); lam comes back with the shift subtracted."""
+        o = ModalOptions(int(n_modes), int(guard), int(max_it), 0, float(tol), float(shift))
+        nm = max(int(n_modes), 0)
+        lam = np.zeros(nm)
+        res = np.zeros(nm)
+        modes = np.zeros((nm, self.n_nodes, 6)) if want_modes else None
+        info = ModalInfo()
+        _check(self._L.femshell_modes(self._h, C.byref(o), _d(lam), _d(modes), _d(res), C.byref(info)))
+        return lam, modes, res, {f[0]: getattr(info, f[0]) for f in ModalInfo._fields_}
+
+    def spmm(self, X):
+        """Y = K X for a block X of shape (n_cols, n_nodes * 6) (or (n_cols, n_nodes, 6)): femshell_spmm"""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        shape = X.shape
+        X = X.reshape(shape[0], -1)
+        if X.shape[1] != 6 * self.n_nodes:
+            raise ValueError("X needs n_nodes x 6 entries per column")
+        Y = np.zeros_like(X)
+        _check(self._L.femshell_spmm(self._h, X.shape[0], _d(X), _d(Y)))
+        return Y.reshape(shape)
+
+    def modal_gram(self, A, B, weighted):
+        """A^T diag(w) B by the Gram kernel of modes(): A (qa, n_nodes * 6), B (qb, n_nodes * 6), columns as rows of the arrays;
+        weighted: w = the lumped mass, else 1.  Returns (qa, qb)."""
+        A = np.ascontiguousarray(A, dtype=np.float64).reshape(len(A), -1)
+        B = np.ascontiguousarray(B, dtype=np.float64).reshape(len(B), -1)
+        if A.shape[1] != 6 * self.n_nodes or B.shape[1] != 6 * self.n_nodes:
+            raise ValueError("A and B need n_nodes x 6 entries per column")
+        G = np.zeros((len(A), len(B)))
+        _check(self._L.femshell_modal_gram(self._h, len(A), _d(A), len(B), _d(B), 1 if weighted else 0, _d(G)))
+        return G
 
     def assemble(self, wait=True):
         """wait=False: femshell_assemble_async -- enqueued only; sync(), solve() ... report a failed element."""

@@ -3,6 +3,7 @@
 // runs in the kernels of kernels.hip; there is no CPU fallback anywhere in this library.
 #include "amg_device.hpp"
 #include "context.hpp"
+#include "modal.hpp"
 #include "reorder.hpp"
 #include "trace.hpp"
 
@@ -1716,6 +1717,66 @@ int femshell_spmv(femshell_ctx *c, const double *x, double *y)
     return FEMSHELL_OK;
 }
 
+// n_cols columns of n_nodes x 6 in the caller's numbering -> a block in HBM (column j at dst + j * ld; padding and ghost space zero)
+static int upload_block(femshell_ctx *c, int32_t n_cols, const double *X, femshell::DevBuf<double> *dst)
+{
+    const Plan &p = c->plan;
+    const size_t ld = (size_t)p.n_local_nodes() * 6;
+    FS_HIP(dst->alloc((size_t)n_cols * ld));
+    FS_HIP(dst->zero(c->stream));
+    std::vector<double> xi; // internal numbering when the library renumbered the nodes
+    for (int32_t j = 0; j < n_cols; j++) {
+        const double *xj = X + (size_t)j * p.n_nodes * 6;
+        if (!c->perm.empty()) {
+            xi.resize((size_t)p.n_own * 6);
+            for (int32_t i = 0; i < p.n_own; i++) std::memcpy(&xi[6ull * i], xj + 6ull * c->perm[i], 6 * sizeof(double));
+            xj = xi.data();
+        }
+        FS_HIP(hipMemcpyAsync(dst->p + (size_t)j * ld, xj, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        FS_HIP(hipStreamSynchronize(c->stream)); // (xi is filled again)
+    }
+    return FEMSHELL_OK;
+}
+// ... and back: the owned rows of n_cols columns of a block in HBM as n_nodes x 6 each, the caller's numbering
+static int download_block(femshell_ctx *c, int32_t n_cols, const double *src, double *Y)
+{
+    const Plan &p = c->plan;
+    const size_t ld = (size_t)p.n_local_nodes() * 6;
+    std::vector<double> yi;
+    for (int32_t j = 0; j < n_cols; j++) {
+        double *yj = Y + (size_t)j * p.n_nodes * 6;
+        if (!c->perm.empty()) yi.resize((size_t)p.n_own * 6);
+        FS_HIP(hipMemcpyAsync(yi.empty() ? yj : yi.data(), src + (size_t)j * ld, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(hipStreamSynchronize(c->stream));
+        for (int32_t i = 0; i < p.n_own && !yi.empty(); i++) std::memcpy(yj + 6ull * c->perm[i], &yi[6ull * i], 6 * sizeof(double));
+    }
+    return FEMSHELL_OK;
+}
+
+int femshell_spmm(femshell_ctx *c, int32_t n_cols, const double *X, double *Y)
+{
+    if (!c || !X || !Y) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: null argument");
+    if (n_cols < 1 || n_cols > kModalMaxCols) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: n_cols must be in 1 .. 96");
+    if (c->assembly_pending) {
+        const int prc = finish_pending_assembly(c);
+        if (prc) return prc;
+    }
+    if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: call femshell_assemble first");
+    if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_spmm: single-rank contexts only");
+    int rc = select_device(c);
+    if (rc) return rc;
+    const Plan &p = c->plan;
+    const int64_t ld = (int64_t)p.n_local_nodes() * 6;
+    DevBuf<double> dx, dy, tb;
+    rc = upload_block(c, n_cols, X, &dx);
+    if (rc) return rc;
+    FS_HIP(dy.alloc((size_t)n_cols * (size_t)ld));
+    if (c->dm.symmetric) FS_HIP(tb.alloc((size_t)kSpmmMaxCols * (size_t)p.total_slots() * 6));
+    block_product(c->dm, dx.p, dy.p, ld, n_cols, tb.p, p.total_slots() * 6, c->stream, nullptr);
+    FS_HIP(hipGetLastError());
+    return download_block(c, n_cols, dy.p, Y);
+}
+
 int femshell_residual(femshell_ctx *c, const double *x, double *r)
 {
     if (!c || !x || !r) return set_err(FEMSHELL_ERR_INVALID, "femshell_residual: null argument");
@@ -2065,6 +2126,156 @@ int femshell_dynamics_end(femshell_ctx *c)
     return FEMSHELL_OK;
 }
 
+// ---- modal analysis (modal.cpp, modal.hip) ----------------------------------------------------------------------------------
+
+int femshell_modal_defaults(femshell_modal_options *out)
+{
+    if (!out) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_defaults: null argument");
+    out->n_modes = 6;
+    out->guard = 4;
+    out->max_it = 500;
+    out->reserved = 0;
+    out->tol = 1e-6;
+    out->shift = 0.0;
+    return FEMSHELL_OK;
+}
+
+int femshell_modal_gram(femshell_ctx *c, int32_t qa, const double *A, int32_t qb, const double *B, int32_t weighted, double *G)
+{
+    if (!c || !A || !B || !G) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_gram: null argument");
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_gram: no mesh set");
+    if (qa < 1 || qa > kModalMaxCols || qb < 1 || qb > kModalMaxCols) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_gram: qa, qb must be in 1 .. 96");
+    if (weighted && !c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_gram: no density set (femshell_set_density)");
+    if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_modal_gram: single-rank contexts only");
+    int rc = select_device(c);
+    if (rc) return rc;
+    if (weighted && (rc = ensure_mass(c))) return rc;
+    DevBuf<double> da, db, partials, dg;
+    if ((rc = upload_block(c, qa, A, &da))) return rc;
+    if ((rc = upload_block(c, qb, B, &db))) return rc;
+    FS_HIP(partials.alloc((size_t)kGramGrid * qa * qb));
+    FS_HIP(dg.alloc((size_t)qa * qb));
+    launch_gram(c->dm, qa, da.p, qb, db.p, (int64_t)c->plan.n_local_nodes() * 6, weighted ? c->mass.p : nullptr, partials.p, dg.p, c->stream);
+    FS_HIP(hipGetLastError());
+    FS_HIP(hipMemcpyAsync(G, dg.p, (size_t)qa * qb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(hipStreamSynchronize(c->stream));
+    return FEMSHELL_OK;
+}
+
+int femshell_modes(femshell_ctx *c, const femshell_modal_options *opt, double *lambda_out, double *modes_out, double *residual_out,
+                   femshell_modal_info *info)
+{
+    if (!c || !opt || !lambda_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: null argument");
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: no mesh set");
+    if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: no density set (femshell_set_density)");
+    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: not while dynamics is active (femshell_dynamics_end first)");
+    if (opt->n_modes < 1 || opt->guard < 0 || opt->n_modes + opt->guard > kModalMaxBlock)
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: need n_modes >= 1, guard >= 0 and n_modes + guard <= 32");
+    if (!(std::isfinite(opt->tol) && opt->tol > 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: need a finite tol > 0");
+    if (!(std::isfinite(opt->shift) && opt->shift >= 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: need a finite shift >= 0");
+    if (opt->max_it < 1) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: max_it < 1");
+    if (c->cfg.world_size != 1)
+        return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_modes: single-rank contexts only (row-partitioned modal analysis is not implemented)");
+    const Plan &p = c->plan;
+    const int mb = opt->n_modes + opt->guard;
+    {
+        int64_t fixed = 0;
+        for (uint8_t b : c->dmask_global) fixed += __builtin_popcount((unsigned)(b & 0x3Fu));
+        if (6ll * p.n_nodes - fixed < 3ll * mb)
+            return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: fewer than 3 (n_modes + guard) free dofs");
+    }
+    if (c->assembly_pending) {
+        const int prc = finish_pending_assembly(c);
+        if (prc) return prc;
+    }
+    TraceRange trace("femshell_modes");
+    const double t_begin = wall_s();
+    int rc = select_device(c);
+    if (rc) return rc;
+    rc = ensure_mass(c);
+    if (rc) return rc;
+    if (!c->matrix_valid || (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)) rc = do_assemble(c); // K itself
+    else if (!c->rhs_valid) rc = do_rhs(c);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    const bool shifted = opt->shift > 0.0;
+    // from here on the matrix in HBM is K + shift M; whatever happens, it is gone when the call returns (femshell_dynamics_end)
+    auto leave = [&](int code) {
+        if (shifted) {
+            (void)hipStreamSynchronize(st);
+            c->matrix_valid = c->rhs_valid = c->jacobi_valid = false;
+            c->amg.reset();
+        }
+        return code;
+    };
+    if (shifted) {
+        launch_mass_shift(c->dm, c->mass.p, opt->shift, st);
+        c->jacobi_valid = false;
+        c->amg.reset();
+        if (hipGetLastError() != hipSuccess) return leave(set_err(FEMSHELL_ERR_HIP, "femshell_modes: the mass shift could not be launched"));
+    }
+    double pc_setup_s = 0.0;
+    if (!c->jacobi_valid && (rc = do_jacobi(c))) return leave(rc);
+    if (c->pc.type == FEMSHELL_PC_AMG && (rc = ensure_amg_hierarchy(c, &pc_setup_s))) return leave(rc);
+
+    ModalProblem mp;
+    mp.dm = c->dm;
+    mp.mass = c->mass.p;
+    mp.ld = (int64_t)p.n_local_nodes() * 6;
+    mp.total_slots = p.total_slots();
+    mp.stream = st;
+    mp.block_jacobi = c->pc.type != FEMSHELL_PC_AMG;
+    if (!mp.block_jacobi) mp.precond = [c](const double *r, double *z) { return amg_apply(c, r, z, nullptr, false); };
+    mp.n_modes = opt->n_modes;
+    mp.guard = opt->guard;
+    mp.max_it = opt->max_it;
+    mp.tol = opt->tol;
+    mp.shift = opt->shift;
+    DevBuf<int32_t> node_ids;
+    if (!c->perm.empty()) {
+        if (hipSuccess != node_ids.upload(c->perm, st) || hipSuccess != hipStreamSynchronize(st))
+            return leave(set_err(FEMSHELL_ERR_HIP, "femshell_modes: upload of the node numbering failed"));
+        mp.node_ids = node_ids.p;
+    }
+    ModalResult res;
+    std::unique_ptr<ModalWork, ModalWorkDeleter> work;
+    rc = modal_lobpcg(mp, &res, &work);
+    if (rc) return leave(rc);
+
+    for (int j = 0; j < opt->n_modes; j++) lambda_out[j] = res.theta[(size_t)j] - opt->shift;
+    if (residual_out)
+        for (int j = 0; j < opt->n_modes; j++) residual_out[j] = res.residual[(size_t)j];
+    if (modes_out) {
+        rc = download_block(c, opt->n_modes, res.X, modes_out);
+        if (rc) return leave(rc);
+        const size_t n6 = (size_t)p.n_nodes * 6;
+        for (int j = 0; j < opt->n_modes; j++) { // the entry of largest magnitude (lowest index on ties) is positive
+            double *x = modes_out + (size_t)j * n6;
+            size_t big = 0;
+            for (size_t i = 1; i < n6; i++)
+                if (std::fabs(x[i]) > std::fabs(x[big])) big = i;
+            if (x[big] < 0.0)
+                for (size_t i = 0; i < n6; i++) x[i] = -x[i];
+        }
+    }
+    if (info) {
+        info->iterations = res.iterations;
+        info->converged = res.converged;
+        info->block = res.block;
+        info->restarts = res.restarts;
+        info->fused_product = res.fused_product;
+        info->pc_type = c->pc.type;
+        info->residual_max = res.residual_max;
+        info->seconds_product = res.seconds_product;
+        info->seconds_precond = res.seconds_precond;
+        info->seconds_gram = res.seconds_gram;
+        info->seconds_update = res.seconds_update;
+        info->pc_setup_seconds = pc_setup_s;
+        info->seconds_total = wall_s() - t_begin;
+    }
+    return leave(FEMSHELL_OK);
+}
+
 int32_t femshell_owned_nodes(femshell_ctx *c, int32_t *ids_out)
 {
     if (!c || !c->have_mesh) return 0;
@@ -2132,6 +2343,65 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
                          : which == FEMSHELL_KERNEL_MASS_SHIFT ? (48.0 + 96.0 + 1.0) * n
                          : which == FEMSHELL_KERNEL_NEWMARK_RHS ? (6.0 * 48.0 + 1.0) * n
                                                                 : (7.0 * 48.0 + 1.0) * n;
+        }
+        return FEMSHELL_OK;
+    }
+    if (which >= FEMSHELL_KERNEL_SPMM && which <= FEMSHELL_KERNEL_BLOCK_COMBINE) {
+        // the block kernels of the modal analysis on scratch blocks of hashed vectors, back to back between one event pair
+        if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_time_kernel: the block kernels run on single-rank contexts");
+        if (which == FEMSHELL_KERNEL_GRAM && !c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no density set");
+        const char *e = getenv("FEMSHELL_TIME_KERNEL_COLS");
+        const int nc = e ? atoi(e) : 4;
+        if (nc < 1 || nc > kModalMaxBlock) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: FEMSHELL_TIME_KERNEL_COLS must be in 1 .. 32");
+        if (which == FEMSHELL_KERNEL_GRAM && (rc = ensure_mass(c))) return rc;
+        if (which == FEMSHELL_KERNEL_SPMM && !c->matrix_valid && (rc = do_assemble(c))) return rc;
+        hipStream_t st = c->stream;
+        const Plan &p = c->plan;
+        const int64_t ld = (int64_t)p.n_local_nodes() * 6;
+        const int q = 3 * nc, n_out = 2 * nc;
+        DevBuf<double> S, Y, tb, partials, G, coef;
+        FS_HIP(S.alloc((size_t)q * (size_t)ld));
+        FS_HIP(S.zero(st));
+        launch_modal_init(c->dm, nullptr, which == FEMSHELL_KERNEL_SPMM ? nc : q, S.p, ld, st);
+        if (which == FEMSHELL_KERNEL_SPMM) {
+            FS_HIP(Y.alloc((size_t)nc * (size_t)ld));
+            if (c->dm.symmetric) FS_HIP(tb.alloc((size_t)kSpmmMaxCols * (size_t)p.total_slots() * 6));
+        } else if (which == FEMSHELL_KERNEL_GRAM) {
+            FS_HIP(partials.alloc((size_t)kGramGrid * q * q));
+            FS_HIP(G.alloc((size_t)q * q));
+        } else {
+            FS_HIP(Y.alloc((size_t)n_out * (size_t)ld));
+            const std::vector<double> ones((size_t)q * n_out, 1.0 / q);
+            FS_HIP(coef.upload(ones, st));
+            FS_HIP(hipStreamSynchronize(st)); // (the host array goes out of scope)
+        }
+        CombineSources src;
+        src.S[0] = S.p;
+        src.C[0] = coef.p;
+        src.q[0] = q;
+        int fused = 0;
+        FS_HIP(hipStreamSynchronize(st));
+        FS_HIP(hipEventRecord(c->ev0, st));
+        for (int32_t i = 0; i < reps; i++) {
+            if (which == FEMSHELL_KERNEL_SPMM) block_product(c->dm, S.p, Y.p, ld, nc, tb.p, p.total_slots() * 6, st, &fused);
+            else if (which == FEMSHELL_KERNEL_GRAM) launch_gram(c->dm, q, S.p, q, S.p, ld, c->mass.p, partials.p, G.p, st);
+            else launch_block_combine(c->dm, src, n_out, n_out, Y.p, ld, st);
+        }
+        FS_HIP(hipEventRecord(c->ev1, st));
+        FS_HIP(hipStreamSynchronize(st));
+        FS_HIP(hipGetLastError());
+        float ms = 0.f;
+        FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *mean_ms_out = (double)ms / reps;
+        if (bytes_out) {
+            const double n = p.n_own;
+            // product: every stored block once per pass of four columns (fused) or once per column, indices alike, x read and y
+            // written per column (the transposed products beside the slots are overhead of the method, as in bytes_spmv); Gram:
+            // the operand and the mass once (A = B); combine: 3c columns read, 2c written
+            const double passes = fused ? (double)((nc + spmm_pass_cols(c->dm) - 1) / spmm_pass_cols(c->dm)) : (double)nc;
+            *bytes_out = which == FEMSHELL_KERNEL_SPMM ? passes * (bytes_spmv(c) - 96.0 * n) + 96.0 * n * nc
+                         : which == FEMSHELL_KERNEL_GRAM ? 48.0 * n * (q + 1)
+                                                         : 48.0 * n * (q + n_out);
         }
         return FEMSHELL_OK;
     }

@@ -639,7 +639,7 @@ void write_meshgen_files(const MeshGenArgs &a, const std::string &name)
     }
 }
 
-void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::string &path)
+void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::string &path, const std::vector<PointVectors> *point_vectors)
 {
     std::ofstream os(path);
     if (!os) throw std::runtime_error("cannot write " + path);
@@ -666,6 +666,15 @@ void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::stri
         os << "SCALARS " << names[v] << " double 1\nLOOKUP_TABLE default\n";
         for (int32_t n = 0; n < nn; n++) os << u[6 * (size_t)n + v] << "\n";
     }
+    if (point_vectors)
+        for (const PointVectors &a : *point_vectors) {
+            os << "VECTORS " << a.name << " double\n";
+            char line[96];
+            for (int32_t n = 0; n < nn; n++) {
+                snprintf(line, sizeof line, "%.17g %.17g %.17g\n", a.xyz[3 * (size_t)n], a.xyz[3 * (size_t)n + 1], a.xyz[3 * (size_t)n + 2]);
+                os << line;
+            }
+        }
     if (m.sections_in_use) { // (runs with -sections / -section_ids only: everything above is the file of a run without)
         os << "CELL_DATA " << ne << "\nSCALARS section int 1\nLOOKUP_TABLE default\n";
         for (long e = 0; e < ne; e++) os << m.tag_of((int32_t)e) << "\n";

@@ -94,7 +94,12 @@ void write_meshgen_files(const MeshGenArgs &a, const std::string &name);
 // u, v, w, tx, ty, tz, written as a classic netCDF (CDF-2) file by hand -- the image has no netCDF library (mesh_io.cpp)
 void write_exodus(const ShellMesh &m, const std::vector<double> &u6, const std::string &path);
 // legacy-VTK dump of the same content (kept beside the ExodusII file: every viewer reads it)
-void write_vtk(const ShellMesh &m, const std::vector<double> &u6, const std::string &path);
+// point_vectors: further point arrays of three components (the mode shapes of FEM-shell -modes), written with every digit
+struct PointVectors {
+    std::string name;
+    std::vector<double> xyz; // n_nodes x 3
+};
+void write_vtk(const ShellMesh &m, const std::vector<double> &u6, const std::string &path, const std::vector<PointVectors> *point_vectors = nullptr);
 // <stem>.pvtu + <stem>_0.vtu: the VTK XML pair libMesh's VTKIO writes per time step of a serial coupled run
 // (fem-shell_precice.cpp:1552-1559); path must end in .pvtu
 void write_pvtu(const ShellMesh &m, const std::vector<double> &u6, const std::string &path);

@@ -67,7 +67,11 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-steps:\t number of time steps (with -rho)\n"
             << "-probe:\t node of the history (optional, default: the node of largest load)\n"
             << "-newmark:\t beta gamma of Newmark's method (optional, default 0.25 0.5)\n"
-            << "-damping:\t mass-proportional damping C = A M (optional, default 0)\n";
+            << "-damping:\t mass-proportional damping C = A M (optional, default 0)\n"
+            << "-modes:\t with -rho: the N lowest natural frequencies and mode shapes instead of a solve (N in 1 .. 28); writes\n"
+            << "\t <out>_modes.txt, lines 'index lambda f residual', and the shapes as point arrays mode_<k>_u / mode_<k>_r of <out>.vtk\n"
+            << "-modes_tol:\t tolerance of the pairs' residuals (with -modes, default 1e-6)\n"
+            << "-modes_shift:\t shift S >= 0: solves with K + S M (with -modes; an unconstrained shell needs S > 0; default 0)\n";
         return false;
     }
     bool failed = false;
@@ -184,6 +188,43 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
         p.damping = v ? std::atof(v) : -1.0;
         if (!(std::isfinite(p.damping) && p.damping >= 0.0)) {
             err << "ERROR: -damping must be >= 0!\n";
+            failed = true;
+        }
+    }
+    // modal analysis: refused here like the dynamics options
+    if (has_flag(argc, argv, "-modes")) {
+        const char *v = arg_after(argc, argv, "-modes");
+        p.modes = v ? std::atoi(v) : 0;
+        if (p.modes < 1 || p.modes > 28) {
+            err << "ERROR: -modes must be a number of modes in 1 .. 28!\n";
+            p.modes = 0;
+            failed = true;
+        }
+        if (!has_flag(argc, argv, "-rho")) {
+            err << "ERROR: -modes needs a density, -rho!\n";
+            failed = true;
+        }
+        if (has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps")) {
+            err << "ERROR: -modes does not go together with the time stepping options -dt / -steps!\n";
+            failed = true;
+        }
+    } else if (has_flag(argc, argv, "-modes_tol") || has_flag(argc, argv, "-modes_shift")) {
+        err << "ERROR: -modes_tol / -modes_shift need a number of modes, -modes!\n";
+        failed = true;
+    }
+    if (has_flag(argc, argv, "-modes_tol")) {
+        const char *v = arg_after(argc, argv, "-modes_tol");
+        p.modes_tol = v ? std::atof(v) : 0.0;
+        if (!(std::isfinite(p.modes_tol) && p.modes_tol > 0.0)) {
+            err << "ERROR: -modes_tol must be a tolerance > 0!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-modes_shift")) {
+        const char *v = arg_after(argc, argv, "-modes_shift");
+        p.modes_shift = v ? std::atof(v) : -1.0;
+        if (!(std::isfinite(p.modes_shift) && p.modes_shift >= 0.0)) {
+            err << "ERROR: -modes_shift must be a shift >= 0!\n";
             failed = true;
         }
     }
@@ -457,6 +498,22 @@ SolveResult ShellSystem::dynamics_step(double tol, int max_it)
 
 void ShellSystem::dynamics_accept() { check(femshell_dynamics_accept(ctx_), "femshell_dynamics_accept"); }
 
+femshell_modal_info ShellSystem::modes(const Parameters &p, std::vector<double> &lambda, std::vector<double> &modes, std::vector<double> &residual)
+{
+    check(femshell_set_density(ctx_, p.rho, 0, nullptr), "femshell_set_density");
+    femshell_modal_options o;
+    check(femshell_modal_defaults(&o), "femshell_modal_defaults");
+    o.n_modes = p.modes;
+    o.tol = p.modes_tol;
+    o.shift = p.modes_shift;
+    lambda.assign((size_t)p.modes, 0.0);
+    residual.assign((size_t)p.modes, 0.0);
+    modes.assign((size_t)p.modes * (size_t)n_nodes_ * 6, 0.0);
+    femshell_modal_info info{};
+    check(femshell_modes(ctx_, &o, lambda.data(), modes.data(), residual.data(), &info), "femshell_modes");
+    return info;
+}
+
 namespace {
 double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 } // namespace
@@ -531,6 +588,47 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         system.set_mesh(mesh);
         if (p.sections_requested()) system.set_sections(section_table);
         clock.done("symbolic phase, boundary conditions, loads");
+        if (p.modes_requested()) {
+            // natural frequencies and mode shapes instead of a solve
+            if (launch.world_size != 1) throw std::runtime_error("-modes runs on one rank");
+            std::vector<double> lambda, shapes, residual;
+            const femshell_modal_info mi = system.modes(p, lambda, shapes, residual);
+            clock.done("assembly, preconditioner setup, modal analysis");
+            const std::string stem = p.isOutfileSet ? p.out_filename : std::string("out");
+            std::ofstream mf(stem + "_modes.txt");
+            if (!mf) throw std::runtime_error("cannot write " + stem + "_modes.txt");
+            const double two_pi = 6.283185307179586476925286766559;
+            for (int k = 0; k < p.modes; k++) {
+                char line[200];
+                snprintf(line, sizeof line, "%d %.15e %.15e %.15e\n", k + 1, lambda[(size_t)k], std::sqrt(std::max(lambda[(size_t)k], 0.0)) / two_pi,
+                         residual[(size_t)k]);
+                mf << line;
+            }
+            out << "Modal analysis: " << mi.converged << " of " << p.modes << " pairs converged in " << mi.iterations << " iterations of a block of "
+                << mi.block << " (" << (mi.pc_type == FEMSHELL_PC_AMG ? "multigrid" : "6x6 block-Jacobi") << " preconditioner, tolerance "
+                << p.modes_tol << ", shift " << p.modes_shift << "), worst residual " << mi.residual_max << "; frequencies in " << stem
+                << "_modes.txt" << std::endl;
+            for (int k = 0; k < p.modes; k++)
+                out << " mode " << k + 1 << ": lambda = " << lambda[(size_t)k] << ", f = " << std::sqrt(std::max(lambda[(size_t)k], 0.0)) / two_pi << std::endl;
+            if (p.isOutfileSet) {
+                const size_t n6 = (size_t)mesh.n_nodes() * 6;
+                std::vector<PointVectors> arrays;
+                for (int k = 0; k < p.modes; k++)
+                    for (int part = 0; part < 2; part++) {
+                        PointVectors a;
+                        a.name = "mode_" + std::to_string(k + 1) + (part == 0 ? "_u" : "_r");
+                        a.xyz.resize((size_t)mesh.n_nodes() * 3);
+                        for (int32_t n = 0; n < mesh.n_nodes(); n++)
+                            for (int d = 0; d < 3; d++) a.xyz[3 * (size_t)n + d] = shapes[(size_t)k * n6 + 6 * (size_t)n + 3 * part + d];
+                        arrays.push_back(std::move(a));
+                    }
+                write_vtk(mesh, std::vector<double>(n6, 0.0), p.out_filename + ".vtk", &arrays);
+                clock.done("output files");
+            }
+            out << "All done :)\n";
+            clock.report(err);
+            return mi.converged == p.modes ? 0 : 2;
+        }
         SolveResult res;
         if (p.dynamics_requested()) {
             // the force file's loads as a step load at t = 0, from rest: p.steps Newmark steps, the probe node's history

@@ -61,7 +61,13 @@ struct Parameters {
     double dt = 0.0;
     int steps = 0, probe = -1;
     double newmark_beta = 0.25, newmark_gamma = 0.5, damping = 0.0;
-    bool dynamics_requested() const { return rho > 0.0; }
+    bool dynamics_requested() const { return rho > 0.0 && modes == 0; }
+    // modal analysis (extension, stand-alone program only): -rho R -modes N [-modes_tol T] [-modes_shift S] computes the N lowest
+    // pairs of K x = lambda M x (femshell_modes) instead of a static solve; writes <out>_modes.txt and the mode shapes as point
+    // arrays of <out>.vtk.  N in 1 .. 28 (the library's block of N + 4 vectors holds at most 32).
+    int modes = 0;
+    double modes_tol = 1e-6, modes_shift = 0.0;
+    bool modes_requested() const { return modes > 0; }
 };
 
 // what femshell_set_sections takes, from the files above: section 0 is the command line's material, the listed ones follow
@@ -139,6 +145,9 @@ class ShellSystem {
     void dynamics_begin(const Parameters &p, double dt);
     SolveResult dynamics_step(double tol, int max_it);
     void dynamics_accept();
+    // modal analysis: density -rho, then femshell_modes with the library's defaults for guard and iteration limit; lambda[n],
+    // modes[n][n_nodes][6], residual[n]
+    femshell_modal_info modes(const Parameters &p, std::vector<double> &lambda, std::vector<double> &modes, std::vector<double> &residual);
     femshell_ctx *handle() { return ctx_; }
 
   private:

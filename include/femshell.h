@@ -350,6 +350,45 @@ int femshell_dynamics_state(femshell_ctx *ctx, int32_t which, double *u, double 
 int femshell_dynamics_energy(femshell_ctx *ctx, int32_t which, double out[2]);
 int femshell_dynamics_end(femshell_ctx *ctx);
 
+/* ---- modal analysis: natural frequencies and mode shapes ----------------------------------------------------------------
+ * extends: the reference has no eigenvalue analysis; with the lumped mass M of femshell_set_density this solves
+ *     K x = lambda M x,  lambda = omega^2,
+ * on the free dofs for the n_modes lowest pairs, by LOBPCG on the device (csrc/modal.cpp) with a block of
+ * mb = n_modes + guard vectors, preconditioned by what femshell_set_preconditioner chose: one multigrid cycle per column, or
+ * the 6x6 block-Jacobi inverse.  The products with K multiply four columns per pass over the stored blocks (k_spmm_sym,
+ * csrc/modal.hip) with symmetric storage, and go column by column through the single-vector kernel with full storage.
+ *
+ * Pair j has converged when ||K x_j - lambda_j M x_j||_{M^-1} <= tol (lambda_j + shift) with x_j^T M x_j = 1; the call stops when
+ * the n_modes lowest pairs have, or after max_it iterations: it then returns FEMSHELL_OK with info->converged < n_modes and the
+ * best pairs it has.  shift >= 0 solves the pencil (K + shift M) x = (lambda + shift) M x -- the shift is added to the free
+ * diagonal of K in HBM as femshell_dynamics_begin adds its own, the preconditioner is built from the shifted matrix, lambda is
+ * reported with the shift subtracted -- which is what makes an unconstrained shell solvable (its K has the three rigid
+ * translations in the null space).  After the call the shift is gone: K is assembled again at the next use, as after
+ * femshell_dynamics_end.  A K + shift M that is not positive definite surfaces as FEMSHELL_ERR_BREAKDOWN (a host-side test of
+ * the Ritz values x.(K + shift M)x and of the Gram matrices; the message names `shift`).
+ *
+ * lambda_out[n_modes] ascending; modes_out (n_modes x n_nodes x 6, the caller's numbering, or NULL): M-orthonormal, each with the
+ * sign that makes its entry of largest magnitude positive (lowest index on ties); residual_out[n_modes] (or NULL):
+ * ||K x - lambda M x||_{M^-1} / (lambda + shift).  Two calls on the same context give the same bits (start vectors are a hash of
+ * the caller's node id, dof and column; every sum has a fixed order).
+ * FEMSHELL_ERR_INVALID, the context left as it was: no mesh, no density, n_modes < 1, guard < 0, n_modes + guard > 32, fewer than
+ * 3 (n_modes + guard) free dofs, tol <= 0, shift < 0, max_it < 1, dynamics active.  FEMSHELL_ERR_UNSUPPORTED: a row-partitioned
+ * context (world_size != 1). */
+typedef struct femshell_modal_options { int32_t n_modes, guard, max_it, reserved; double tol, shift; } femshell_modal_options;
+typedef struct femshell_modal_info {
+    int32_t iterations, converged /* pairs */, block /* mb */, restarts, fused_product /* 1: k_spmm_sym ran */, pc_type;
+    double residual_max;        /* worst ||Kx - lambda Mx||_{M^-1} / (lambda + shift) of the returned pairs */
+    double seconds_total, seconds_product, seconds_precond, seconds_gram, seconds_update, pc_setup_seconds;
+} femshell_modal_info;
+int femshell_modal_defaults(femshell_modal_options *out);   /* n_modes 6, guard 4, max_it 500, tol 1e-6, shift 0 */
+int femshell_modes(femshell_ctx *ctx, const femshell_modal_options *opt, double *lambda_out /* n_modes */,
+                   double *modes_out /* n_modes x n_nodes x 6, or NULL */, double *residual_out /* n_modes, or NULL */,
+                   femshell_modal_info *info);
+/* test entry: G = A^T diag(w) B (qa x qb, row-major) by the solver's Gram kernel; A, B: qa / qb columns of n_nodes x 6 in the
+ * caller's numbering, 1 <= qa, qb <= 96; weighted != 0: w = the lumped mass (a density must be set), else w = 1.  Partial sums
+ * are added in a fixed order: two calls give the same bits. */
+int femshell_modal_gram(femshell_ctx *ctx, int32_t qa, const double *A, int32_t qb, const double *B, int32_t weighted, double *G);
+
 /* ---- parity / debug exports (single-rank contexts) --------------------------------- */
 
 /* element matrices in the reference's variable-major element ordering Ke(n*alpha+i, n*beta+j)
@@ -366,6 +405,9 @@ int64_t femshell_nnz_blocks(femshell_ctx *ctx); /* number of 6x6 blocks of K on 
 int femshell_export_bsr(femshell_ctx *ctx, int32_t *rowptr, int32_t *colidx, double *vals, double *F);
 /* y = K x on the device */
 int femshell_spmv(femshell_ctx *ctx, const double *x, double *y);
+/* Y = K X for a block of n_cols (1 .. 96) vectors, column j at X + j * n_nodes * 6: the block product of femshell_modes; same
+ * preconditions as femshell_spmv */
+int femshell_spmm(femshell_ctx *ctx, int32_t n_cols, const double *X, double *Y);   /* Y = K X, columns of n_nodes x 6 */
 /* r = F - K x with products and row sums in double-double (the residual the iterative refinement of the
  * multigrid-preconditioned solve restarts from); x[n_nodes][6] */
 int femshell_residual(femshell_ctx *ctx, const double *x, double *r);
@@ -419,7 +461,13 @@ typedef enum femshell_kernel {
     FEMSHELL_KERNEL_LUMPED_MASS = 4,  /* k_lumped_mass */
     FEMSHELL_KERNEL_MASS_SHIFT = 5,   /* k_mass_shift (the shifts add up: K is assembled again at the next use) */
     FEMSHELL_KERNEL_NEWMARK_RHS = 6,  /* k_newmark_rhs */
-    FEMSHELL_KERNEL_NEWMARK_UPDATE = 7 /* k_newmark_update (a candidate from whatever the solution vector holds; not committed) */
+    FEMSHELL_KERNEL_NEWMARK_UPDATE = 7, /* k_newmark_update (a candidate from whatever the solution vector holds; not committed) */
+    /* modal analysis, launched back to back on scratch blocks of hashed vectors; FEMSHELL_TIME_KERNEL_COLS = c in the
+     * environment (default 4, at most 32) sets the width */
+    FEMSHELL_KERNEL_SPMM = 8,         /* Y = K X for c columns, both phases (FEMSHELL_SPMM_FUSED=0: column by column through
+                                         the single-vector kernels, the yardstick of the fused kernel) */
+    FEMSHELL_KERNEL_GRAM = 9,         /* S^T M S for 3c columns */
+    FEMSHELL_KERNEL_BLOCK_COMBINE = 10 /* 2c columns out of 3c */
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
