@@ -746,7 +746,7 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     }
     if (!build_plan(n_nodes, xyz, n_tri, tri, n_quad, quad, c->cfg.rank, c->cfg.world_size, &c->plan, &e, default_symmetric_storage(),
                     /* geometric orientation of the symmetric storage when the library chose the numbering: */ !c->perm.empty()))
-        return set_err(FEMSHELL_ERR_MESH, "femshell_set_mesh: " + e);
+        return set_err(c->plan.over_capacity ? FEMSHELL_ERR_UNSUPPORTED : FEMSHELL_ERR_MESH, "femshell_set_mesh: " + e);
     part_done("coordinate check, renumbering, plan");
     c->have_mesh_centre = false;
     if (c->cfg.world_size > 1 || c->comm.active()) { // (the row-partitioned multigrid: rigid-body modes about the centre of the whole mesh)

@@ -298,8 +298,8 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
             // not: the item's constraint word (no global load in this phase: vmcnt retires in order, so waiting
             // for one would also wait for the previous slice's K stores)
             const uint32_t mrow = flags & 63u, mcol = (flags >> 6) & 63u;
-            const int valence = (int)((flags >> 12) & 255u);
-            const bool diag_slot = (flags >> 20) & 1u;
+            const int valence = (int)((flags >> 12) & kFlagValenceMask);
+            const bool diag_slot = (flags >> kFlagDiagBit) & 1u;
             // constraints (libMesh constrain_element_matrix_and_vector semantics) and the 18 stores of a finished block
             typedef double v2d __attribute__((ext_vector_type(2)));
             // the same for a diagonal block held as its upper triangle: row and column masks coincide
@@ -449,6 +449,7 @@ __device__ __forceinline__ double lane_below(double v)
 
 constexpr int kPipeConsumers = 192;  // lanes that own work items (three waves)
 constexpr int kPipeFlagShift = 9;    // item.w of the pipelined layout: wave word (9 bits) | constraint word << 9
+static_assert(kFlagDiagBit + 1 + kPipeFlagShift <= 32 && kFlagValenceMask >= (uint32_t)(kItemPairs * 255), "the constraint word must fit item.w and hold the count of 255 chunks");
 constexpr int kPipeRecPasses = 3;    // record passes the producer wave runs at most per slice: 192 records, more than a slice
                                      // of a plan with Plan::pipe has (kPipeMaxSliceElems)
 
@@ -825,8 +826,8 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
                     // the slot's constraint word rides in the item (k_item_flags: bits 9.. of w, beside the wave's word)
                     const uint32_t flags = item.w >> kPipeFlagShift;
                     const uint32_t mrow = flags & 63u, mcol = (flags >> 6) & 63u;
-                    const int valence = (int)((flags >> 12) & 255u);
-                    const bool diag_slot = (flags >> 20) & 1u;
+                    const int valence = (int)((flags >> 12) & kFlagValenceMask);
+                    const bool diag_slot = (flags >> kFlagDiagBit) & 1u;
                     typedef double v2d __attribute__((ext_vector_type(2)));
                     if (sym_item) {
                         if (mrow) {

@@ -125,8 +125,10 @@ __global__ __launch_bounds__(256) void k_item_flags(DeviceMatrix m)
                 const int64_t slot = base + slot_in_slice;
                 const int row = s * kSliceNodes + (slot_in_slice & 31), col = m.cols[slot];
                 const uint32_t valence = (uint32_t)(m.pair_ptr[slot + 1] - m.pair_ptr[slot]);
-                f = (uint32_t)m.dmask[row] | ((uint32_t)m.dmask[col] << 6) | ((valence < 255u ? valence : 255u) << 12) |
-                    (col == row ? 1u << 20 : 0u);
+                // (the plan accepts at most 765 contributions per slot, plan.cpp: ten bits hold the count in full -- it is the
+                //  diagonal entry of a constrained dof; in the pipelined layout the word's 23 bits sit above the wave word's 9)
+                f = (uint32_t)m.dmask[row] | ((uint32_t)m.dmask[col] << 6) | ((valence < kFlagValenceMask ? valence : kFlagValenceMask) << 12) |
+                    (col == row ? 1u << kFlagDiagBit : 0u);
             }
             if (m.pipe) { // the pipelined kernel reads the word from the item itself: one load and 4 bytes per item less
                 uint32_t *w = &const_cast<uint4 *>(m.items)[i0 + it].w;
@@ -995,8 +997,11 @@ static void spmv_dispatch(const DeviceMatrix &m, const double *x, double *y, dou
     // x of the block columns, at most kSpmvPanel slots at a time (96 KiB of the CU's 160)
     const int panel = m.max_slice_width < kSpmvPanel ? (m.max_slice_width > 0 ? m.max_slice_width : 1) : kSpmvPanel;
     const size_t lds = (size_t)panel * kSliceNodes * 3 * sizeof(double2);
+    // (k_spmv's own arrays -- sh, rs -- count towards a workgroup's LDS as well: a row of 42 blocks stays below 64 KiB with
+    //  its panel alone and passes it with them)
+    constexpr size_t kStaticLds = (3 + kSliceRows) * sizeof(double);
     auto launch = [&](auto kernel) {
-        if (lds > 64 * 1024) // beyond the default dynamic-LDS limit (slices wider than 42 blocks)
+        if (lds + kStaticLds > 64 * 1024) // beyond the default LDS limit (slices of 42 blocks and wider)
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL(kernel, g, b, lds, st, m, x, y, partials, s, order, count, base_vec, sign, panel, cheb);
     };

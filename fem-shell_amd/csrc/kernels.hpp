@@ -9,6 +9,11 @@
 namespace femshell {
 
 constexpr int32_t kStatusDirect = 0x40000000; // status values above this carry a local element id directly
+// constraint word of an assembly work item (DeviceMatrix::item_flags, k_item_flags): width of the contribution count and
+// the bit that marks a diagonal slot.  23 bits in all: the pipelined layout keeps the word in item.w above the 9 bits of
+// the wave word (assemble_kernel.hpp kPipeFlagShift).
+constexpr uint32_t kFlagValenceMask = 1023u;
+constexpr int kFlagDiagBit = 22;
 
 // Device view of the mesh + matrix structure of one rank (see plan.hpp for the layout).
 struct DeviceMatrix {
@@ -31,8 +36,9 @@ struct DeviceMatrix {
     const uint4 *items = nullptr;            // assembly work items (plan.hpp)
     uint32_t *item_flags = nullptr;          // per item: what its owner lane needs to know about the slot besides the
                                              // contributions (k_item_flags): Dirichlet mask of the row node (bits 0-5)
-                                             // and of the column node (6-11), contributions in the slot (12-19), bit 20
-                                             // = diagonal slot; 0 for items that do not own their slot
+                                             // and of the column node (6-11), contributions in the slot (12-21: up to
+                                             // the 765 the plan accepts), bit 22 = diagonal slot; 0 for items that do
+                                             // not own their slot
     int32_t max_stage_rows = 0;
     int32_t lds_bytes = 0;                   // dynamic LDS of k_assemble (assemble_lds_layout)
     int32_t lds_rec_off = 0, lds_stage_off = 0; // offsets in doubles (pipe: lds_rec_off = doubles of one record buffer)

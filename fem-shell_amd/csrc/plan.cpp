@@ -484,7 +484,10 @@ static bool pack_assembly_items(Plan &p, std::string *err)
         });
         size_t total_items = 0;
         for (int t = 0; t < nchunks_t; t++) {
-            if (part_bad[(size_t)t]) return fail("a block slot has more than 765 contributions");
+            if (part_bad[(size_t)t]) {
+                p.over_capacity = true;
+                return fail("a block slot has more than 765 contributions");
+            }
             p.max_stage_rows = std::max(p.max_stage_rows, part_stage[(size_t)t]);
             total_items += part_items[(size_t)t].size();
         }
@@ -528,6 +531,7 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
         if (err) *err = m;
         return false;
     };
+    P->over_capacity = false; // (the input checks below return before the plan is reset)
     if (n_nodes <= 0) return fail("mesh has no nodes");
     if (n_tri < 0 || n_quad < 0 || (int64_t)n_tri + n_quad <= 0) return fail("mesh has no elements");
     if (world < 1 || rank < 0 || rank >= world) return fail("invalid rank/world_size");
@@ -1198,7 +1202,10 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
             part_nodes[(size_t)t].swap(nodes);
         });
         for (int t = 0; t < nchunks; t++) {
-            if (part_bad[(size_t)t]) return fail("more than 4095 elements touch one 32-node slice");
+            if (part_bad[(size_t)t]) {
+                p.over_capacity = true;
+                return fail("more than 4095 elements touch one 32-node slice");
+            }
             p.max_slice_elems = std::max(p.max_slice_elems, part_max[(size_t)t]);
         }
         for (int32_t s = 0; s < p.n_slices; s++) p.slice_elem_ptr[(size_t)s + 1] += p.slice_elem_ptr[(size_t)s];

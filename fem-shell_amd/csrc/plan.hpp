@@ -82,6 +82,9 @@ struct HaloPeer {
 struct Plan {
     // global problem
     int32_t n_nodes = 0, n_tri = 0, n_quad = 0;
+    // set when build_plan refuses a valid mesh because it exceeds one of the layout's fixed-width fields (contributions per
+    // slot, elements per slice): the callers report FEMSHELL_ERR_UNSUPPORTED then, not FEMSHELL_ERR_MESH
+    bool over_capacity = false;
     int rank = 0, world = 1;
     int32_t row_begin = 0, row_end = 0; // owned global node range
     std::vector<int32_t> part_bounds;   // world + 1 row boundaries of the partition (partition_bounds)

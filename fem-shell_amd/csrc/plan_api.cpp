@@ -27,8 +27,9 @@ int femshell_plan_create(int32_t n_nodes, const double *xyz, int32_t n_tri, cons
     femshell_plan *pl = new femshell_plan();
     std::string e;
     if (!build_plan(n_nodes, xyz, n_tri, tri, n_quad, quad, rank, world_size, &pl->p, &e, default_symmetric_storage())) {
+        const bool over = pl->p.over_capacity;
         delete pl;
-        return set_err(FEMSHELL_ERR_MESH, "femshell_plan_create: " + e);
+        return set_err(over ? FEMSHELL_ERR_UNSUPPORTED : FEMSHELL_ERR_MESH, "femshell_plan_create: " + e);
     }
     *out = pl;
     return FEMSHELL_OK;

@@ -79,7 +79,11 @@ const char *femshell_last_error(void);
  * (either count may be 0).  Every rank passes the same global mesh; the library keeps
  * the node rows [femshell_row_begin, femshell_row_end) of its rank plus the ghost
  * nodes/elements they touch, and builds the block sparsity (libMesh does this in
- * EquationSystems::init, SA:125). */
+ * EquationSystems::init, SA:125).  FEMSHELL_ERR_MESH: an invalid mesh (index out of range,
+ * repeated node, unattached node).  FEMSHELL_ERR_UNSUPPORTED: a valid mesh beyond a limit of
+ * the layout (more than 765 elements at a node, more than 4095 elements or too many for the
+ * assembly kernel's LDS on one 32-node slice, more than 63 neighbours of a node in full
+ * storage); the context stays usable. */
 int femshell_set_mesh(femshell_ctx *ctx, int32_t n_nodes, const double *xyz, int32_t n_tri,
                       const int32_t *tri, int32_t n_quad, const int32_t *quad);
 
