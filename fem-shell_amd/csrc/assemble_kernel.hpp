@@ -435,16 +435,29 @@ __global__ __launch_bounds__(256, kWavesPerSimd) void k_assemble(DeviceMatrix m,
 // that every SIMD carries one long and one short wave; the producer runs at raised priority.
 // Records of triangles are RecLean (34 doubles), items and flags as in k_assemble, in rounds of 192 lanes.
 // kAblate (lab): 8 = no record math, 16 = roles by wave index and the same in every workgroup, 32 = s_memtime stamps,
-// 64 = no priority for the producer, 128 = the second workgroup swaps neighbouring roles instead of shifting them by two SIMDs;
-// 0 in the product.
+// 64 = no priority for the producer, 128 = the second workgroup swaps neighbouring roles instead of shifting them by two SIMDs,
+// 1024 = the full off-diagonal wave at priority 3, 2048 = the diagonal wave at priority 1; 0 in the product.
 // =====================================================================================
-// value of the next lane of the wave (lane 63: unspecified): DPP wave_shl:1 on both halves of the double
+// value of the next lane of the wave (lane 63: zero): DPP wave_shl:1 on both halves of the double.  With bound_ctrl the
+// result is defined in every lane, so the move needs no `old` operand: two instructions per double (a form that keeps the
+// old value where no lane is read had the compiler zero a register pair per double first).
+// Nobody reads lane 63's zero: the plan keeps the chunks of a slot in neighbouring lanes of ONE wave (plan.cpp
+// pack_items_pipe), so an owner with c chunks sits in lane 64 - c at the highest and takes from the c - 1 lanes after it.
 __device__ __forceinline__ double lane_below(double v)
 {
     const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, false);
-    const int hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, false);
+    const int lo2 = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, true);
+    const int hi2 = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, true);
     return __hiloint2double(hi2, lo2);
+}
+
+// A double of unspecified value, at no instruction: what a register happens to hold.  For accumulators nobody reads -- a
+// constant there would cost a move per register, and the compiler makes a zero of anything it knows to be arbitrary.
+__device__ __forceinline__ double unspecified_double()
+{
+    double x;
+    asm volatile("" : "=v"(x)); // (volatile: the definition stays where the value is wanted, it is not hoisted out of the loops)
+    return x;
 }
 
 constexpr int kPipeConsumers = 192;  // lanes that own work items (three waves)
@@ -683,6 +696,9 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
     } else {
         // ================= consumers: block slots of slice j from record buffer j & 1 =================
         const int vtid = vwave * 64 + lane; // 0..191
+        // lab: the full off-diagonal wave (it shares its SIMD with the other workgroup's producer) / the diagonal wave at raised priority
+        if ((kAblate & 1024) && vwave == 1) __builtin_amdgcn_s_setprio(3);
+        if ((kAblate & 2048) && vwave == 0) __builtin_amdgcn_s_setprio(1);
         struct Desc {
             int e0, ne, i0, ni;
             int64_t base;
@@ -750,29 +766,43 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
                 const int wave_chunks = __builtin_amdgcn_readfirstlane((int)(item.w & 0xffu));
                 const bool wave_sym = !kHasQuads && __builtin_amdgcn_readfirstlane((int)((item.w >> 8) & 1u)) != 0;
                 const bool sym_item = !kHasQuads && slot_in_slice < kSliceNodes && !general;
+                // The first contribution of a lane starts from constants -- zeros that vanish into its operations -- instead of
+                // 36 zeroed registers (72 moves per lane and round, 21 doubles of them unused in a diagonal lane); the others add
+                // to it as before, the same operations in the same order.  Every lane runs a first contribution: a lane
+                // without any (an inert item: cnt == 0, slot 0xffff, pairs 0) takes record 0 along with the off-diagonal lanes
+                // of its wave -- one test and one exec mask less than skipping it, and its sums are as good as any other
+                // value.  Such a lane is no owner, so it stores nothing, and no owner takes from it (an owner adds its own
+                // chunks only, and those have cnt >= 1).  The 15 doubles a diagonal lane does not use hold unspecified
+                // values in the same way: the owner of a diagonal slot stores blk[0..20] alone.
+                auto add_diag = [&](uint32_t pr, double acc[21]) {
+                    const double *rec = lds_rec + pipe_rec_offset((int)(pr >> 4), kRec);
+                    if (kSecConsume) tri3_diag_add_rec<RecLean>(rec, (int)(pr & 3u), rec_material_lean(rec, mc.flags), acc);
+                    else tri3_diag_add_rec<RecLean>(rec, (int)(pr & 3u), mc, acc);
+                };
+                auto add_block = [&](uint32_t pr, double acc[36]) {
+                    const double *rec = lds_rec + pipe_rec_offset((int)(pr >> 4), kRec);
+                    if (kSecConsume) {
+                        if (kHasQuads) block_add_rec<true>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), rec_material<true>(rec, mc.flags), acc);
+                        else tri3_block_add_rec<RecLean>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), rec_material_lean(rec, mc.flags), acc);
+                    } else if (kHasQuads) {
+                        block_add_rec<true>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, acc);
+                    } else {
+                        tri3_block_add_rec<RecLean>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, acc);
+                    }
+                };
                 double blk[36];
+                if (sym_item) { // (a live item: cnt >= 1)
 #pragma unroll
-                for (int i = 0; i < 36; i++) blk[i] = 0.0;
-                if (sym_item) {
-                    for (int q = 0; q < cnt; q++) {
-                        const uint32_t pr = (q == 0) ? (item.y & 0xffffu) : (q == 1 ? (item.y >> 16) : (item.z & 0xffffu));
-                        const double *rec = lds_rec + pipe_rec_offset((int)(pr >> 4), kRec);
-                        if (kSecConsume) tri3_diag_add_rec<RecLean>(rec, (int)(pr & 3u), rec_material_lean(rec, mc.flags), blk);
-                        else tri3_diag_add_rec<RecLean>(rec, (int)(pr & 3u), mc, blk);
-                    }
+                    for (int i = 0; i < 21; i++) blk[i] = 0.0;
+#pragma unroll
+                    for (int i = 21; i < 36; i++) blk[i] = unspecified_double();
+                    add_diag(item.y & 0xffffu, blk);
+                    for (int q = 1; q < cnt; q++) add_diag(q == 1 ? (item.y >> 16) : (item.z & 0xffffu), blk);
                 } else {
-                    for (int q = 0; q < cnt; q++) {
-                        const uint32_t pr = (q == 0) ? (item.y & 0xffffu) : (q == 1 ? (item.y >> 16) : (item.z & 0xffffu));
-                        const double *rec = lds_rec + pipe_rec_offset((int)(pr >> 4), kRec);
-                        if (kSecConsume) {
-                            if (kHasQuads) block_add_rec<true>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), rec_material<true>(rec, mc.flags), blk);
-                            else tri3_block_add_rec<RecLean>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), rec_material_lean(rec, mc.flags), blk);
-                        } else if (kHasQuads) {
-                            block_add_rec<true>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, blk);
-                        } else {
-                            tri3_block_add_rec<RecLean>(rec, (int)((pr >> 2) & 3u), (int)(pr & 3u), mc, blk);
-                        }
-                    }
+#pragma unroll
+                    for (int i = 0; i < 36; i++) blk[i] = 0.0;
+                    add_block(item.y & 0xffffu, blk);
+                    for (int q = 1; q < cnt; q++) add_block(q == 1 ? (item.y >> 16) : (item.z & 0xffffu), blk);
                 }
                 stamp(2);
                 const bool owner = live && chunk == 0 && nchunks > 0;
@@ -797,28 +827,30 @@ __global__ __launch_bounds__(256, 2) void k_assemble_pipe(DeviceMatrix m, MatCon
                         for (int i = 0; i < 36; i++) blk[i] += t[i];
                     }
                 } else if (wave_chunks > 1 && wave_sym) { // more chunks: shift by shift, every owner adding what is its own
-                    double t[21];
+                    double t[21]; // (the first shift takes the sums where they are, the others shift t in place)
 #pragma unroll
-                    for (int i = 0; i < 21; i++) t[i] = blk[i];
-                    for (int c = 1; c < wave_chunks; c++) {
-#pragma unroll
-                        for (int i = 0; i < 21; i++) t[i] = lane_below(t[i]);
+                    for (int i = 0; i < 21; i++) t[i] = lane_below(blk[i]);
+                    for (int c = 1;;) {
                         if (owner && c < nchunks) {
 #pragma unroll
                             for (int i = 0; i < 21; i++) blk[i] += t[i];
                         }
+                        if (++c >= wave_chunks) break;
+#pragma unroll
+                        for (int i = 0; i < 21; i++) t[i] = lane_below(t[i]);
                     }
                 } else if (wave_chunks > 1) {
                     double t[36];
 #pragma unroll
-                    for (int i = 0; i < 36; i++) t[i] = blk[i];
-                    for (int c = 1; c < wave_chunks; c++) {
-#pragma unroll
-                        for (int i = 0; i < 36; i++) t[i] = lane_below(t[i]);
+                    for (int i = 0; i < 36; i++) t[i] = lane_below(blk[i]);
+                    for (int c = 1;;) {
                         if (owner && c < nchunks) {
 #pragma unroll
                             for (int i = 0; i < 36; i++) blk[i] += t[i];
                         }
+                        if (++c >= wave_chunks) break;
+#pragma unroll
+                        for (int i = 0; i < 36; i++) t[i] = lane_below(t[i]);
                     }
                 }
                 stamp(3);

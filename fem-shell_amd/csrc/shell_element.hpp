@@ -156,11 +156,58 @@ constexpr int kRecDoublesQuad = 66;
 constexpr int kQuadSide = 46; // DKQ coefficients (a, b, c, d, e) of the four sides, side s = node s -> node s+1
 constexpr int kQuadGp = 26;
 // index of entry (n,m) of a symmetric 3x3 table stored as 00,01,02,11,12,22
-__device__ __forceinline__ int sym3(int n, int m)
+__host__ __device__ constexpr int sym3(int n, int m)
 {
     const int lo = n < m ? n : m, hi = n < m ? m : n;
     return ((lo * (5 - lo)) >> 1) + hi;
 }
+// What the block functions derive from the local node numbers of a contribution:
+// k = (i+2)%3; rows of (xs,ys) seen from node i: (x_ki,y_ki) = row {1,0,2}[i], (x_ji,y_ji) = -row {0,2,1}[i]
+__host__ __device__ constexpr int tri_prev(int i) { return (i + 2) % 3; }
+__host__ __device__ constexpr int tri_row_ki(int i) { return (i == 2) ? 2 : 1 - i; }
+__host__ __device__ constexpr int tri_row_ji(int i) { return (i == 0) ? 0 : 3 - i; }
+// The node numbers are run-time values of every lane, and as formulas the above cost the block functions a quarter of
+// their instructions (min, max, subtract, multiply, shift, add per sym3; compare and select per row pick).  The block
+// functions look them up in literals instead: a node table packs f(i), four bits per node; the pair table packs
+// sym3(n, m), three bits per pair, entry 3*n + m -- the offset of (n, m) in QC, which the functions need anyway.  A lookup
+// is one bit-field extract at a shift that the lookups of a node share.  Three literals only -- row {0,2,1}[i] is
+// 2 - (i+2)%3, and one pair table serves all pairs of a contribution: each literal occupies a scalar register through the
+// consumers' loops of the pipelined assembly kernel, which is at its limit of them.
+__host__ __device__ constexpr int node_lut_shift(int i) { return 4 * i; }
+__host__ __device__ constexpr int pair_lut_shift(int q) { return 3 * q; } // q = 3*n + m
+constexpr uint32_t pack_node_lut(int (*f)(int))
+{
+    uint32_t bits = 0;
+    for (int i = 0; i < 3; i++) bits |= (uint32_t)f(i) << node_lut_shift(i);
+    return bits;
+}
+constexpr uint32_t pack_pair_lut(int (*f)(int, int))
+{
+    uint32_t bits = 0;
+    for (int n = 0; n < 3; n++)
+        for (int m = 0; m < 3; m++) bits |= (uint32_t)f(n, m) << pair_lut_shift(3 * n + m);
+    return bits;
+}
+constexpr uint32_t kLutPrev = pack_node_lut(tri_prev), kLutRowKi = pack_node_lut(tri_row_ki), kLutSym3 = pack_pair_lut(sym3);
+constexpr int node_lut_at(uint32_t lut, int i) { return (int)((lut >> node_lut_shift(i)) & 15u); }
+constexpr int pair_lut_at(uint32_t lut, int q) { return (int)((lut >> pair_lut_shift(q)) & 7u); }
+// every lookup against its formula: all three nodes, all nine pairs; row {0,2,1}[i] is 2 - (i+2)%3
+constexpr bool tri_luts_agree()
+{
+    for (int ia = 0; ia < 3; ia++) {
+        if (node_lut_at(kLutPrev, ia) != (ia + 2) % 3 || node_lut_at(kLutRowKi, ia) != ((ia == 2) ? 2 : 1 - ia) ||
+            2 - node_lut_at(kLutPrev, ia) != ((ia == 0) ? 0 : 3 - ia) || 2 - tri_prev(ia) != tri_row_ji(ia))
+            return false;
+        for (int ib = 0; ib < 3; ib++)
+            if (pair_lut_at(kLutSym3, 3 * ia + ib) != sym3(ia, ib)) return false;
+    }
+    return true;
+}
+static_assert(tri_luts_agree(), "the packed node and pair tables must give what the formulas give");
+static_assert(pair_lut_shift(8) + 3 <= 32 && node_lut_shift(2) + 4 <= 32 && sym3(2, 2) < 8 && tri_row_ki(2) < 16, "entries must fit their fields");
+// the lookups on the device: v_bfe_u32 with the table in a scalar register
+__device__ __forceinline__ int node_lut(uint32_t lut, int shift) { return (int)__builtin_amdgcn_ubfe(lut, (uint32_t)shift, 4u); }
+__device__ __forceinline__ int pair_lut(uint32_t lut, int shift) { return (int)__builtin_amdgcn_ubfe(lut, (uint32_t)shift, 3u); }
 
 __device__ __forceinline__ bool tri3_record(const double X[9], const MatConst &mc, double rec[kRecDoubles])
 {
@@ -308,11 +355,12 @@ __device__ __forceinline__ void tri3_block_add_rec(const double *rec, int ia, in
 {
 #pragma clang fp reassociate(on) contract(fast) // element math only; parity bar is 1e-12, not bitwise
 
-    const int ka = (ia == 0) ? 2 : ia - 1, kb = (ib == 0) ? 2 : ib - 1; // (i+2)%3
     // rows of (xs,ys) are (12),(31),(23).  Seen from node i: (x_ki,y_ki) = row {1,0,2}[i],
     // (x_ji,y_ji) = -row {0,2,1}[i]; membrane: beta = y of row {2,1,0}[i], gamma = -x of that row
-    const int rki_a = (ia == 2) ? 2 : 1 - ia, rji_a = (ia == 0) ? 0 : 3 - ia;
-    const int rki_b = (ib == 2) ? 2 : 1 - ib, rji_b = (ib == 0) ? 0 : 3 - ib;
+    const int sh_a = node_lut_shift(ia), sh_b = node_lut_shift(ib);
+    const int ka = node_lut(kLutPrev, sh_a), kb = node_lut(kLutPrev, sh_b); // (i+2)%3
+    const int rki_a = node_lut(kLutRowKi, sh_a), rji_a = 2 - ka;
+    const int rki_b = node_lut(kLutRowKi, sh_b), rji_b = 2 - kb;
     const double xki_a = rec[L::xs + rki_a], yki_a = rec[L::ys + rki_a], xji_a = -rec[L::xs + rji_a], yji_a = -rec[L::ys + rji_a];
     const double xki_b = rec[L::xs + rki_b], yki_b = rec[L::ys + rki_b], xji_b = -rec[L::xs + rji_b], yji_b = -rec[L::ys + rji_b];
     const double bi = rec[L::ys + 2 - ia], gi = -rec[L::xs + 2 - ia];
@@ -327,10 +375,13 @@ __device__ __forceinline__ void tri3_block_add_rec(const double *rec, int ia, in
 
     // ---- plate block (3x3)  (SA:555-603): p = L_i^T S L_j from the record's Gram tables
     const double *QQ = rec + L::QQ, *QC = rec + L::QC, *CC = rec + L::CC;
-    const int s_ab = sym3(ia, ib), s_akb = sym3(ia, kb), s_kab = sym3(ka, ib), s_kakb = sym3(ka, kb);
+    // offsets of the four pairs in QC, and through them their entries of the pair table
+    const int q_ab = 3 * ia + ib, q_akb = 3 * ia + kb, q_kab = 3 * ka + ib, q_kakb = 3 * ka + kb;
+    const int s_ab = pair_lut(kLutSym3, pair_lut_shift(q_ab)), s_akb = pair_lut(kLutSym3, pair_lut_shift(q_akb)),
+              s_kab = pair_lut(kLutSym3, pair_lut_shift(q_kab)), s_kakb = pair_lut(kLutSym3, pair_lut_shift(q_kakb));
     double S[4][4];
-    S[0][0] = QQ[s_ab];        S[0][1] = QQ[s_akb];       S[0][2] = QC[3 * ia + kb]; S[0][3] = QC[3 * ia + ib];
-    S[1][0] = QQ[s_kab];       S[1][1] = QQ[s_kakb];      S[1][2] = QC[3 * ka + kb]; S[1][3] = QC[3 * ka + ib];
+    S[0][0] = QQ[s_ab];        S[0][1] = QQ[s_akb];       S[0][2] = QC[q_akb];       S[0][3] = QC[q_ab];
+    S[1][0] = QQ[s_kab];       S[1][1] = QQ[s_kakb];      S[1][2] = QC[q_kakb];      S[1][3] = QC[q_kab];
     S[2][0] = QC[3 * ib + ka]; S[2][1] = QC[3 * kb + ka]; S[2][2] = CC[s_kakb];      S[2][3] = CC[s_kab];
     S[3][0] = QC[3 * ib + ia]; S[3][1] = QC[3 * kb + ia]; S[3][2] = CC[s_akb];       S[3][3] = CC[s_ab];
     double Xm[4][3];
@@ -399,8 +450,8 @@ __device__ __forceinline__ void tri3_diag_add_rec(const double *rec, int ia, con
 {
 #pragma clang fp reassociate(on) contract(fast) // element math only; parity bar is 1e-12, not bitwise
 
-    const int ka = (ia == 0) ? 2 : ia - 1;
-    const int rki = (ia == 2) ? 2 : 1 - ia, rji = (ia == 0) ? 0 : 3 - ia;
+    const int sh_a = node_lut_shift(ia);
+    const int ka = node_lut(kLutPrev, sh_a), rki = node_lut(kLutRowKi, sh_a), rji = 2 - ka;
     const double xki = rec[L::xs + rki], yki = rec[L::ys + rki], xji = -rec[L::xs + rji], yji = -rec[L::ys + rji];
     const double bi = rec[L::ys + 2 - ia], gi = -rec[L::xs + 2 - ia];
 
@@ -412,9 +463,11 @@ __device__ __forceinline__ void tri3_diag_add_rec(const double *rec, int ia, con
 
     // plate (SA:555-603): p = L^T S L, S symmetric
     const double *QQ = rec + L::QQ, *QC = rec + L::QC, *CC = rec + L::CC;
-    const int s_aa = sym3(ia, ia), s_ak = sym3(ia, ka), s_kk = sym3(ka, ka);
-    const double S00 = QQ[s_aa], S01 = QQ[s_ak], S02 = QC[3 * ia + ka], S03 = QC[3 * ia + ia];
-    const double S11 = QQ[s_kk], S12 = QC[3 * ka + ka], S13 = QC[3 * ka + ia];
+    const int q_aa = 4 * ia, q_ak = 3 * ia + ka, q_kk = 4 * ka; // offsets in QC
+    const int s_aa = pair_lut(kLutSym3, pair_lut_shift(q_aa)), s_ak = pair_lut(kLutSym3, pair_lut_shift(q_ak)),
+              s_kk = pair_lut(kLutSym3, pair_lut_shift(q_kk));
+    const double S00 = QQ[s_aa], S01 = QQ[s_ak], S02 = QC[q_ak], S03 = QC[q_aa];
+    const double S11 = QQ[s_kk], S12 = QC[q_kk], S13 = QC[3 * ka + ia];
     const double S22 = CC[s_kk], S23 = CC[s_ak], S33 = CC[s_aa];
     const double S[4][4] = {{S00, S01, S02, S03}, {S01, S11, S12, S13}, {S02, S12, S22, S23}, {S03, S13, S23, S33}};
     double Xm[4][3];

@@ -25,7 +25,7 @@ template <int W, int F> float run(const DeviceMatrix &m, const MatConst &mc, int
     return ms / reps;
 }
 
-template <class T> T *up(const std::vector<T> &v) { T *d = nullptr; CK(hipMalloc(&d, std::max<size_t>(1, v.size()) * sizeof(T))); if (!v.empty()) CK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)); return d; }
+template <class T, class A> T *up(const std::vector<T, A> &v) { T *d = nullptr; CK(hipMalloc(&d, std::max<size_t>(1, v.size()) * sizeof(T))); if (!v.empty()) CK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice)); return d; }
 
 int main(int argc, char **argv)
 {
@@ -100,6 +100,10 @@ int main(int argc, char **argv)
         printf("pipe, roles by wave id : %.3f ms\n", runp(k_assemble_pipe<16>, g, R));
         printf("pipe, no priority      : %.3f ms\n", runp(k_assemble_pipe<64>, g, R));
         printf("pipe, neighbours swapped: %.3f ms\n", runp(k_assemble_pipe<128>, g, R));
+        printf("pipe, off-diag wave prio 3 = producer's       : %.3f ms\n", runp(k_assemble_pipe<1024>, g, R));
+        printf("pipe, off-diag wave prio 3, producer none     : %.3f ms\n", runp(k_assemble_pipe<1024 + 64>, g, R));
+        printf("pipe, diagonal wave prio 1                    : %.3f ms\n", runp(k_assemble_pipe<2048>, g, R));
+        printf("pipe, off-diag 3, producer none, diagonal 1   : %.3f ms\n", runp(k_assemble_pipe<1024 + 64 + 2048>, g, R));
         printf("pipe again             : %.3f ms\n", runp(k_assemble_pipe<0>, g, R));
         const bool fake = getenv("LAB_FAKE_RECORDS") != nullptr;
         const float ms = fake ? runp(k_assemble_pipe<40>, g, 1) : runp(k_assemble_pipe<32>, g, 1);
