@@ -20,45 +20,76 @@
 #endif
 #include <time.h>
 
+/* The element path (material, frames, membrane, plate, superposition, rotation) is written in fso_real.  It is double in
+ * every build of this file on its own: the typedef and the macros below then change nothing in the object code.
+ * femshell_oracle_quad.c includes this file with FSO_QUAD set: fso_real is __float128 there, the constants that are no
+ * dyadic fractions (FSO_C(1.0) / FSO_C(6.0), FSO_SQRT(1/3)) are evaluated in the wide type, the functions of the element
+ * path get names of their own (their signatures differ from the header's) and assembly and solver are left out. */
+#ifdef FSO_QUAD
+#include <quadmath.h>
+typedef __float128 fso_real;
+#define FSO_SQRT sqrtq
+#define FSO_POW  powq
+#define FSO_FMAX fmaxq
+#define FSO_FMIN fminq
+typedef struct fsoq_tri3_parts {
+    fso_real trafo[9], transUV[6], dphi[6], area, Ke_m[36], Ke_p[81], K_local[324], K_global_nm[324];
+} fsoq_tri3_parts;
+#define fso_tri3_parts        fsoq_tri3_parts
+#define fso_material_matrices fsoq_wide_material_matrices
+#define fso_tri3_specht_B     fsoq_wide_tri3_specht_B
+#define fso_element_tri3      fsoq_wide_element_tri3
+#define fso_element_quad4     fsoq_wide_element_quad4
+#else
+typedef double fso_real;
+#define FSO_SQRT sqrt
+#define FSO_POW  pow
+#define FSO_FMAX fmax
+#define FSO_FMIN fmin
+#endif
+#define FSO_C(x) ((fso_real)(x))
+
 /* ---------------------------------------------------------------- small dense helpers */
 
 /* C(m x n) = A(m x k) * B(k x n), all row-major */
-static void mm(int m, int k, int n, const double *A, const double *B, double *C)
+static void mm(int m, int k, int n, const fso_real *A, const fso_real *B, fso_real *C)
 {
     for (int i = 0; i < m; i++)
         for (int j = 0; j < n; j++) {
-            double s = 0.0;
+            fso_real s = 0.0;
             for (int l = 0; l < k; l++) s += A[i * k + l] * B[l * n + j];
             C[i * n + j] = s;
         }
 }
 
 /* C(k x n) = A(m x k)^T * B(m x n) */
-static void mtm(int m, int k, int n, const double *A, const double *B, double *C)
+static void mtm(int m, int k, int n, const fso_real *A, const fso_real *B, fso_real *C)
 {
     for (int i = 0; i < k; i++)
         for (int j = 0; j < n; j++) {
-            double s = 0.0;
+            fso_real s = 0.0;
             for (int l = 0; l < m; l++) s += A[l * k + i] * B[l * n + j];
             C[i * n + j] = s;
         }
 }
 
+#ifndef FSO_QUAD
 static double wall_seconds(void)
 {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
+#endif
 
 /* ---------------------------------------------------------------- material (SA:273-294) */
 
-void fso_material_matrices(const fso_material *mat, double Dm[9], double Dp[9])
+void fso_material_matrices(const fso_material *mat, fso_real Dm[9], fso_real Dp[9])
 {
-    const double nu = mat->nu, E = mat->E, t = mat->thickness;
-    const double D[9] = {1.0, nu, 0.0, nu, 1.0, 0.0, 0.0, 0.0, (1.0 - nu) / 2.0};
-    const double cm = E / (1.0 - nu * nu);
-    const double cp = E * pow(t, 3.0) / (12.0 * (1.0 - nu * nu));
+    const fso_real nu = mat->nu, E = mat->E, t = mat->thickness;
+    const fso_real D[9] = {1.0, nu, 0.0, nu, 1.0, 0.0, 0.0, 0.0, (1.0 - nu) / 2.0};
+    const fso_real cm = E / (1.0 - nu * nu);
+    const fso_real cp = E * FSO_POW(t, 3.0) / (12.0 * (1.0 - nu * nu));
     for (int i = 0; i < 9; i++) {
         Dm[i] = cm * D[i];
         Dp[i] = cp * D[i];
@@ -67,28 +98,28 @@ void fso_material_matrices(const fso_material *mat, double Dm[9], double Dp[9])
 
 /* ---------------------------------------------------------------- TRI3 frame (SA:306-341, 378-411) */
 
-static void cross3(const double a[3], const double b[3], double c[3])
+static void cross3(const fso_real a[3], const fso_real b[3], fso_real c[3])
 {
     c[0] = a[1] * b[2] - a[2] * b[1];
     c[1] = a[2] * b[0] - a[0] * b[2];
     c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-static double norm3(const double a[3]) { return sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
+static fso_real norm3(const fso_real a[3]) { return FSO_SQRT(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
 
-static int tri3_frame(const double xyz[9], double trafo[9], double transUV[6], double dphi[6],
-                      double *area)
+static int tri3_frame(const fso_real xyz[9], fso_real trafo[9], fso_real transUV[6], fso_real dphi[6],
+                      fso_real *area)
 {
-    double U[3], V[3], W[3];
+    fso_real U[3], V[3], W[3];
     for (int i = 0; i < 3; i++) {
         U[i] = xyz[3 + i] - xyz[i]; /* B - A */
         V[i] = xyz[6 + i] - xyz[i]; /* C - A */
     }
     cross3(U, V, W);
-    const double lw = norm3(W), lu = norm3(U);
+    const fso_real lw = norm3(W), lu = norm3(U);
     if (!(lw > 0.0) || !(lu > 0.0)) return -1;
     *area = 0.5 * lw;
-    double ex[3], ey[3], ez[3];
+    fso_real ex[3], ey[3], ez[3];
     for (int i = 0; i < 3; i++) {
         ex[i] = U[i] / lu;
         ez[i] = W[i] / lw;
@@ -116,19 +147,19 @@ static int tri3_frame(const double xyz[9], double trafo[9], double transUV[6], d
 
 /* ---------------------------------------------------------------- TRI3 membrane, CST (SA:443-468) */
 
-static void tri3_membrane(const double dphi[6], double area, const double Dm[9], double t,
-                          double Ke_m[36])
+static void tri3_membrane(const fso_real dphi[6], fso_real area, const fso_real Dm[9], fso_real t,
+                          fso_real Ke_m[36])
 {
-    const double x12 = dphi[0], y12 = dphi[1], x31 = dphi[2], y31 = dphi[3], x23 = dphi[4],
+    const fso_real x12 = dphi[0], y12 = dphi[1], x31 = dphi[2], y31 = dphi[3], x23 = dphi[4],
                  y23 = dphi[5];
-    const double s = 1.0 / (2.0 * area);
-    double B[18] = {0};
+    const fso_real s = 1.0 / (2.0 * area);
+    fso_real B[18] = {0};
     B[0 * 6 + 0] = y23 * s;  B[0 * 6 + 2] = y31 * s;  B[0 * 6 + 4] = y12 * s;
     B[1 * 6 + 1] = -x23 * s; B[1 * 6 + 3] = -x31 * s; B[1 * 6 + 5] = -x12 * s;
     B[2 * 6 + 0] = -x23 * s; B[2 * 6 + 1] = y23 * s;
     B[2 * 6 + 2] = -x31 * s; B[2 * 6 + 3] = y31 * s;
     B[2 * 6 + 4] = -x12 * s; B[2 * 6 + 5] = y12 * s;
-    double DB[18];
+    fso_real DB[18];
     mm(3, 3, 6, Dm, B, DB);
     mtm(3, 6, 6, B, DB, Ke_m);
     for (int i = 0; i < 36; i++) Ke_m[i] *= t * area;
@@ -142,7 +173,7 @@ static void tri3_membrane(const double dphi[6], double area, const double Dm[9],
  * shellelements.tex:1148-1152; the factor 2 is SA:889-890). */
 
 #define PDEG 4 /* chi7..chi9 are quartic: L_j L_i^2 plus (L1 L2 L3) x (linear) */
-typedef struct { double c[PDEG + 1][PDEG + 1]; } poly; /* c[i][j] * L1^i * L2^j, i+j <= PDEG */
+typedef struct { fso_real c[PDEG + 1][PDEG + 1]; } poly; /* c[i][j] * L1^i * L2^j, i+j <= PDEG */
 
 static poly p_zero(void)
 {
@@ -151,7 +182,7 @@ static poly p_zero(void)
     return p;
 }
 
-static poly p_lin(double c0, double c1, double c2) /* c0 + c1 L1 + c2 L2 */
+static poly p_lin(fso_real c0, fso_real c1, fso_real c2) /* c0 + c1 L1 + c2 L2 */
 {
     poly p = p_zero();
     p.c[0][0] = c0;
@@ -160,7 +191,7 @@ static poly p_lin(double c0, double c1, double c2) /* c0 + c1 L1 + c2 L2 */
     return p;
 }
 
-static poly p_axpby(double a, const poly *x, double b, const poly *y)
+static poly p_axpby(fso_real a, const poly *x, fso_real b, const poly *y)
 {
     poly r;
     for (int i = 0; i <= PDEG; i++)
@@ -180,16 +211,16 @@ static poly p_mul(const poly *x, const poly *y)
 }
 
 /* (d2/dL1^2, d2/dL2^2, 2*d2/dL1dL2) of p at (L1,L2) */
-static void p_curv(const poly *p, double L1, double L2, double out[3])
+static void p_curv(const poly *p, fso_real L1, fso_real L2, fso_real out[3])
 {
-    double d11 = 0.0, d22 = 0.0, d12 = 0.0;
+    fso_real d11 = 0.0, d22 = 0.0, d12 = 0.0;
     for (int i = 0; i <= PDEG; i++)
         for (int j = 0; i + j <= PDEG; j++) {
-            const double c = p->c[i][j];
+            const fso_real c = p->c[i][j];
             if (c == 0.0) continue;
-            if (i >= 2) d11 += c * i * (i - 1) * pow(L1, i - 2) * pow(L2, j);
-            if (j >= 2) d22 += c * j * (j - 1) * pow(L1, i) * pow(L2, j - 2);
-            if (i >= 1 && j >= 1) d12 += c * i * j * pow(L1, i - 1) * pow(L2, j - 1);
+            if (i >= 2) d11 += c * i * (i - 1) * FSO_POW(L1, i - 2) * FSO_POW(L2, j);
+            if (j >= 2) d22 += c * j * (j - 1) * FSO_POW(L1, i) * FSO_POW(L2, j - 2);
+            if (i >= 1 && j >= 1) d12 += c * i * j * FSO_POW(L1, i - 1) * FSO_POW(L2, j - 1);
         }
     out[0] = d11;
     out[1] = d22;
@@ -197,7 +228,7 @@ static void p_curv(const poly *p, double L1, double L2, double out[3])
 }
 
 /* chi_1..chi_9 for the side ratios mu (SA:702-704) as polynomials */
-static void specht_chi(const double mu[3], poly chi[9])
+static void specht_chi(const fso_real mu[3], poly chi[9])
 {
     poly L[3];
     L[0] = p_lin(0.0, 1.0, 0.0);
@@ -210,7 +241,7 @@ static void specht_chi(const double mu[3], poly chi[9])
     poly L123 = p_mul(&chi[3], &L[2]);
     for (int i = 0; i < 3; i++) {
         const int j = (i + 1) % 3, k = (i + 2) % 3;
-        const double m = mu[k]; /* chi7 uses mu3, chi8 mu1, chi9 mu2 */
+        const fso_real m = mu[k]; /* chi7 uses mu3, chi8 mu1, chi9 mu2 */
         poly sq = p_mul(&L[i], &L[i]);
         poly lead = p_mul(&L[j], &sq);           /* L_j L_i^2 */
         poly a = p_axpby(3.0 * (1.0 - m), &L[i], -(1.0 + 3.0 * m), &L[j]);
@@ -222,7 +253,7 @@ static void specht_chi(const double mu[3], poly chi[9])
 
 /* rows of B~ from the curvature triples cc[n] of chi_1..chi_9 at one point: the shape functions are linear
  * combinations of the chi (shellelements.tex:1107-1111), and so are their curvatures */
-static void specht_compose(const double cc[9][3], const double dphi[6], double B[27])
+static void specht_compose(const fso_real cc[9][3], const fso_real dphi[6], fso_real B[27])
 {
     /* coordinate differences seen from node i: (x_ki, y_ki) and (x_ji, y_ji);
      * dphi rows are (12),(31),(23) */
@@ -230,12 +261,12 @@ static void specht_compose(const double cc[9][3], const double dphi[6], double B
     static const int row_ji[3] = {0, 2, 1};
     for (int i = 0; i < 3; i++) {
         const int k = (i + 2) % 3;
-        const double xki = dphi[2 * row_ki[i]], yki = dphi[2 * row_ki[i] + 1];
-        const double xji = -dphi[2 * row_ji[i]], yji = -dphi[2 * row_ji[i] + 1];
+        const fso_real xki = dphi[2 * row_ki[i]], yki = dphi[2 * row_ki[i] + 1];
+        const fso_real xji = -dphi[2 * row_ji[i]], yji = -dphi[2 * row_ji[i] + 1];
         for (int r = 0; r < 3; r++) {
-            const double d = cc[6 + k][r] - cc[3 + k][r];           /* chi_{k+6} - chi_{k+3} */
-            const double e = cc[6 + i][r] - cc[6 + k][r];
-            const double w = cc[i][r] - cc[3 + i][r] + cc[3 + k][r] + 2.0 * e;
+            const fso_real d = cc[6 + k][r] - cc[3 + k][r];           /* chi_{k+6} - chi_{k+3} */
+            const fso_real e = cc[6 + i][r] - cc[6 + k][r];
+            const fso_real w = cc[i][r] - cc[3 + i][r] + cc[3 + k][r] + 2.0 * e;
             B[r * 9 + 3 * i + 0] = w;
             B[r * 9 + 3 * i + 1] = -yki * d + yji * cc[6 + i][r];
             B[r * 9 + 3 * i + 2] = xki * d - xji * cc[6 + i][r];
@@ -243,13 +274,13 @@ static void specht_compose(const double cc[9][3], const double dphi[6], double B
     }
 }
 
-void fso_tri3_specht_B(const double C[3], double L1, double L2, const double dphi[6], double B[27])
+void fso_tri3_specht_B(const fso_real C[3], fso_real L1, fso_real L2, const fso_real dphi[6], fso_real B[27])
 {
     /* SA:702-704 */
-    const double mu[3] = {(C[0] - C[1]) / C[2], (C[2] - C[0]) / C[1], (C[1] - C[2]) / C[0]};
+    const fso_real mu[3] = {(C[0] - C[1]) / C[2], (C[2] - C[0]) / C[1], (C[1] - C[2]) / C[0]};
     poly chi[9];
     specht_chi(mu, chi);
-    double cc[9][3];
+    fso_real cc[9][3];
     for (int n = 0; n < 9; n++) p_curv(&chi[n], L1, L2, cc[n]);
     specht_compose(cc, dphi, B);
 }
@@ -259,21 +290,23 @@ void fso_tri3_specht_B(const double C[3], double L1, double L2, const double dph
  * those of chi_7..chi_9 are affine in one side ratio mu.  The tables are filled once from the polynomial machinery
  * above (values at mu = 0 and mu = 1), so the derivation stays the single source; fso_tri3_specht_B remains the
  * cross-check (tests/test_oracle_known_answers.py). */
-static const double kGauss[3][2] = {{1.0 / 6.0, 1.0 / 6.0}, {2.0 / 3.0, 1.0 / 6.0}, {1.0 / 6.0, 2.0 / 3.0}};
-static double g_chi0[3][9][3], g_chi1[3][3][3];
+#define FSO_SIXTH      (FSO_C(1.0) / FSO_C(6.0))
+#define FSO_TWO_THIRDS (FSO_C(2.0) / FSO_C(3.0))
+static const fso_real kGauss[3][2] = {{FSO_SIXTH, FSO_SIXTH}, {FSO_TWO_THIRDS, FSO_SIXTH}, {FSO_SIXTH, FSO_TWO_THIRDS}};
+static fso_real g_chi0[3][9][3], g_chi1[3][3][3];
 static int g_tables_ready = 0;
 
 void fso_init_tables(void)
 {
     if (g_tables_ready) return;
-    const double mu0[3] = {0.0, 0.0, 0.0}, mu1[3] = {1.0, 1.0, 1.0};
+    const fso_real mu0[3] = {0.0, 0.0, 0.0}, mu1[3] = {1.0, 1.0, 1.0};
     poly c0[9], c1[9];
     specht_chi(mu0, c0);
     specht_chi(mu1, c1);
     for (int g = 0; g < 3; g++) {
         for (int n = 0; n < 9; n++) p_curv(&c0[n], kGauss[g][0], kGauss[g][1], g_chi0[g][n]);
         for (int i = 0; i < 3; i++) {
-            double t[3];
+            fso_real t[3];
             p_curv(&c1[6 + i], kGauss[g][0], kGauss[g][1], t);
             for (int r = 0; r < 3; r++) g_chi1[g][i][r] = t[r] - g_chi0[g][6 + i][r];
         }
@@ -284,18 +317,18 @@ void fso_init_tables(void)
 static int g_specht_polynomial = 0;
 void fso_set_specht_polynomial(int on) { g_specht_polynomial = on; }
 
-static void specht_B_gauss(const double C[3], int g, const double dphi[6], double B[27])
+static void specht_B_gauss(const fso_real C[3], int g, const fso_real dphi[6], fso_real B[27])
 {
     if (g_specht_polynomial || !g_tables_ready) {
         fso_tri3_specht_B(C, kGauss[g][0], kGauss[g][1], dphi, B);
         return;
     }
-    const double mu[3] = {(C[0] - C[1]) / C[2], (C[2] - C[0]) / C[1], (C[1] - C[2]) / C[0]};
-    double cc[9][3];
+    const fso_real mu[3] = {(C[0] - C[1]) / C[2], (C[2] - C[0]) / C[1], (C[1] - C[2]) / C[0]};
+    fso_real cc[9][3];
     for (int n = 0; n < 6; n++)
         for (int r = 0; r < 3; r++) cc[n][r] = g_chi0[g][n][r];
     for (int i = 0; i < 3; i++) {
-        const double m = mu[(i + 2) % 3];
+        const fso_real m = mu[(i + 2) % 3];
         for (int r = 0; r < 3; r++) cc[6 + i][r] = g_chi0[g][6 + i][r] + m * g_chi1[g][i][r];
     }
     specht_compose(cc, dphi, B);
@@ -303,43 +336,43 @@ static void specht_B_gauss(const double C[3], int g, const double dphi[6], doubl
 
 /* ---------------------------------------------------------------- TRI3 plate (SA:555-603) */
 
-static void tri3_plate(const double dphi[6], double area, const double Dp[9], uint32_t flags,
-                       double Ke_p[81])
+static void tri3_plate(const fso_real dphi[6], fso_real area, const fso_real Dp[9], uint32_t flags,
+                       fso_real Ke_p[81])
 {
-    const double x31 = dphi[2], y31 = dphi[3], x23 = dphi[4], y23 = dphi[5];
-    double C[3];
+    const fso_real x31 = dphi[2], y31 = dphi[3], x23 = dphi[4], y23 = dphi[5];
+    fso_real C[3];
     for (int i = 0; i < 3; i++) C[i] = dphi[2 * i] * dphi[2 * i] + dphi[2 * i + 1] * dphi[2 * i + 1];
 
     /* SA:578-588; Y(2,1) as coded unless the flag is cleared */
-    double Y[9];
+    fso_real Y[9];
     Y[0] = y23 * y23;  Y[1] = y31 * y31;  Y[2] = y23 * y31;
     Y[3] = x23 * x23;  Y[4] = x31 * x31;  Y[5] = x31 * x23;
     Y[6] = -2.0 * x23 * y23;
     Y[7] = (flags & FSO_REF_Y21) ? -2.0 * x31 * x31 : -2.0 * x31 * y31;
     Y[8] = -x23 * y31 - x31 * y23;
-    const double sY = 1.0 / (4.0 * area * area);
+    const fso_real sY = 1.0 / (4.0 * area * area);
     for (int i = 0; i < 9; i++) Y[i] *= sY;
 
-    memset(Ke_p, 0, 81 * sizeof(double));
+    memset(Ke_p, 0, 81 * sizeof(fso_real));
     for (int g = 0; g < 3; g++) {
-        double B[27], YB[27], DYB[27], YtDYB[27], BtK[81];
+        fso_real B[27], YB[27], DYB[27], YtDYB[27], BtK[81];
         specht_B_gauss(C, g, dphi, B);
         mm(3, 3, 9, Y, B, YB);        /* Y B        */
         mm(3, 3, 9, Dp, YB, DYB);     /* Dp Y B     */
         mtm(3, 3, 9, Y, DYB, YtDYB);  /* Y^T Dp Y B */
         mtm(3, 9, 9, B, YtDYB, BtK);  /* B^T ...    */
-        for (int i = 0; i < 81; i++) Ke_p[i] += BtK[i] * (1.0 / 6.0);
+        for (int i = 0; i < 81; i++) Ke_p[i] += BtK[i] * FSO_SIXTH;
     }
     for (int i = 0; i < 81; i++) Ke_p[i] *= 2.0 * area;
 }
 
 /* ---------------------------------------------------------------- shell superposition (SA:999-1053) */
 
-static void shell_superpose(int nodes, const double *Ke_m, const double *Ke_p, uint32_t flags,
-                            double *K /* (6n)^2 node-major */)
+static void shell_superpose(int nodes, const fso_real *Ke_m, const fso_real *Ke_p, uint32_t flags,
+                            fso_real *K /* (6n)^2 node-major */)
 {
     const int N = 6 * nodes, nm = 2 * nodes, np = 3 * nodes;
-    memset(K, 0, (size_t)N * N * sizeof(double));
+    memset(K, 0, (size_t)N * N * sizeof(fso_real));
     for (int i = 0; i < nodes; i++)
         for (int j = 0; j < nodes; j++) {
             for (int a = 0; a < 2; a++)
@@ -348,24 +381,24 @@ static void shell_superpose(int nodes, const double *Ke_m, const double *Ke_p, u
             for (int a = 0; a < 3; a++)
                 for (int b = 0; b < 3; b++)
                     K[(6 * i + 2 + a) * N + 6 * j + 2 + b] = Ke_p[(3 * i + a) * np + 3 * j + b];
-            double d;
+            fso_real d;
             if (flags & FSO_REF_DRILL_MAX) {
                 /* as coded: max over the five "diagonal" entries of block (i,j), for every (i,j) */
                 d = Ke_m[(2 * i) * nm + 2 * j];
-                d = fmax(d, Ke_m[(2 * i + 1) * nm + 2 * j + 1]);
-                d = fmax(d, Ke_p[(3 * i) * np + 3 * j]);
-                d = fmax(d, Ke_p[(3 * i + 1) * np + 3 * j + 1]);
-                d = fmax(d, Ke_p[(3 * i + 2) * np + 3 * j + 2]);
+                d = FSO_FMAX(d, Ke_m[(2 * i + 1) * nm + 2 * j + 1]);
+                d = FSO_FMAX(d, Ke_p[(3 * i) * np + 3 * j]);
+                d = FSO_FMAX(d, Ke_p[(3 * i + 1) * np + 3 * j + 1]);
+                d = FSO_FMAX(d, Ke_p[(3 * i + 2) * np + 3 * j + 2]);
                 d /= 1000.0;
             } else {
                 /* thesis theory chapter (shellelements.tex:1722): smallest diagonal
                  * entry / 1000, diagonal node blocks only */
                 if (i != j) continue;
                 d = Ke_m[(2 * i) * nm + 2 * j];
-                d = fmin(d, Ke_m[(2 * i + 1) * nm + 2 * j + 1]);
-                d = fmin(d, Ke_p[(3 * i) * np + 3 * j]);
-                d = fmin(d, Ke_p[(3 * i + 1) * np + 3 * j + 1]);
-                d = fmin(d, Ke_p[(3 * i + 2) * np + 3 * j + 2]);
+                d = FSO_FMIN(d, Ke_m[(2 * i + 1) * nm + 2 * j + 1]);
+                d = FSO_FMIN(d, Ke_p[(3 * i) * np + 3 * j]);
+                d = FSO_FMIN(d, Ke_p[(3 * i + 1) * np + 3 * j + 1]);
+                d = FSO_FMIN(d, Ke_p[(3 * i + 2) * np + 3 * j + 2]);
                 d /= 1000.0;
             }
             K[(6 * i + 5) * N + 6 * j + 5] = d;
@@ -375,16 +408,16 @@ static void shell_superpose(int nodes, const double *Ke_m, const double *Ke_p, u
 /* ---------------------------------------------------------------- local -> global (SA:1061-1110) */
 
 /* Kg(node-major) = blockwise TSub^T K_ij TSub with TSub = diag(trafo, trafo) */
-static void rotate_blocks(int nodes, const double trafo[9], const double *K, double *Kg)
+static void rotate_blocks(int nodes, const fso_real trafo[9], const fso_real *K, fso_real *Kg)
 {
     const int N = 6 * nodes;
-    double TS[36] = {0};
+    fso_real TS[36] = {0};
     for (int h = 0; h < 2; h++)
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) TS[(3 * h + i) * 6 + 3 * h + j] = trafo[3 * i + j];
     for (int i = 0; i < nodes; i++)
         for (int j = 0; j < nodes; j++) {
-            double S[36], ST[36], R[36];
+            fso_real S[36], ST[36], R[36];
             for (int a = 0; a < 6; a++)
                 for (int b = 0; b < 6; b++) S[a * 6 + b] = K[(6 * i + a) * N + 6 * j + b];
             mm(6, 6, 6, S, TS, ST);
@@ -395,7 +428,7 @@ static void rotate_blocks(int nodes, const double trafo[9], const double *K, dou
 }
 
 /* node-major (6*i+alpha) -> variable-major (nodes*alpha+i), SA:1105-1109 */
-static void to_var_major(int nodes, const double *Knm, double *Kvm)
+static void to_var_major(int nodes, const fso_real *Knm, fso_real *Kvm)
 {
     const int N = 6 * nodes;
     for (int al = 0; al < 6; al++)
@@ -405,10 +438,10 @@ static void to_var_major(int nodes, const double *Knm, double *Kvm)
                     Kvm[(nodes * al + i) * N + nodes * be + j] = Knm[(6 * i + al) * N + 6 * j + be];
 }
 
-static int element_tri3_nm(const double xyz[9], const fso_material *mat, const double Dm[9],
-                           const double Dp[9], double Kg[324], fso_tri3_parts *parts)
+static int element_tri3_nm(const fso_real xyz[9], const fso_material *mat, const fso_real Dm[9],
+                           const fso_real Dp[9], fso_real Kg[324], fso_tri3_parts *parts)
 {
-    double trafo[9], transUV[6], dphi[6], area, Ke_m[36], Ke_p[81], Kl[324];
+    fso_real trafo[9], transUV[6], dphi[6], area, Ke_m[36], Ke_p[81], Kl[324];
     if (tri3_frame(xyz, trafo, transUV, dphi, &area)) return -1;
     tri3_membrane(dphi, area, Dm, mat->thickness, Ke_m);
     tri3_plate(dphi, area, Dp, mat->flags, Ke_p);
@@ -422,15 +455,15 @@ static int element_tri3_nm(const double xyz[9], const fso_material *mat, const d
         memcpy(parts->Ke_m, Ke_m, sizeof Ke_m);
         memcpy(parts->Ke_p, Ke_p, sizeof Ke_p);
         memcpy(parts->K_local, Kl, sizeof Kl);
-        memcpy(parts->K_global_nm, Kg, 324 * sizeof(double));
+        memcpy(parts->K_global_nm, Kg, 324 * sizeof(fso_real));
     }
     return 0;
 }
 
-int fso_element_tri3(const double xyz[9], const fso_material *mat, double Ke[324],
+int fso_element_tri3(const fso_real xyz[9], const fso_material *mat, fso_real Ke[324],
                      fso_tri3_parts *parts)
 {
-    double Dm[9], Dp[9], Kg[324];
+    fso_real Dm[9], Dp[9], Kg[324];
     fso_material_matrices(mat, Dm, Dp);
     fso_init_tables(); /* the same arithmetic as the global assembly */
     if (element_tri3_nm(xyz, mat, Dm, Dp, Kg, parts)) return -1;
@@ -440,21 +473,21 @@ int fso_element_tri3(const double xyz[9], const fso_material *mat, double Ke[324
 
 /* ---------------------------------------------------------------- QUAD4 frame (SA:342-375, 413-432) */
 
-static int quad4_frame(const double xyz[12], double trafo[9], double loc[12] /*3x4*/,
-                       double dphi[8] /*4x2*/, double *area)
+static int quad4_frame(const fso_real xyz[12], fso_real trafo[9], fso_real loc[12] /*3x4*/,
+                       fso_real dphi[8] /*4x2*/, fso_real *area)
 {
-    double mid[4][3]; /* midpoints of AB, BC, CD, DA */
+    fso_real mid[4][3]; /* midpoints of AB, BC, CD, DA */
     for (int s = 0; s < 4; s++)
         for (int i = 0; i < 3; i++) {
-            const double p = xyz[3 * s + i], q = xyz[3 * ((s + 1) % 4) + i];
+            const fso_real p = xyz[3 * s + i], q = xyz[3 * ((s + 1) % 4) + i];
             mid[s][i] = p + 0.5 * (q - p);
         }
-    double ex[3], ey[3], ez[3], vr[3];
+    fso_real ex[3], ey[3], ez[3], vr[3];
     for (int i = 0; i < 3; i++) {
         ex[i] = mid[1][i] - mid[3][i]; /* nJ - nL */
         vr[i] = mid[2][i] - mid[0][i]; /* nK - nI */
     }
-    double l = norm3(ex);
+    fso_real l = norm3(ex);
     if (!(l > 0.0)) return -1;
     for (int i = 0; i < 3; i++) ex[i] /= l;
     cross3(ex, vr, ez);
@@ -477,7 +510,7 @@ static int quad4_frame(const double xyz[12], double trafo[9], double loc[12] /*3
         dphi[2 * s + 0] = loc[0 * 4 + s] - loc[0 * 4 + (s + 1) % 4];
         dphi[2 * s + 1] = loc[1 * 4 + s] - loc[1 * 4 + (s + 1) % 4];
     }
-    double a = 0.0; /* shoelace formula */
+    fso_real a = 0.0; /* shoelace formula */
     for (int i = 0; i < 4; i++)
         a += loc[0 * 4 + i] * loc[1 * 4 + (i + 1) % 4] - loc[0 * 4 + (i + 1) % 4] * loc[1 * 4 + i];
     *area = 0.5 * a;
@@ -486,15 +519,15 @@ static int quad4_frame(const double xyz[12], double trafo[9], double loc[12] /*3
 
 /* ---------------------------------------------------------------- QUAD4 membrane (SA:469-541) */
 
-static void quad4_membrane(const double loc[12], const double Dm[9], double t, double Ke_m[64])
+static void quad4_membrane(const fso_real loc[12], const fso_real Dm[9], fso_real t, fso_real Ke_m[64])
 {
-    static const double rn[4] = {-1.0, 1.0, 1.0, -1.0}, sn[4] = {-1.0, -1.0, 1.0, 1.0};
-    const double root = sqrt(1.0 / 3.0);
-    memset(Ke_m, 0, 64 * sizeof(double));
+    static const fso_real rn[4] = {-1.0, 1.0, 1.0, -1.0}, sn[4] = {-1.0, -1.0, 1.0, 1.0};
+    const fso_real root = FSO_SQRT(FSO_C(1.0) / FSO_C(3.0));
+    memset(Ke_m, 0, 64 * sizeof(fso_real));
     for (int ii = 0; ii < 2; ii++)
         for (int jj = 0; jj < 2; jj++) {
-            const double r = (ii ? -root : root), s = (jj ? -root : root);
-            double dr[4], ds[4], J[4] = {0, 0, 0, 0};
+            const fso_real r = (ii ? -root : root), s = (jj ? -root : root);
+            fso_real dr[4], ds[4], J[4] = {0, 0, 0, 0};
             for (int n = 0; n < 4; n++) {
                 dr[n] = 0.25 * rn[n] * (1.0 + sn[n] * s);
                 ds[n] = 0.25 * sn[n] * (1.0 + rn[n] * r);
@@ -503,9 +536,9 @@ static void quad4_membrane(const double loc[12], const double Dm[9], double t, d
                 J[2] += ds[n] * loc[0 * 4 + n];
                 J[3] += ds[n] * loc[1 * 4 + n];
             }
-            const double det = J[0] * J[3] - J[1] * J[2];
+            const fso_real det = J[0] * J[3] - J[1] * J[2];
             /* A (3x4) maps (u_r,u_s,v_r,v_s) to strains, G (4x8) maps nodal (u,v) to those */
-            double A[12] = {0}, G[32] = {0}, B[24], DB[24], BtDB[64];
+            fso_real A[12] = {0}, G[32] = {0}, B[24], DB[24], BtDB[64];
             A[0 * 4 + 0] = J[3] / det;  A[0 * 4 + 1] = -J[1] / det;
             A[1 * 4 + 2] = -J[2] / det; A[1 * 4 + 3] = J[0] / det;
             A[2 * 4 + 0] = -J[2] / det; A[2 * 4 + 1] = J[0] / det;
@@ -525,13 +558,13 @@ static void quad4_membrane(const double loc[12], const double Dm[9], double t, d
 
 /* ---------------------------------------------------------------- QUAD4 plate, DKQ (SA:604-687, 901-990) */
 
-static void quad4_dkq_B(const double H[5][4], double xi, double eta, const double Jinv[4],
-                        double B[36])
+static void quad4_dkq_B(const fso_real H[5][4], fso_real xi, fso_real eta, const fso_real Jinv[4],
+                        fso_real B[36])
 {
     /* derivatives of the 8-node serendipity functions; corners (-1,-1),(1,-1),(1,1),(-1,1),
      * mid-sides 5..8 on sides 12,23,34,41  (SA:906-923) */
-    static const double xn[4] = {-1.0, 1.0, 1.0, -1.0}, en[4] = {-1.0, -1.0, 1.0, 1.0};
-    double Nx[8], Ne[8];
+    static const fso_real xn[4] = {-1.0, 1.0, 1.0, -1.0}, en[4] = {-1.0, -1.0, 1.0, 1.0};
+    fso_real Nx[8], Ne[8];
     for (int n = 0; n < 4; n++) {
         Nx[n] = 0.25 * xn[n] * (1.0 + eta * en[n]) * (2.0 * xi * xn[n] + eta * en[n]);
         Ne[n] = 0.25 * en[n] * (1.0 + xi * xn[n]) * (2.0 * eta * en[n] + xi * xn[n]);
@@ -541,13 +574,13 @@ static void quad4_dkq_B(const double H[5][4], double xi, double eta, const doubl
     Nx[6] = -xi * (1.0 + eta);          Ne[6] = 0.5 * (1.0 - xi * xi);
     Nx[7] = -0.5 * (1.0 - eta * eta);   Ne[7] = -eta * (1.0 - xi);
 
-    double Hx_x[12], Hy_x[12], Hx_e[12], Hy_e[12];
+    fso_real Hx_x[12], Hy_x[12], Hx_e[12], Hy_e[12];
     for (int n = 0; n < 4; n++) {
         const int sa = n, sb = (n + 3) % 4; /* the two sides meeting at node n (SA:931-981) */
-        const double *N[2] = {Nx, Ne};
-        double *Hx[2] = {Hx_x, Hx_e}, *Hy[2] = {Hy_x, Hy_e};
+        const fso_real *N[2] = {Nx, Ne};
+        fso_real *Hx[2] = {Hx_x, Hx_e}, *Hy[2] = {Hy_x, Hy_e};
         for (int d = 0; d < 2; d++) {
-            const double Na = N[d][4 + sa], Nb = N[d][4 + sb], Nn = N[d][n];
+            const fso_real Na = N[d][4 + sa], Nb = N[d][4 + sb], Nn = N[d][n];
             Hx[d][3 * n + 0] = 1.5 * (H[0][sa] * Na - H[0][sb] * Nb);
             Hx[d][3 * n + 1] = H[1][sa] * Na + H[1][sb] * Nb;
             Hx[d][3 * n + 2] = Nn - H[2][sa] * Na - H[2][sb] * Nb;
@@ -563,30 +596,30 @@ static void quad4_dkq_B(const double H[5][4], double xi, double eta, const doubl
     }
 }
 
-static void quad4_plate(const double dphi[8], const double Dp[9], double Ke_p[144])
+static void quad4_plate(const fso_real dphi[8], const fso_real Dp[9], fso_real Ke_p[144])
 {
-    double H[5][4];
+    fso_real H[5][4];
     for (int s = 0; s < 4; s++) {
-        const double x = dphi[2 * s], y = dphi[2 * s + 1], l2 = x * x + y * y;
+        const fso_real x = dphi[2 * s], y = dphi[2 * s + 1], l2 = x * x + y * y;
         H[0][s] = -x / l2;
         H[1][s] = 0.75 * x * y / l2;
         H[2][s] = (0.25 * x * x - 0.5 * y * y) / l2;
         H[3][s] = -y / l2;
         H[4][s] = (0.25 * y * y - 0.5 * x * x) / l2;
     }
-    const double root = sqrt(1.0 / 3.0);
-    memset(Ke_p, 0, 144 * sizeof(double));
+    const fso_real root = FSO_SQRT(FSO_C(1.0) / FSO_C(3.0));
+    memset(Ke_p, 0, 144 * sizeof(fso_real));
     for (int ii = 0; ii < 2; ii++)
         for (int jj = 0; jj < 2; jj++) {
-            const double r = (ii ? -root : root), s = (jj ? -root : root);
-            double J[4]; /* SA:641-645 */
+            const fso_real r = (ii ? -root : root), s = (jj ? -root : root);
+            fso_real J[4]; /* SA:641-645 */
             J[0] = 0.25 * ((dphi[0] + dphi[4]) * s - dphi[0] + dphi[4]);
             J[1] = 0.25 * ((dphi[1] + dphi[5]) * s - dphi[1] + dphi[5]);
             J[2] = 0.25 * ((dphi[0] + dphi[4]) * r - dphi[2] + dphi[6]);
             J[3] = 0.25 * ((dphi[1] + dphi[5]) * r - dphi[3] + dphi[7]);
-            const double det = J[0] * J[3] - J[1] * J[2];
-            const double Jinv[4] = {J[3] / det, -J[1] / det, -J[2] / det, J[0] / det};
-            double B[36], DB[36], BtDB[144];
+            const fso_real det = J[0] * J[3] - J[1] * J[2];
+            const fso_real Jinv[4] = {J[3] / det, -J[1] / det, -J[2] / det, J[0] / det};
+            fso_real B[36], DB[36], BtDB[144];
             quad4_dkq_B(H, r, s, Jinv, B);
             mm(3, 3, 12, Dp, B, DB);
             mtm(3, 12, 12, B, DB, BtDB);
@@ -594,10 +627,10 @@ static void quad4_plate(const double dphi[8], const double Dp[9], double Ke_p[14
         }
 }
 
-static int element_quad4_nm(const double xyz[12], const fso_material *mat, const double Dm[9],
-                            const double Dp[9], double Kg[576], double *Ke_m_out, double *Ke_p_out)
+static int element_quad4_nm(const fso_real xyz[12], const fso_material *mat, const fso_real Dm[9],
+                            const fso_real Dp[9], fso_real Kg[576], fso_real *Ke_m_out, fso_real *Ke_p_out)
 {
-    double trafo[9], loc[12], dphi[8], area, Ke_m[64], Ke_p[144], Kl[576];
+    fso_real trafo[9], loc[12], dphi[8], area, Ke_m[64], Ke_p[144], Kl[576];
     if (quad4_frame(xyz, trafo, loc, dphi, &area)) return -1;
     quad4_membrane(loc, Dm, mat->thickness, Ke_m);
     quad4_plate(dphi, Dp, Ke_p);
@@ -608,16 +641,18 @@ static int element_quad4_nm(const double xyz[12], const fso_material *mat, const
     return 0;
 }
 
-int fso_element_quad4(const double xyz[12], const fso_material *mat, double Ke[576], double *Ke_m,
-                      double *Ke_p, double *K_global_nm)
+int fso_element_quad4(const fso_real xyz[12], const fso_material *mat, fso_real Ke[576], fso_real *Ke_m,
+                      fso_real *Ke_p, fso_real *K_global_nm)
 {
-    double Dm[9], Dp[9], Kg[576];
+    fso_real Dm[9], Dp[9], Kg[576];
     fso_material_matrices(mat, Dm, Dp);
     if (element_quad4_nm(xyz, mat, Dm, Dp, Kg, Ke_m, Ke_p)) return -1;
     if (K_global_nm) memcpy(K_global_nm, Kg, sizeof Kg);
     to_var_major(4, Kg, Ke);
     return 0;
 }
+
+#ifndef FSO_QUAD /* pattern, assembly, products and solver exist in FP64 only */
 
 /* ---------------------------------------------------------------- sparsity pattern */
 
@@ -1082,3 +1117,4 @@ double fso_stream_triad(int64_t n, int32_t reps)
     free(a); free(b); free(c);
     return check == 7.0 ? best * 1e-9 : -1.0;
 }
+#endif /* !FSO_QUAD */
