@@ -18,6 +18,7 @@ REORDER_RCM = 0x20
 KERNEL_ASSEMBLE, KERNEL_SPMV, KERNEL_CG_UPDATE, KERNEL_CG_DIRECTION = 0, 1, 2, 3
 KERNEL_LUMPED_MASS, KERNEL_MASS_SHIFT, KERNEL_NEWMARK_RHS, KERNEL_NEWMARK_UPDATE = 4, 5, 6, 7
 KERNEL_SPMM, KERNEL_GRAM, KERNEL_BLOCK_COMBINE = 8, 9, 10
+KERNEL_ELEMENT_PRODUCT = 11
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -32,6 +33,7 @@ SYMBOLS = [
     "femshell_set_density", "femshell_lumped_mass", "femshell_dynamics_defaults", "femshell_dynamics_begin", "femshell_dynamics_step",
     "femshell_dynamics_accept", "femshell_dynamics_state", "femshell_dynamics_energy", "femshell_dynamics_end",
     "femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram",
+    "femshell_set_prescribed", "femshell_reactions", "femshell_element_product",
 ]
 
 
@@ -185,6 +187,9 @@ def load_library():
     L.femshell_modes.argtypes = [vp, C.POINTER(ModalOptions), dp, dp, dp, C.POINTER(ModalInfo)]
     L.femshell_spmm.argtypes = [vp, C.c_int32, dp, dp]
     L.femshell_modal_gram.argtypes = [vp, C.c_int32, dp, C.c_int32, dp, C.c_int32, dp]
+    L.femshell_set_prescribed.argtypes = [vp, C.c_int32, ip, dp]
+    L.femshell_reactions.argtypes = [vp, dp, dp]
+    L.femshell_element_product.argtypes = [vp, dp, dp]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -264,6 +269,32 @@ class FemShell:
         f6 = np.ascontiguousarray(f6, dtype=np.float64).reshape(-1, 6)
         ids = None if node_ids is None else np.ascontiguousarray(node_ids, dtype=np.int32)
         _check(self._L.femshell_set_loads(self._h, len(f6), _i(ids), _d(f6)))
+
+    def set_prescribed(self, u6, node_ids=None):
+        """Prescribed displacements (femshell_set_prescribed): u6 is (n, 6), one row per entry of node_ids or per node; only the
+        entries at dofs the Dirichlet set fixes are used.  set_prescribed(None) (or an empty array) clears them."""
+        if u6 is None:
+            _check(self._L.femshell_set_prescribed(self._h, 0, None, None))
+            return
+        u6 = np.ascontiguousarray(u6, dtype=np.float64).reshape(-1, 6)
+        ids = None if node_ids is None else np.ascontiguousarray(node_ids, dtype=np.int32)
+        if ids is not None and len(ids) != len(u6):
+            raise ValueError("u6 needs one row per entry of node_ids")
+        _check(self._L.femshell_set_prescribed(self._h, len(u6), _i(ids), _d(u6)))
+
+    def reactions(self, u=None):
+        """r = K_unc u - loads, (n_nodes, 6): the support reactions at fixed dofs, the negative residual at free ones.  u None:
+        the solution of the last solve, prescribed part included."""
+        r = np.zeros((self.n_nodes, 6))
+        _check(self._L.femshell_reactions(self._h, _d(self._node_vector(u, "u")), _d(r)))
+        return r
+
+    def element_product(self, x):
+        """y = K_unc x: the matrix-free product with the unconstrained stiffness (femshell_element_product)."""
+        x = self._node_vector(x, "x")
+        y = np.zeros_like(x)
+        _check(self._L.femshell_element_product(self._h, _d(x), _d(y)))
+        return y
 
     def set_sections(self, sections, tri_section=None, quad_section=None):
         """Shell sections: `sections` is an (n, 3) array-like of (nu, E, thickness), tri_section / quad_section give every

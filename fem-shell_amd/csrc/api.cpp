@@ -237,6 +237,8 @@ void forget_density(femshell_ctx *c)
     c->sec_rho.clear();
 }
 
+int do_rhs(femshell_ctx *c);
+
 int do_assemble(femshell_ctx *c, bool wait = true)
 {
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: no mesh set");
@@ -264,6 +266,10 @@ int do_assemble(femshell_ctx *c, bool wait = true)
     if (c->dyn.active) launch_mass_shift(c->dm, c->mass.p, c->dyn.k.shift, c->stream);
     if (events) FS_HIP(hipEventRecord(c->ev1, c->stream));
     FS_HIP(hipGetLastError());
+    if (c->have_prescribed) { // (the assembly kernel wrote the masked loads: F of the prescribed values behind it)
+        rc = do_rhs(c);
+        if (rc) return rc;
+    }
     if (wait) {
         rc = check_and_agree(c, "femshell_assemble");
         if (rc) return rc;
@@ -284,8 +290,46 @@ int do_assemble(femshell_ctx *c, bool wait = true)
     return FEMSHELL_OK;
 }
 
+// u_bar of the prescribed values and the Dirichlet set in force (femshell_set_prescribed): the entries at fixed dofs, zero
+// elsewhere, on the host and in HBM.  Single-rank contexts only: the owned rows are all rows.
+int resolve_prescribed(femshell_ctx *c)
+{
+    if (c->ubar_valid) return FEMSHELL_OK;
+    const Plan &p = c->plan;
+    c->ubar_host.assign((size_t)p.n_nodes * 6, 0.0);
+    bool nonzero = false;
+    for (int32_t a = 0; a < p.n_nodes; a++) {
+        const uint32_t fixed = c->dmask_global[(size_t)a];
+        for (int v = 0; v < 6 && fixed; v++)
+            if ((fixed >> v) & 1u) {
+                const double val = c->prescribed_global[6ull * (size_t)a + v];
+                c->ubar_host[6ull * (size_t)a + v] = val;
+                nonzero = nonzero || val != 0.0;
+            }
+    }
+    FS_HIP(c->ubar.alloc((size_t)p.n_local_nodes() * 6));
+    FS_HIP(c->ubar.zero(c->stream));
+    FS_HIP(hipMemcpyAsync(c->ubar.p, c->ubar_host.data(), (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(hipStreamSynchronize(c->stream));
+    c->ubar_nonzero = nonzero;
+    c->ubar_valid = true;
+    return FEMSHELL_OK;
+}
+
 int do_rhs(femshell_ctx *c)
 {
+    if (c->have_prescribed) {
+        // F = mask(loads - K_unc u_bar): one launch of the matrix-free product with the unconstrained element matrices, the
+        // masked combine in its epilogue.  (No fixed dof carries a non-zero value: the masked copy below, as without the call.)
+        const int rc = resolve_prescribed(c);
+        if (rc) return rc;
+        if (c->ubar_nonzero) {
+            launch_element_product(c->dm, c->mc, c->sections_or_null(), c->ubar.p, nullptr, c->loads.p, c->F.p, true, c->stream);
+            FS_HIP(hipGetLastError());
+            c->rhs_valid = true;
+            return FEMSHELL_OK;
+        }
+    }
     launch_rhs(c->dm, c->loads.p, c->F.p, c->stream);
     FS_HIP(hipGetLastError());
     c->rhs_valid = true;
@@ -711,6 +755,10 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     c->sec_thickness.clear();
     forget_density(c);
     c->dyn.reset(); // (a new mesh ends dynamics)
+    c->have_prescribed = c->ubar_valid = c->ubar_nonzero = false; // (... and forgets the prescribed displacements)
+    c->prescribed_global.clear();
+    c->ubar_host.clear();
+    c->ubar.release();
     c->ds = DeviceSections();
     c->sec_table.release();
     c->slice_elem_section.release();
@@ -913,6 +961,45 @@ int femshell_set_dirichlet(femshell_ctx *c, int32_t n, const int32_t *node_ids, 
     rc = upload_node_data(c, kNodeMasks);
     if (rc) return rc;
     c->matrix_valid = c->rhs_valid = c->jacobi_valid = false;
+    c->ubar_valid = false; // (which of the prescribed values count is decided by the new set)
+    return FEMSHELL_OK;
+}
+
+int femshell_set_prescribed(femshell_ctx *c, int32_t n, const int32_t *node_ids, const double *u6)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: null context");
+    if (c->cfg.world_size != 1)
+        return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_set_prescribed: single-rank contexts only (a row partition would need the ghost values of the prescribed displacements and a halo exchange in front of the element product)");
+    if (n > 0 && !u6) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: null argument");
+    if (c->assembly_pending) {
+        const int prc = finish_pending_assembly(c);
+        if (prc) return prc;
+    }
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: call femshell_set_mesh first");
+    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: not while dynamics is active (femshell_dynamics_end first)");
+    if (n < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: n < 0");
+    const int32_t nn = c->plan.n_nodes;
+    if (n == 0) { // clears
+        c->have_prescribed = c->ubar_valid = c->ubar_nonzero = false;
+        c->prescribed_global.clear();
+        c->ubar_host.clear();
+        c->rhs_valid = false;
+        return FEMSHELL_OK;
+    }
+    if (!node_ids && n != nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: dense form needs n == n_nodes");
+    std::vector<double> l((size_t)nn * 6, 0.0);
+    for (int32_t i = 0; i < n; i++) {
+        const int32_t a = node_ids ? node_ids[i] : i;
+        if (a < 0 || a >= nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: node id out of range");
+        for (int v = 0; v < 6; v++) {
+            if (!std::isfinite(u6[6ll * i + v])) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: non-finite value");
+            l[6ull * (size_t)(c->iperm.empty() ? a : c->iperm[a]) + v] = u6[6ll * i + v];
+        }
+    }
+    c->prescribed_global.swap(l);
+    c->have_prescribed = true;
+    c->ubar_valid = false;
+    c->rhs_valid = false; // (K, block-Jacobi and the multigrid hierarchy are kept)
     return FEMSHELL_OK;
 }
 
@@ -1515,7 +1602,8 @@ int femshell_set_initial_guess(femshell_ctx *c, const double *u0)
             for (int v = 0; v < 6; v++) {
                 const double val = u0[6ull * (size_t)node + v];
                 if (!std::isfinite(val)) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_initial_guess: non-finite entry");
-                h[6ull * (size_t)i + v] = val;
+                // (with prescribed displacements the iterate in HBM is the homogeneous part: zero on the fixed dofs)
+                h[6ull * (size_t)i + v] = (c->have_prescribed && ((c->dmask_global[(size_t)row] >> v) & 1u)) ? 0.0 : val;
             }
         }
         FS_HIP(c->x0.alloc(n6));
@@ -1535,7 +1623,18 @@ int femshell_get_solution(femshell_ctx *c, double *u_out)
     if (!c->have_solution) return set_err(FEMSHELL_ERR_INVALID, "femshell_get_solution: no solve has run");
     int rc = select_device(c);
     if (rc) return rc;
-    return gather_node_vector(c, c->x.p, u_out);
+    rc = gather_node_vector(c, c->x.p, u_out);
+    if (rc || !c->have_prescribed) return rc;
+    // the vector in HBM is the homogeneous part (zero on the fixed dofs): the prescribed values where the solution leaves
+    rc = resolve_prescribed(c);
+    if (rc) return rc;
+    for (int32_t a = 0; a < c->plan.n_nodes && c->ubar_nonzero; a++) {
+        const uint32_t fixed = c->dmask_global[(size_t)a];
+        const int32_t node = c->perm.empty() ? a : c->perm[(size_t)a];
+        for (int v = 0; v < 6 && fixed; v++)
+            if ((fixed >> v) & 1u) u_out[6ull * (size_t)node + v] = c->ubar_host[6ull * (size_t)a + v];
+    }
+    return FEMSHELL_OK;
 }
 
 static int gather_node_vector(femshell_ctx *c, const double *owned, double *u_out)
@@ -1715,6 +1814,78 @@ int femshell_spmv(femshell_ctx *c, const double *x, double *y)
     FS_HIP(hipStreamSynchronize(c->stream));
     for (int32_t i = 0; i < p.n_own && !yi.empty(); i++) std::memcpy(y + 6ull * c->perm[i], &yi[6ull * i], 6 * sizeof(double));
     return FEMSHELL_OK;
+}
+
+static int upload_owned_rows(femshell_ctx *c, const double *full, double *dst);
+static bool all_finite(const double *x, int64_t n);
+static int gather_node_vector(femshell_ctx *c, const double *owned, double *u_out);
+
+int femshell_element_product(femshell_ctx *c, const double *x, double *y)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_element_product: null context");
+    if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_element_product: single-rank contexts only");
+    if (!x || !y) return set_err(FEMSHELL_ERR_INVALID, "femshell_element_product: null argument");
+    if (c->assembly_pending) {
+        const int prc = finish_pending_assembly(c);
+        if (prc) return prc;
+    }
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_element_product: no mesh set");
+    int rc = select_device(c);
+    if (rc) return rc;
+    const Plan &p = c->plan;
+    DevBuf<double> dx, dy;
+    FS_HIP(dx.alloc((size_t)p.n_local_nodes() * 6));
+    FS_HIP(dy.alloc((size_t)p.n_pad * 6));
+    FS_HIP(dx.zero(c->stream));
+    std::vector<double> xi; // internal numbering when the library renumbered the nodes
+    if (!c->perm.empty()) {
+        xi.resize((size_t)p.n_own * 6);
+        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(&xi[6ull * i], x + 6ull * c->perm[i], 6 * sizeof(double));
+    }
+    FS_HIP(hipMemcpyAsync(dx.p, xi.empty() ? x : xi.data(), (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    launch_element_product(c->dm, c->mc, c->sections_or_null(), dx.p, nullptr, nullptr, dy.p, false, c->stream);
+    FS_HIP(hipGetLastError());
+    rc = check_status(c, "femshell_element_product"); // (synchronises: xi may go)
+    if (rc) return rc;
+    return gather_node_vector(c, dy.p, y);
+}
+
+int femshell_reactions(femshell_ctx *c, const double *u, double *r6_out)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: null context");
+    if (c->cfg.world_size != 1)
+        return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_reactions: single-rank contexts only (a row partition would need a halo exchange in front of the element product)");
+    if (!r6_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: null argument");
+    if (c->assembly_pending) {
+        const int prc = finish_pending_assembly(c);
+        if (prc) return prc;
+    }
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: no mesh set");
+    if (!u && !c->have_solution) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: no solve has run (pass u)");
+    const Plan &p = c->plan;
+    if (u && !all_finite(u, 6ll * p.n_nodes)) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: non-finite entry in u");
+    int rc = select_device(c);
+    if (rc) return rc;
+    DevBuf<double> dx, dy;
+    FS_HIP(dy.alloc((size_t)p.n_pad * 6));
+    const double *x = c->x.p, *xp = nullptr;
+    if (u) {
+        FS_HIP(dx.alloc((size_t)p.n_local_nodes() * 6));
+        FS_HIP(dx.zero(c->stream));
+        rc = upload_owned_rows(c, u, dx.p);
+        if (rc) return rc;
+        x = dx.p;
+    } else if (c->have_prescribed) { // the solution in HBM is the homogeneous part: the kernel adds u_bar entry by entry
+        rc = resolve_prescribed(c);
+        if (rc) return rc;
+        if (c->ubar_nonzero) xp = c->ubar.p;
+    }
+    // r = K_unc u - loads, the loads as set (not masked)
+    launch_element_product(c->dm, c->mc, c->sections_or_null(), x, xp, c->loads.p, dy.p, false, c->stream);
+    FS_HIP(hipGetLastError());
+    rc = check_status(c, "femshell_reactions");
+    if (rc) return rc;
+    return gather_node_vector(c, dy.p, r6_out);
 }
 
 // n_cols columns of n_nodes x 6 in the caller's numbering -> a block in HBM (column j at dst + j * ld; padding and ghost space zero)
@@ -1958,6 +2129,8 @@ int femshell_dynamics_begin(femshell_ctx *c, const femshell_dynamics_options *op
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: no mesh set");
     if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: dynamics is active already (femshell_dynamics_end first)");
     if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: no density set (femshell_set_density)");
+    if (c->have_prescribed)
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: prescribed displacements are in force (femshell_set_prescribed with n = 0 clears them)");
     const double dt = opt->dt, beta = opt->beta, gamma = opt->gamma, alpha = opt->alpha;
     if (!(std::isfinite(dt) && dt > 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need a finite dt > 0");
     if (!(std::isfinite(gamma) && gamma >= 0.5)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need gamma >= 1/2");
@@ -2405,6 +2578,34 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         }
         return FEMSHELL_OK;
     }
+    if (which == FEMSHELL_KERNEL_ELEMENT_PRODUCT) {
+        // the matrix-free product with the unconstrained element matrices on a hashed vector, back to back between one event pair
+        if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_time_kernel: the element product runs on single-rank contexts");
+        hipStream_t st = c->stream;
+        const Plan &p = c->plan;
+        const int64_t ld = (int64_t)p.n_local_nodes() * 6;
+        DevBuf<double> S, Y;
+        FS_HIP(S.alloc((size_t)ld));
+        FS_HIP(S.zero(st));
+        FS_HIP(Y.alloc((size_t)p.n_pad * 6));
+        launch_modal_init(c->dm, nullptr, 1, S.p, ld, st);
+        FS_HIP(hipStreamSynchronize(st));
+        FS_HIP(hipEventRecord(c->ev0, st));
+        for (int32_t i = 0; i < reps; i++) launch_element_product(c->dm, c->mc, c->sections_or_null(), S.p, nullptr, nullptr, Y.p, false, st);
+        FS_HIP(hipEventRecord(c->ev1, st));
+        FS_HIP(hipGetLastError());
+        rc = check_status(c, "femshell_time_kernel");
+        if (rc) return rc;
+        float ms = 0.f;
+        FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *mean_ms_out = (double)ms / reps;
+        // coordinates once per node, the node ids of the slices' element lists (16 B per entry, counted as listed, as for the
+        // lumped mass; a section index beside each where the context has sections), x read and y written once per node.  (What
+        // the lanes of phase B gather of x beyond that comes from the caches: overhead of the method, not algorithmic traffic.)
+        if (bytes_out)
+            *bytes_out = 24.0 * p.n_own + (16.0 + (c->have_sections ? 4.0 : 0.0)) * (double)p.slice_elem_nodes.size() / 4.0 + 96.0 * p.n_own;
+        return FEMSHELL_OK;
+    }
     if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->matrix_valid) {
         rc = do_assemble(c);
         if (rc) return rc;
@@ -2489,6 +2690,7 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         if (rc) return rc;
         c->matrix_valid = true;
         c->jacobi_valid = false;
+        if (c->have_prescribed) c->rhs_valid = false; // (the assembly kernel wrote the masked loads over F)
     }
     return FEMSHELL_OK;
 }

@@ -540,6 +540,13 @@ struct femshell_ctx {
             cur = 0;
         }
     } dyn;
+    // prescribed displacements (femshell_set_prescribed): the values as the caller gave them (n_nodes x 6, internal numbering; which
+    // of them count is decided by the Dirichlet set when the right-hand side is built) and u_bar in HBM -- the entries at fixed dofs,
+    // zero elsewhere -- resolved by resolve_prescribed (api.cpp) after every change of either.  The solution vector in HBM stays the
+    // homogeneous part; u_bar is added where a solution leaves the library.
+    bool have_prescribed = false, ubar_valid = false, ubar_nonzero = false;
+    std::vector<double> prescribed_global, ubar_host;
+    femshell::DevBuf<double> ubar;
     // CG state
     femshell::DevBuf<double> x, r, z, p, q, sv, partials, hist, sendbuf, ufull;
     femshell::DevBuf<double> xacc, rres; // iterative refinement of the multigrid-preconditioned solve: accumulated solution, residual

@@ -179,6 +179,15 @@ void launch_status_flags(const int32_t *status, double *agree, hipStream_t st);
 void launch_element_matrices(const DeviceMatrix &m, const MatConst &mc, int32_t first, int32_t count,
                              double *Ke_out, hipStream_t st, const DeviceSections *sections = nullptr);
 
+// Matrix-free product with the UNCONSTRAINED stiffness (element_product.hip), from the slices' element lists and the element
+// routines of shell_element.hpp: y = sum_e K_e (x + xp)_e - sub on the owned rows, zero on padding rows; xp (a second input, added to
+// x entry by entry) and sub may be nullptr.  rhs: y = mask(sub - sum_e K_e (x + xp)_e) instead, zero on the fixed dofs -- the
+// right-hand side of prescribed displacements.  x and xp hold n_pad + n_ghost nodes, sub and y n_pad.  No atomics, the additions
+// of a row in the order of its slice's element list: two launches give the same bits.  A degenerate element reports through
+// m.status as in launch_assemble.
+void launch_element_product(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const double *x, const double *xp,
+                            const double *sub, double *y, bool rhs, hipStream_t st);
+
 // y = K x; when partials != nullptr also partials[wg] = sum over the workgroup's rows of x*y
 // (s != nullptr: no-op once s->done != 0)
 void launch_spmv(const DeviceMatrix &m, const double *x, double *y, double *partials, const CgScalars *s,

@@ -45,6 +45,49 @@ bool has_flag(int argc, char **argv, const char *flag)
 
 } // namespace
 
+// -prescribed FILE into p.prescribed_*: the conventions of the -sections reader ('#' comments, blank lines, file and line number
+// in every message)
+static void read_prescribed(Parameters &p)
+{
+    std::ifstream in(p.prescribed_file);
+    if (!in) throw std::runtime_error("cannot open " + p.prescribed_file);
+    p.prescribed_nodes.clear();
+    p.prescribed_lines.clear();
+    p.prescribed_values.clear();
+    std::string line;
+    for (int no = 1; std::getline(in, line); no++) {
+        const size_t h = line.find('#');
+        if (h != std::string::npos) line.erase(h);
+        std::istringstream is(line);
+        std::string first;
+        if (!(is >> first)) continue; // blank or comment
+        const std::string where = p.prescribed_file + ": line " + std::to_string(no) + ": ";
+        char *end = nullptr;
+        const long node = std::strtol(first.c_str(), &end, 10);
+        double v[6];
+        std::string rest;
+        if (*end != '\0' || !(is >> v[0] >> v[1] >> v[2] >> v[3] >> v[4] >> v[5]) || (is >> rest))
+            throw std::runtime_error(where + "expected 'node u v w tx ty tz'");
+        for (double x : v)
+            if (!std::isfinite(x)) throw std::runtime_error(where + "a value is not finite");
+        if (node < 0 || node > 2147483647L) throw std::runtime_error(where + "node id " + first + " is out of range");
+        if (std::find(p.prescribed_nodes.begin(), p.prescribed_nodes.end(), (int32_t)node) != p.prescribed_nodes.end())
+            throw std::runtime_error(where + "node " + first + " is listed twice");
+        p.prescribed_nodes.push_back((int32_t)node);
+        p.prescribed_lines.push_back(no);
+        p.prescribed_values.insert(p.prescribed_values.end(), v, v + 6);
+    }
+}
+
+// ... and against the mesh: every listed node must exist
+static void check_prescribed_nodes(const Parameters &p, int32_t n_nodes)
+{
+    for (size_t i = 0; i < p.prescribed_nodes.size(); i++)
+        if (p.prescribed_nodes[i] >= n_nodes)
+            throw std::runtime_error(p.prescribed_file + ": line " + std::to_string(p.prescribed_lines[i]) + ": node id " +
+                                     std::to_string(p.prescribed_nodes[i]) + " is out of range (the mesh has " + std::to_string(n_nodes) + " nodes)");
+}
+
 bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, std::ostream &err)
 {
     if (argc < 5) {
@@ -71,7 +114,10 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-modes:\t with -rho: the N lowest natural frequencies and mode shapes instead of a solve (N in 1 .. 28); writes\n"
             << "\t <out>_modes.txt, lines 'index lambda f residual', and the shapes as point arrays mode_<k>_u / mode_<k>_r of <out>.vtk\n"
             << "-modes_tol:\t tolerance of the pairs' residuals (with -modes, default 1e-6)\n"
-            << "-modes_shift:\t shift S >= 0: solves with K + S M (with -modes; an unconstrained shell needs S > 0; default 0)\n";
+            << "-modes_shift:\t shift S >= 0: solves with K + S M (with -modes; an unconstrained shell needs S > 0; default 0)\n"
+            << "-prescribed:\t file of lines 'node u v w tx ty tz': prescribed displacements of the dofs the boundary ids fix (optional)\n"
+            << "-reactions:\t writes <out>_reactions.txt, lines 'node rx ry rz mx my mz' of the nodes with a fixed dof and a line 'sum',\n"
+            << "\t and the point arrays reaction_f / reaction_m of <out>.vtk (optional)\n";
         return false;
     }
     bool failed = false;
@@ -228,6 +274,34 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             failed = true;
         }
     }
+    // prescribed displacements and reactions: the file is read here, so that a missing file or a malformed line is refused
+    // like any other option (the node ids are held against the mesh as soon as it is read, still before any device is touched)
+    if (has_flag(argc, argv, "-prescribed")) {
+        const char *v = arg_after(argc, argv, "-prescribed");
+        p.prescribed_file = v ? v : "";
+        if (!v) {
+            err << "ERROR: -prescribed needs a file!\n";
+            failed = true;
+        } else {
+            try {
+                read_prescribed(p);
+            } catch (const std::exception &e) {
+                err << "ERROR: " << e.what() << "\n";
+                failed = true;
+            }
+        }
+        if (has_flag(argc, argv, "-modes") || has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps")) {
+            err << "ERROR: -prescribed does not go together with -modes or the time stepping options -dt / -steps!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-reactions")) {
+        p.reactions = true;
+        if (has_flag(argc, argv, "-modes") || has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps")) {
+            err << "ERROR: -reactions belongs to the static solve: not with -modes or the time stepping options -dt / -steps!\n";
+            failed = true;
+        }
+    }
 
     out << "Run program with parameters:"
         << " debug messages = " << (p.debug ? "true" : "false") << ", nu = " << p.nu << ", E = " << p.em
@@ -367,6 +441,7 @@ void ShellSystem::set_mesh(const ShellMesh &m)
           "femshell_set_mesh");
     const std::vector<uint8_t> mask = m.dirichlet_mask();
     check(femshell_set_dirichlet(ctx_, m.n_nodes(), nullptr, mask.data()), "femshell_set_dirichlet");
+    mask_ = mask;
     if (!m.loads.empty()) set_forces(m.loads);
 }
 
@@ -375,6 +450,20 @@ void ShellSystem::set_sections(const SectionTable &t)
     check(femshell_set_sections(ctx_, (int32_t)t.sections.size(), t.sections.data(), t.tri_section.empty() ? nullptr : t.tri_section.data(),
                                 t.quad_section.empty() ? nullptr : t.quad_section.data()),
           "femshell_set_sections");
+}
+
+void ShellSystem::set_prescribed(const Parameters &p)
+{
+    check_prescribed_nodes(p, n_nodes_);
+    check(femshell_set_prescribed(ctx_, (int32_t)p.prescribed_nodes.size(), p.prescribed_nodes.data(), p.prescribed_values.data()),
+          "femshell_set_prescribed");
+}
+
+std::vector<double> ShellSystem::reactions()
+{
+    std::vector<double> r((size_t)n_nodes_ * 6, 0.0);
+    check(femshell_reactions(ctx_, nullptr, r.data()), "femshell_reactions");
+    return r;
 }
 
 SectionTable read_sections(const Parameters &p, ShellMesh &mesh)
@@ -581,12 +670,18 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         }
         SectionTable section_table;
         if (p.sections_requested()) section_table = read_sections(p, mesh);
+        if (p.prescribed_requested()) check_prescribed_nodes(p, mesh.n_nodes()); // (before any device is touched)
         clock.done("read mesh and loads");
         const Launch launch = Launch::from_environment();
         ShellSystem system(p, launch);
         clock.done("context (device, ranks)");
         system.set_mesh(mesh);
         if (p.sections_requested()) system.set_sections(section_table);
+        if (p.prescribed_requested()) {
+            if (launch.world_size != 1) throw std::runtime_error("-prescribed runs on one rank");
+            system.set_prescribed(p);
+        }
+        if (p.reactions && launch.world_size != 1) throw std::runtime_error("-reactions runs on one rank");
         clock.done("symbolic phase, boundary conditions, loads");
         if (p.modes_requested()) {
             // natural frequencies and mode shapes instead of a solve
@@ -701,9 +796,40 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         }
         out << "]" << std::endl << std::endl;
         clock.done("print the solution");
+        std::vector<PointVectors> reaction_arrays;
+        if (p.reactions) {
+            // what the supports carry: a line per node with a fixed dof, then the column sums over all nodes (at free dofs r is
+            // the negative residual of the solve: the force columns of the sum balance the loads)
+            const std::vector<double> r = system.reactions();
+            const std::vector<uint8_t> &mask = system.dirichlet_mask();
+            const std::string stem = p.isOutfileSet ? p.out_filename : std::string("out");
+            std::ofstream rf(stem + "_reactions.txt");
+            if (!rf) throw std::runtime_error("cannot write " + stem + "_reactions.txt");
+            double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            char line[240];
+            for (int32_t n = 0; n < mesh.n_nodes(); n++) {
+                const double *q = &r[6 * (size_t)n];
+                for (int v = 0; v < 6; v++) sum[v] += q[v];
+                if (!mask[(size_t)n]) continue;
+                snprintf(line, sizeof line, "%d %.15e %.15e %.15e %.15e %.15e %.15e\n", n, q[0], q[1], q[2], q[3], q[4], q[5]);
+                rf << line;
+            }
+            snprintf(line, sizeof line, "sum %.15e %.15e %.15e %.15e %.15e %.15e\n", sum[0], sum[1], sum[2], sum[3], sum[4], sum[5]);
+            rf << line;
+            out << "Support reactions: sum of the forces = (" << sum[0] << ", " << sum[1] << ", " << sum[2] << "), in " << stem << "_reactions.txt"
+                << std::endl;
+            for (int part = 0; part < 2; part++) {
+                PointVectors a;
+                a.name = part == 0 ? "reaction_f" : "reaction_m";
+                a.xyz.resize((size_t)mesh.n_nodes() * 3);
+                for (int32_t n = 0; n < mesh.n_nodes(); n++)
+                    for (int d = 0; d < 3; d++) a.xyz[3 * (size_t)n + d] = r[6 * (size_t)n + 3 * part + d];
+                reaction_arrays.push_back(std::move(a));
+            }
+        }
         if (p.isOutfileSet) {
             write_exodus(mesh, sols, p.out_filename + ".e"); // the reference's file (fem-shell.cpp:1249)
-            write_vtk(mesh, sols, p.out_filename + ".vtk");
+            write_vtk(mesh, sols, p.out_filename + ".vtk", p.reactions ? &reaction_arrays : nullptr);
             clock.done("output files");
         }
         out << "All done :)\n";

@@ -68,6 +68,18 @@ struct Parameters {
     int modes = 0;
     double modes_tol = 1e-6, modes_shift = 0.0;
     bool modes_requested() const { return modes > 0; }
+    // prescribed displacements and support reactions (extension, stand-alone program only; the reference fixes dofs to zero,
+    // fem-shell.cpp:90-120).  -prescribed FILE: lines "node u v w tx ty tz" ('#' starts a comment), the values of the dofs the
+    // boundary ids fix at that node (femshell_set_prescribed: entries at free dofs are ignored).  The file is read with the
+    // command line (read_parameters), the node ids are held against the mesh before any device is touched.  -reactions:
+    // writes <out>_reactions.txt -- a line "node rx ry rz mx my mz" (%.15e) per node with a fixed dof, then "sum" and the six
+    // column sums over ALL nodes -- and the point arrays reaction_f / reaction_m of <out>.vtk (femshell_reactions).
+    std::string prescribed_file;
+    std::vector<int32_t> prescribed_nodes; // node of every line of the file
+    std::vector<int> prescribed_lines;     // ... and its line number
+    std::vector<double> prescribed_values; // ... and its six values
+    bool reactions = false;
+    bool prescribed_requested() const { return !prescribed_file.empty(); }
 };
 
 // what femshell_set_sections takes, from the files above: section 0 is the command line's material, the listed ones follow
@@ -133,6 +145,12 @@ class ShellSystem {
     void set_mesh(const ShellMesh &m);
     void set_forces(const std::vector<double> &f6); // n_nodes x 6, replaces the `forces` global
     void set_sections(const SectionTable &t);       // after set_mesh (femshell_set_mesh forgets the sections)
+    // -prescribed: the file's values (after set_mesh; throws on a node the mesh does not have, with file and line)
+    void set_prescribed(const Parameters &p);
+    // -reactions: r = K_unc u - loads of the last solve's solution, n_nodes x 6
+    std::vector<double> reactions();
+    // per node: the Dirichlet mask in force (what set_mesh derived from the boundary ids)
+    const std::vector<uint8_t> &dirichlet_mask() const { return mask_; }
     // the assembly callback (SA:1160-1233); the name argument is checked like SA:1163
     void assemble_elasticity(const std::string &system_name = "Elasticity");
     // equation_systems.solve(): runs the callback if K is not current, then the Krylov solve
@@ -156,6 +174,7 @@ class ShellSystem {
     int n_nodes_ = 0, rank_ = 0;
     bool solved_once_ = false; // later solves start from the solution before (libMesh's initial guess: ShellSystem::solve)
     std::vector<double> sols_;
+    std::vector<uint8_t> mask_;
 };
 
 // The stand-alone program (SA:14-185); returns the process exit code.

@@ -109,6 +109,29 @@ int femshell_set_sections(femshell_ctx *ctx, int32_t n_sections, const femshell_
  * Calling it again replaces the previous set. */
 int femshell_set_dirichlet(femshell_ctx *ctx, int32_t n, const int32_t *node_ids, const uint8_t *mask6);
 
+/* extends: the homogeneous DirichletBoundary of the reference (SA:90-120, every fixed dof is fixed to 0) to NON-ZERO prescribed
+ * displacements: support settlement, displacement-controlled loading, a sub-model driven by a coarse model's displacements.
+ * u6[n][6]; the argument forms of femshell_set_loads: node_ids == NULL needs n == n_nodes, nodes not listed get 0, n == 0 clears;
+ * a non-finite value returns FEMSHELL_ERR_INVALID and leaves the values that were in force untouched.  Only the entries at dofs
+ * the Dirichlet set fixes are used -- entries at free dofs are IGNORED --, and that is decided when the right-hand side is built:
+ * the order of femshell_set_dirichlet and femshell_set_prescribed does not matter.  femshell_set_mesh forgets the values.
+ *
+ * With u = u_h + u_bar (u_bar: the prescribed values at the fixed dofs, 0 elsewhere) the system solved is the one of the
+ * homogeneous set with the right-hand side
+ *     F = mask(loads - K_unc u_bar),
+ * K_unc the stiffness WITHOUT constraints.  K_unc is never stored (the assembly writes zero rows and columns with a counting
+ * diagonal at fixed dofs): the product is formed on the device from the element matrices (csrc/element_product.hip), one launch
+ * per right-hand side.  Only the right-hand side is rebuilt: K, block-Jacobi and the multigrid hierarchy are kept.  With no fixed
+ * dof carrying a non-zero value the right-hand side is built exactly as without this call.
+ * The solvers and the solution vector in HBM see the homogeneous part u_h (zero on fixed dofs; femshell_set_initial_guess(NULL)
+ * starts from it, an explicit u0 counts on the free dofs only); u_bar is put in where a solution leaves the library:
+ * femshell_get_solution and u_out of femshell_solve return u, with the prescribed values at the fixed dofs bit for bit.
+ * femshell_export_bsr's F and femshell_residual see the F above.  femshell_modes is unaffected (it solves on the free dofs).
+ * FEMSHELL_ERR_INVALID while dynamics is active (and femshell_dynamics_begin returns it while prescribed values are in force, i.e.
+ * until n == 0 clears them: a Newmark step with moving supports is an open end).  FEMSHELL_ERR_UNSUPPORTED on a row-partitioned
+ * context (world_size != 1): the ghost values of u_bar and a halo exchange in front of the element product are an open end. */
+int femshell_set_prescribed(femshell_ctx *ctx, int32_t n, const int32_t *node_ids, const double *u6);
+
 /* replaces: the global `forces` vector read by contribRHS (SA:44-67, 1118-1153; PC:1377-1438).
  * f6[n][6] nodal forces and moments; node_ids == NULL: one row per node (n == n_nodes).
  * Nodes not listed get zero load.  Only the right-hand side is rebuilt. */
@@ -291,6 +314,16 @@ int femshell_assembly_kernel(femshell_ctx *ctx);
 int femshell_solve(femshell_ctx *ctx, double rtol, int32_t max_it, double *u_out,
                    femshell_solve_info *info);
 int femshell_get_solution(femshell_ctx *ctx, double *u_out);
+/* extends: the reference writes displacements only (SA:141-169); this gives what the supports carry.
+ *     r = K_unc u - loads
+ * with the unconstrained stiffness (the element product of femshell_set_prescribed) and the loads as set, NOT masked.  At free
+ * dofs r is the negative residual of the solve; at fixed dofs it is the support reaction: force (u, v, w) and moment (tx, ty,
+ * tz) the support exerts on the shell.  The translations are in the null space of K_unc, so the force columns of r summed over
+ * all nodes balance the summed loads.  u: n_nodes x 6 in the caller's numbering, or NULL: the solution of the last solve,
+ * prescribed part included (taken where it lies in HBM).  r6_out: n_nodes x 6, the caller's numbering (FEMSHELL_REORDER too).
+ * Needs a mesh, not an assembled K.  Sums in a fixed order: two calls give the same bits, and the NULL form gives the bits of the
+ * explicit one.  FEMSHELL_ERR_UNSUPPORTED on a row-partitioned context (world_size != 1). */
+int femshell_reactions(femshell_ctx *ctx, const double *u /* n_nodes x 6, or NULL */, double *r6_out /* n_nodes x 6 */);
 /* The NEXT femshell_solve of this context starts from u0 (n_nodes x 6, the caller's numbering; every rank passes the whole vector
  * and keeps its own rows) instead of from zero; u0 == NULL: from the solution of the context's previous solve, where it lies in
  * HBM (no transfer).  Consumed by that solve; femshell_set_mesh forgets it.
@@ -409,6 +442,10 @@ int64_t femshell_nnz_blocks(femshell_ctx *ctx); /* number of 6x6 blocks of K on 
 int femshell_export_bsr(femshell_ctx *ctx, int32_t *rowptr, int32_t *colidx, double *vals, double *F);
 /* y = K x on the device */
 int femshell_spmv(femshell_ctx *ctx, const double *x, double *y);
+/* y = K_unc x on the device: the product with the UNCONSTRAINED stiffness, formed from the element matrices (no Dirichlet rows,
+ * whatever femshell_set_dirichlet holds; csrc/element_product.hip).  x, y: n_nodes x 6, the caller's numbering.  Single-rank
+ * contexts (FEMSHELL_ERR_UNSUPPORTED otherwise); needs a mesh only, not an assembled K.  A degenerate element: FEMSHELL_ERR_MESH. */
+int femshell_element_product(femshell_ctx *ctx, const double *x, double *y);
 /* Y = K X for a block of n_cols (1 .. 96) vectors, column j at X + j * n_nodes * 6: the block product of femshell_modes; same
  * preconditions as femshell_spmv */
 int femshell_spmm(femshell_ctx *ctx, int32_t n_cols, const double *X, double *Y);   /* Y = K X, columns of n_nodes x 6 */
@@ -471,7 +508,10 @@ typedef enum femshell_kernel {
     FEMSHELL_KERNEL_SPMM = 8,         /* Y = K X for c columns, both phases (FEMSHELL_SPMM_FUSED=0: column by column through
                                          the single-vector kernels, the yardstick of the fused kernel) */
     FEMSHELL_KERNEL_GRAM = 9,         /* S^T M S for 3c columns */
-    FEMSHELL_KERNEL_BLOCK_COMBINE = 10 /* 2c columns out of 3c */
+    FEMSHELL_KERNEL_BLOCK_COMBINE = 10, /* 2c columns out of 3c */
+    /* k_element_product (y = K_unc x, matrix-free) back to back on a hashed vector; needs a mesh only.  bytes_out: coordinates,
+     * the node ids of the slices' element lists, x read, y written */
+    FEMSHELL_KERNEL_ELEMENT_PRODUCT = 11
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
