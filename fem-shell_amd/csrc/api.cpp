@@ -1,11 +1,9 @@
-// api.cpp -- the C ABI of libfemshell (include/femshell.h): context, host<->HBM plumbing, measurement hooks.
-// The CG driver is cg_driver.cpp, the plan inspection entry points plan_api.cpp.  All arithmetic of the hot path
-// runs in the kernels of kernels.hip; there is no CPU fallback anywhere in this library.
-#include "amg_device.hpp"
-#include "context.hpp"
-#include "modal.hpp"
+// api.cpp -- the C ABI of libfemshell (include/femshell.h): context, communication, mesh and the data on it, assembly, solve,
+// export and products.  Dynamics: api_dynamics.cpp; modal analysis: api_modal.cpp; measurement hooks: api_timing.cpp; node ids and
+// node vectors across the boundary: node_io.cpp.  The CG driver is cg_driver.cpp, the plan inspection entry points plan_api.cpp.
+// All arithmetic of the hot path runs in the kernels of kernels.hip; there is no CPU fallback anywhere in this library.
+#include "api_internal.hpp"
 #include "reorder.hpp"
-#include "trace.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -21,7 +19,23 @@ namespace femshell {
 
 namespace {
 thread_local std::string g_err;
-}
+
+// The operands of a product y = A x through the C ABI: x from the host (owned rows | padding | ghost space, zero beyond the owned
+// rows; hx null: the caller has its x in HBM already) and a zeroed y beside it.
+struct ProductBuffers {
+    DevBuf<double> x, y;
+    std::vector<double> stage; // (upload_node_block: lives until the product is synchronised)
+    int upload(femshell_ctx *c, NodeOrder order, const double *hx)
+    {
+        const size_t ld = (size_t)c->plan.n_local_nodes() * 6;
+        FS_HIP(y.alloc((size_t)c->plan.n_pad * 6));
+        FS_HIP(y.zero(c->stream));
+        if (!hx) return FEMSHELL_OK;
+        FS_HIP(x.alloc(ld));
+        return upload_node_block(c, order, 1, hx, x.p, ld, &stage);
+    }
+};
+} // namespace
 
 int set_err(int code, const std::string &msg)
 {
@@ -31,53 +45,16 @@ int set_err(int code, const std::string &msg)
 
 const std::string &last_err() { return g_err; }
 
-} // namespace femshell
-
-namespace {
-
 int select_device(femshell_ctx *c)
 {
     FS_HIP(hipSetDevice(c->device));
     return FEMSHELL_OK;
 }
 
-int64_t real_blocks(const femshell_ctx *c) { return c->plan.nnz_blocks; }
-
-double bytes_assemble(const femshell_ctx *c)
-{
-    const Plan &p = c->plan;
-    // (symmetric storage: only the stored blocks are computed and written -- the algorithmic bytes of that layout -- and of a
-    //  diagonal block, symmetric itself, the 12 words of the upper triangle: 192 instead of 288 bytes per node)
-    return 12.0 * p.n_ltri() + 16.0 * p.n_lquad() + 24.0 * (p.n_own + p.n_ghost) + 292.0 * (double)p.stored_blocks -
-           (c->dm.diag_upper ? 96.0 * p.n_own : 0.0) + 4.0 * (p.n_own + 1) + 48.0 * p.n_own +
-           // sections: an index per element and every row of the table that is in use, once
-           (c->have_sections ? 4.0 * (p.n_ltri() + p.n_lquad()) + (double)sizeof(SecConst) * std::min<double>(c->n_sections, p.n_ltri() + p.n_lquad()) : 0.0);
-}
-double bytes_spmv(const femshell_ctx *c)
-{
-    const Plan &p = c->plan;
-    // (symmetric storage: every stored block is streamed once; the 48-byte transposed products written and read
-    // beside them are overhead of the method, not algorithmic traffic)
-    // ... and of a diagonal block the 12 words (192 bytes) that hold its upper triangle
-    return 292.0 * (double)p.stored_blocks - (p.symmetric ? 96.0 * p.n_own : 0.0) + 4.0 * (p.n_own + 1) + 96.0 * p.n_own;
-}
-// (the inverse diagonal blocks are symmetric: 21 of their 36 words are stored and read)
-double bytes_update(const femshell_ctx *c) { return (7.0 * 48.0 + 168.0) * c->plan.n_own; }
-double bytes_direction(const femshell_ctx *c) { return 3.0 * 48.0 * c->plan.n_own; }
-// single-reduction recurrence: z, w, p, s, x, r read, p, s, x, r, z written, Minv read
-double bytes_update_single_reduction(const femshell_ctx *c) { return (11.0 * 48.0 + 168.0) * c->plan.n_own; }
-
-int interpret_status(femshell_ctx *c, int32_t st, const char *what);
-
-int check_status(femshell_ctx *c, const char *what)
-{
-    if (!c->status_mapped) FS_HIP(hipMemcpyAsync(c->status_host, c->status_word, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream));
-    return interpret_status(c, *(volatile int32_t *)c->status_host, what);
-}
+static int64_t real_blocks(const femshell_ctx *c) { return c->plan.nnz_blocks; }
 
 // the device status word of this rank as an error code + message (and the word cleared for the next launch)
-int interpret_status(femshell_ctx *c, int32_t st, const char *what)
+static int interpret_status(femshell_ctx *c, int32_t st, const char *what)
 {
     if (st == 0) return FEMSHELL_OK;
     {
@@ -103,9 +80,32 @@ int interpret_status(femshell_ctx *c, int32_t st, const char *what)
     {
         const int32_t node = c->plan.row_begin + (-st - 1);
         snprintf(buf, sizeof buf, "%s: diagonal block of node %d is not positive definite", what,
-                 (!c->perm.empty() && node >= 0 && node < (int32_t)c->perm.size()) ? c->perm[node] : node);
+                 caller_node(c, node));
     }
     return set_err(FEMSHELL_ERR_BREAKDOWN, buf);
+}
+
+int check_status(femshell_ctx *c, const char *what)
+{
+    if (!c->status_mapped) FS_HIP(hipMemcpyAsync(c->status_host, c->status_word, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    FS_HIP(hipStreamSynchronize(c->stream));
+    return interpret_status(c, *(volatile int32_t *)c->status_host, what);
+}
+
+// The all-reduced pair in c->agree_host, [ranks with a mesh error, ranks with any other error], as the outcome of a rank that has
+// no error of its own: the healthy ranks leave with the same class of error.
+static int agreed_outcome(femshell_ctx *c, const char *what, bool neutral)
+{
+    if (!(c->agree_host[0] + c->agree_host[1] > 0.0)) return FEMSHELL_OK;
+    const int failed = (int)(c->agree_host[0] + c->agree_host[1]);
+    char buf[200];
+    if (neutral) {
+        snprintf(buf, sizeof buf, "%s: failed on %d other rank(s) of the row partition (their own message says why)", what, failed);
+        return set_err(FEMSHELL_ERR_COMM, buf);
+    }
+    snprintf(buf, sizeof buf, "%s: failed on %d other rank(s) of the row partition (%s there)", what, failed,
+             c->agree_host[0] > 0.0 ? "degenerate element" : "non-SPD diagonal block");
+    return set_err(c->agree_host[0] > 0.0 ? FEMSHELL_ERR_MESH : FEMSHELL_ERR_BREAKDOWN, buf);
 }
 
 // Collective agreement on a rank-local outcome (multi-rank contexts): a degenerate element or a non-SPD diagonal
@@ -114,12 +114,11 @@ int interpret_status(femshell_ctx *c, int32_t st, const char *what)
 // assembly and after the block-Jacobi setup); all of them leave with an error when any of them has one.
 // (neutral: the caller is neither the assembly nor the block-Jacobi setup -- the healthy ranks then report "failed on N
 //  other rank(s)" with FEMSHELL_ERR_COMM instead of guessing at a degenerate element or a non-SPD block over there)
-int agree_status(femshell_ctx *c, int local_rc, const char *what, bool neutral = false)
+static int agree_status(femshell_ctx *c, int local_rc, const char *what, bool neutral = false)
 {
     if (!c->comm.active()) return local_rc;
     const std::string local_msg = last_err();
     FS_HIP(c->agree.alloc(2));
-    // [ranks with a mesh error, ranks with any other error]: the healthy ranks leave with the same class of error
     c->agree_host[0] = local_rc == FEMSHELL_ERR_MESH ? 1.0 : 0.0;
     c->agree_host[1] = (local_rc && local_rc != FEMSHELL_ERR_MESH) ? 1.0 : 0.0;
     FS_HIP(hipMemcpyAsync(c->agree.p, c->agree_host, 2 * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -128,26 +127,14 @@ int agree_status(femshell_ctx *c, int local_rc, const char *what, bool neutral =
     FS_HIP(hipMemcpyAsync(c->agree_host, c->agree.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     FS_HIP(hipStreamSynchronize(c->stream));
     if (local_rc) return set_err(local_rc, local_msg);
-    if (neutral && c->agree_host[0] + c->agree_host[1] > 0.0) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "%s: failed on %d other rank(s) of the row partition (their own message says why)", what,
-                 (int)(c->agree_host[0] + c->agree_host[1]));
-        return set_err(FEMSHELL_ERR_COMM, buf);
-    }
-    if (c->agree_host[0] + c->agree_host[1] > 0.0) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "%s: failed on %d other rank(s) of the row partition (%s there)", what,
-                 (int)(c->agree_host[0] + c->agree_host[1]), c->agree_host[0] > 0.0 ? "degenerate element" : "non-SPD diagonal block");
-        return set_err(c->agree_host[0] > 0.0 ? FEMSHELL_ERR_MESH : FEMSHELL_ERR_BREAKDOWN, buf);
-    }
-    return FEMSHELL_OK;
+    return agreed_outcome(c, what, neutral);
 }
 
 // After a kernel that reports through the device status word (assembly, block-Jacobi setup): the local check and the
 // cross-rank agreement in ONE stream synchronisation -- a kernel turns the status word into the two agreement counters,
 // the all-reduce runs on the device, status and counters come back together.  (check_status followed by agree_status is
 // two synchronisations and three copies; on 8 ranks a 0.1 ms assembly step would spend as long agreeing as assembling.)
-int check_and_agree(femshell_ctx *c, const char *what)
+static int check_and_agree(femshell_ctx *c, const char *what)
 {
     if (!c->comm.active()) return check_status(c, what);
     FS_HIP(c->agree.alloc(2));
@@ -158,21 +145,14 @@ int check_and_agree(femshell_ctx *c, const char *what)
     FS_HIP(hipMemcpyAsync(c->agree_host, c->agree.p, 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     FS_HIP(hipStreamSynchronize(c->stream));
     const int local_rc = interpret_status(c, *c->status_host, what);
-    if (local_rc) return local_rc;
-    if (c->agree_host[0] + c->agree_host[1] > 0.0) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "%s: failed on %d other rank(s) of the row partition (%s there)", what,
-                 (int)(c->agree_host[0] + c->agree_host[1]), c->agree_host[0] > 0.0 ? "degenerate element" : "non-SPD diagonal block");
-        return set_err(c->agree_host[0] > 0.0 ? FEMSHELL_ERR_MESH : FEMSHELL_ERR_BREAKDOWN, buf);
-    }
-    return FEMSHELL_OK;
+    return local_rc ? local_rc : agreed_outcome(c, what, false);
 }
 
 // scatter the global per-node arrays into the rank-local numbering and upload
 // the rank's part of the Dirichlet masks (kNodeMasks) and / or of the nodal loads (kNodeLoads) to HBM; kNodeCleared: both
 // are known to be zero (a mesh was just set), no host data moves at all
 enum : int { kNodeMasks = 1, kNodeLoads = 2, kNodeCleared = 4 };
-int upload_node_data(femshell_ctx *c, int what)
+static int upload_node_data(femshell_ctx *c, int what)
 {
     const Plan &p = c->plan;
     hipStream_t st = c->stream;
@@ -209,8 +189,8 @@ int upload_node_data(femshell_ctx *c, int what)
     return FEMSHELL_OK;
 }
 
-// status and timing of an assembly that femshell_assemble_async enqueued: every entry point that reads results, changes
-// inputs or synchronises calls this first
+// status and timing of an assembly that femshell_assemble_async enqueued (nothing where none is pending): every entry point that
+// reads results, changes inputs or synchronises calls this first
 int finish_pending_assembly(femshell_ctx *c)
 {
     if (!c->assembly_pending) return FEMSHELL_OK;
@@ -230,16 +210,14 @@ int finish_pending_assembly(femshell_ctx *c)
 }
 
 // femshell_set_mesh and femshell_set_sections forget the densities (and with them the mass matrix in HBM)
-void forget_density(femshell_ctx *c)
+static void forget_density(femshell_ctx *c)
 {
     c->have_density = c->mass_valid = false;
     c->rho = 0.0;
     c->sec_rho.clear();
 }
 
-int do_rhs(femshell_ctx *c);
-
-int do_assemble(femshell_ctx *c, bool wait = true)
+int do_assemble(femshell_ctx *c, bool wait)
 {
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: no mesh set");
     TraceRange trace("femshell_assemble");
@@ -292,7 +270,7 @@ int do_assemble(femshell_ctx *c, bool wait = true)
 
 // u_bar of the prescribed values and the Dirichlet set in force (femshell_set_prescribed): the entries at fixed dofs, zero
 // elsewhere, on the host and in HBM.  Single-rank contexts only: the owned rows are all rows.
-int resolve_prescribed(femshell_ctx *c)
+static int resolve_prescribed(femshell_ctx *c)
 {
     if (c->ubar_valid) return FEMSHELL_OK;
     const Plan &p = c->plan;
@@ -358,7 +336,201 @@ double wall_s()
     return duration<double>(steady_clock::now().time_since_epoch()).count();
 }
 
-} // namespace
+bool all_finite(const double *x, int64_t n)
+{
+    std::atomic<int> bad{0};
+    parallel_chunks(n, [&](int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; i++)
+            if (!std::isfinite(x[i])) bad.store(1);
+    }, 1 << 18);
+    return bad.load() == 0;
+}
+
+// What a solve needs in HBM before its Krylov loop: K and F assembled (again, with FEMSHELL_REASSEMBLE_EACH_SOLVE), the
+// block-Jacobi inverse.  *asm_s / *setup_s: seconds of the assembly and of the block-Jacobi setup done here (0: none needed).
+static int prepare_system(femshell_ctx *c, double *asm_s, double *setup_s)
+{
+    int rc = FEMSHELL_OK;
+    *asm_s = *setup_s = 0.0;
+    if (!c->matrix_valid || (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)) {
+        rc = do_assemble(c);
+        if (rc) return rc;
+        *asm_s = c->last_assemble_s;
+    } else if (!c->rhs_valid) {
+        rc = do_rhs(c);
+        if (rc) return rc;
+    }
+    if (!c->jacobi_valid) {
+        rc = do_jacobi(c);
+        if (rc) return rc;
+        *setup_s = c->last_setup_s;
+    }
+    return rc;
+}
+
+// The multigrid hierarchy of the K in HBM, built where there is none (first solve, K changed, the all-FP64 rebuild): on one rank,
+// or row-partitioned and collective when the context has a communicator.  *pc_setup_s += its seconds.
+int ensure_amg_hierarchy(femshell_ctx *c, double *pc_setup_s)
+{
+    if (c->amg && c->amg->valid) return FEMSHELL_OK;
+    int rc = FEMSHELL_OK;
+    if (c->comm.active()) {
+        const double t0 = wall_s();
+        // row-partitioned hierarchy (amg_dist.cpp); a failure only one rank sees must reach the others
+        rc = agree_status(c, amg_setup_dist(c), "multigrid setup", true);
+        if (rc) {
+            c->amg.reset();
+            return rc;
+        }
+        *pc_setup_s += wall_s() - t0;
+    } else {
+        rc = amg_setup(c);
+        if (rc) {
+            c->amg.reset();
+            return rc;
+        }
+        *pc_setup_s += c->amg->setup_seconds;
+    }
+    return rc;
+}
+
+// dynamic: the solve of a Newmark step -- the right-hand side is F_eff, built from the F of the loads in force and the
+// committed state by k_newmark_rhs behind the (re)assembly, instead of F itself
+int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic)
+{
+    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: null context");
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: no mesh set");
+    if (max_it < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: max_it < 0");
+    if (const int prc = finish_pending_assembly(c)) return prc;
+    TraceRange trace("femshell_solve");
+    // (the CG loops report progress at every poll of the convergence flag: CommWatch::heartbeat)
+    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_solve (halo exchanges and all-reduces of the solve)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    double asm_s = 0.0, setup_s = 0.0;
+    rc = prepare_system(c, &asm_s, &setup_s);
+    if (rc) return rc;
+    double pc_setup_s = 0.0;
+    const bool use_amg = c->pc.type == FEMSHELL_PC_AMG;
+    hipStream_t st = c->stream;
+    TraceRange trace_cg(use_amg ? "femshell_solve: multigrid-preconditioned CG" : "femshell_solve: block-Jacobi CG");
+    FS_HIP(c->hist.alloc((size_t)std::min<int64_t>(std::max(max_it, 1), 1 << 22))); // history of the first 4M iterations
+    CgVectors v = cg_vectors(c);
+    const DeviceMatrix &m = c->dm;
+    if (dynamic) {
+        femshell_ctx::Dynamics &d = c->dyn;
+        launch_newmark_rhs(m, d.k, c->mass.p, c->F.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.b.p, st);
+        FS_HIP(hipGetLastError());
+        v.b = d.b.p;
+    }
+    const bool single_reduction = !use_amg && use_single_reduction(c);
+    const double *x0 = c->warm_next ? c->x0.p : nullptr; // femshell_set_initial_guess: this solve's, and only this one's
+    c->warm_next = false;
+    double amg_true_rr = -1.0, amg_rec_rr = -1.0;
+    CgScalars hs{};
+    bool fp64_fallback = false;
+    float ms_abandoned = 0.f; // device time of an attempt that ended in the breakdown below: part of solve_seconds
+    for (int attempt = 0;; attempt++) {
+        if (use_amg) {
+            rc = ensure_amg_hierarchy(c, &pc_setup_s);
+            if (rc) return rc;
+        }
+        // a previous solve leaves done = 1 behind; the reduction launch in front of an all-reduce carries no phase and
+        // would skip its work on it (multi-rank re-solves, e.g. every coupling iteration)
+        FS_HIP(hipEventRecord(c->ev0, st)); // (behind the multigrid setup: solve_seconds is the time of the Krylov loop)
+        FS_HIP(c->scal.zero(st));
+        amg_true_rr = amg_rec_rr = -1.0;
+        // (from an initial guess the block-Jacobi method runs its classic recurrence: the single-reduction form has no such start)
+        rc = use_amg ? cg_amg(c, v, rtol, max_it, &amg_true_rr, &amg_rec_rr, x0)
+                     : (single_reduction && !x0) ? cg_single_reduction(c, v, rtol, max_it) : cg_classic(c, v, rtol, max_it, x0);
+        if (rc) return rc;
+        FS_HIP(hipMemcpyAsync(&hs, v.s, sizeof hs, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipStreamSynchronize(st));
+        // A breakdown of the flexible CG (p.Ap <= 0, the same all-reduced number on every rank) under a hierarchy that keeps
+        // single-precision copies: on very thin shells the rounded preconditioner is not positive definite any more.  Once:
+        // the hierarchy again, everything FP64, and the solve from the start.  The context stays that way until a new mesh
+        // or preconditioner is set; femshell_solve_info::pc_fp64_fallback says it happened.
+        // (row-partitioned contexts decide by what every rank knows alike -- the rebuild is collective --, not by what this
+        //  rank's part of the hierarchy happens to hold: a rank without rows on a split level keeps no copies)
+        const bool had_copies = use_amg && (c->comm.active() || amg_uses_single_precision(*c->amg));
+        if (use_amg && hs.done < 0 && attempt == 0 && !c->amg_fp64_only && had_copies) {
+            FS_HIP(hipEventRecord(c->ev1, st));
+            FS_HIP(hipEventSynchronize(c->ev1));
+            FS_HIP(hipEventElapsedTime(&ms_abandoned, c->ev0, c->ev1));
+            c->amg_fp64_only = true;
+            c->amg.reset();
+            fp64_fallback = true;
+            continue;
+        }
+        break;
+    }
+    const bool recurrence_converged = hs.done == 1;
+    const double recurrence_rr = (use_amg && amg_rec_rr >= 0.0) ? amg_rec_rr : hs.rr;
+    double true_rel = -1.0;
+    if (use_amg && amg_true_rr >= 0.0 && hs.bb > 0.0) {
+        true_rel = std::sqrt(amg_true_rr / hs.bb); // computed by the residual replacement of cg_amg
+    } else if (recurrence_converged && rtol > 0.0 && hs.bb > 0.0) {
+        // explicit residual r = b - K x (reported, not enforced): q = K x through the SpMV kernel, whose
+        // input vector carries the ghost entries; the CG state is dead at this point
+        launch_copy_x_to_p(m, v, st);
+        rc = halo_exchange(c, v.p, st);
+        if (rc) return rc;
+        launch_spmv(m, v.p, v.q, nullptr, nullptr, st);
+        launch_cg_init(m, v, true, st);
+        rc = scalar_step(c, v, 2, CG_PHASE_RESTART, rtol);
+        if (rc) return rc;
+        CgScalars hv{};
+        FS_HIP(hipMemcpyAsync(&hv, v.s, sizeof hv, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipStreamSynchronize(st));
+        true_rel = std::sqrt(hv.rr / hv.bb);
+    }
+    FS_HIP(hipEventRecord(c->ev1, st));
+    FS_HIP(hipMemcpyAsync(&hs, v.s, sizeof hs, hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    FS_HIP(hipGetLastError());
+    float ms = 0.f;
+    FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    ms += ms_abandoned;
+    c->last_iters = hs.iters;
+    c->hist_host.assign((size_t)std::min<int64_t>(hs.iters, (int64_t)c->hist.n), 0.0);
+    if (!c->hist_host.empty())
+        FS_HIP(hipMemcpy(c->hist_host.data(), c->hist.p, c->hist_host.size() * sizeof(double), hipMemcpyDeviceToHost));
+    c->have_solution = true;
+    if (info) {
+        info->iterations = hs.iters;
+        info->converged = recurrence_converged ? 1 : 0;
+        info->rel_residual = hs.bb > 0.0 ? std::sqrt(recurrence_rr / hs.bb) : 0.0;
+        info->true_rel_residual = true_rel;
+        info->assemble_seconds = asm_s;
+        info->setup_seconds = setup_s;
+        info->solve_seconds = 1e-3 * ms;
+        // (multigrid: the Krylov product, the update with its start of the smoothing, the two dot products and the new direction
+        //  around the cycle: x, p, r, q read, x, r, q, z written, D^-1; z, r, q; z, p read, p written)
+        info->bytes_per_iteration = use_amg ? bytes_spmv(c) + (8.0 + 3.0 + 3.0) * 48.0 * c->plan.n_own + amg_cycle_bytes(c)
+                                    : single_reduction ? bytes_spmv(c) + bytes_update_single_reduction(c)
+                                                       : bytes_spmv(c) + bytes_update(c) + bytes_direction(c);
+        info->pc_type = c->pc.type;
+        info->amg_levels = use_amg ? (int32_t)c->amg->levels.size() : 0;
+        info->pc_setup_seconds = pc_setup_s;
+        info->operator_complexity = 0.0;
+        info->refine_passes_done = use_amg ? c->refine.passes : 0;
+        info->pc_fp64_fallback = fp64_fallback ? 1 : 0;
+        info->refine_correction_rel = use_amg ? c->refine.correction_rel : -1.0;
+        info->refine_residual_reduction = use_amg ? c->refine.residual_reduction : 0.0;
+        info->error_estimate = (use_amg && c->refine.passes > 0) ? c->refine.correction_rel * c->refine.residual_reduction : -1.0;
+        if (use_amg) {
+            double tot = 0.0;
+            for (auto &L : c->amg->levels) tot += (double)L->nnzb;
+            info->operator_complexity = tot / (double)c->amg->levels[0]->nnzb;
+        }
+    }
+    if (hs.done < 0)
+        return set_err(FEMSHELL_ERR_BREAKDOWN, "femshell_solve: CG breakdown, p.Ap <= 0 (matrix not positive definite)");
+    if (u_out) return femshell_get_solution(c, u_out);
+    return FEMSHELL_OK;
+}
+
+} // namespace femshell
 
 int clear_status_word(femshell_ctx *c, hipStream_t st)
 {
@@ -701,33 +873,6 @@ int femshell_comm_selftest(femshell_ctx *c, double out_us[3])
 int32_t femshell_comm_ranks(femshell_ctx *c) { return c ? comm_count(c->comm) : 0; }
 
 static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t *tri,
-                                 int32_t n_quad, const int32_t *quad);
-
-int femshell_set_mesh(femshell_ctx *c, int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t *tri,
-                      int32_t n_quad, const int32_t *quad)
-{
-    if (!c || !xyz || (n_tri > 0 && !tri) || (n_quad > 0 && !quad))
-        return set_err(FEMSHELL_ERR_INVALID, "femshell_set_mesh: null argument");
-    if (c->cfg.world_size > 1 && !c->comm.active())
-        return set_err(FEMSHELL_ERR_INVALID, "femshell_set_mesh: call femshell_comm_init first on a multi-rank context");
-    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_set_mesh (agreement of the ranks on the outcome)");
-    int rc = select_device(c);
-    if (rc) return rc;
-    if (c->assembly_pending) {
-        // an assembly of the previous mesh whose status nobody asked for: its mark in the device status word (a degenerate
-        // element of the OLD mesh) must not surface as a failure of the first assembly on the new one
-        c->assembly_pending = false;
-        {
-            const int rcc = clear_status_word(c, c->stream);
-            if (rcc) return rcc;
-        }
-    }
-    // a failure that only this rank sees (its slices exceed the LDS staging, one of its nodes has too many neighbours, a
-    // HIP allocation failed) must reach the others: they would wait in the next collective forever
-    return agree_status(c, set_mesh_on_this_rank(c, n_nodes, xyz, n_tri, tri, n_quad, quad), "femshell_set_mesh", true);
-}
-
-static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t *tri,
                                  int32_t n_quad, const int32_t *quad)
 {
     int rc = FEMSHELL_OK;
@@ -740,14 +885,7 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
         if (verbose) fprintf(stderr, "[femshell set_mesh] %-40s %.3f s\n", what, t - t_part);
         t_part = t;
     };
-    {
-        std::atomic<int> bad{0};
-        parallel_chunks(3ll * n_nodes, [&](int64_t b, int64_t e) {
-            for (int64_t i = b; i < e; i++)
-                if (!std::isfinite(xyz[i])) bad.store(1);
-        }, 1 << 18);
-        if (bad.load()) return set_err(FEMSHELL_ERR_MESH, "femshell_set_mesh: non-finite coordinate");
-    }
+    if (!all_finite(xyz, 3ll * n_nodes)) return set_err(FEMSHELL_ERR_MESH, "femshell_set_mesh: non-finite coordinate");
     std::string e;
     c->have_mesh = false;
     c->have_sections = false; // (the element count may change)
@@ -937,23 +1075,44 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     return FEMSHELL_OK;
 }
 
+int femshell_set_mesh(femshell_ctx *c, int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t *tri,
+                      int32_t n_quad, const int32_t *quad)
+{
+    if (!c || !xyz || (n_tri > 0 && !tri) || (n_quad > 0 && !quad))
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_set_mesh: null argument");
+    if (c->cfg.world_size > 1 && !c->comm.active())
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_set_mesh: call femshell_comm_init first on a multi-rank context");
+    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_set_mesh (agreement of the ranks on the outcome)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    if (c->assembly_pending) {
+        // an assembly of the previous mesh whose status nobody asked for: its mark in the device status word (a degenerate
+        // element of the OLD mesh) must not surface as a failure of the first assembly on the new one
+        c->assembly_pending = false;
+        {
+            const int rcc = clear_status_word(c, c->stream);
+            if (rcc) return rcc;
+        }
+    }
+    // a failure that only this rank sees (its slices exceed the LDS staging, one of its nodes has too many neighbours, a
+    // HIP allocation failed) must reach the others: they would wait in the next collective forever
+    return agree_status(c, set_mesh_on_this_rank(c, n_nodes, xyz, n_tri, tri, n_quad, quad), "femshell_set_mesh", true);
+}
+
 int femshell_set_dirichlet(femshell_ctx *c, int32_t n, const int32_t *node_ids, const uint8_t *mask6)
 {
     if (!c || (n > 0 && !mask6)) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: call femshell_set_mesh first");
     if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: not while dynamics is active (femshell_dynamics_end first)");
     const int32_t nn = c->plan.n_nodes;
     if (!node_ids && n != nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: dense form needs n == n_nodes");
     std::vector<uint8_t> m((size_t)nn, 0);
     for (int32_t i = 0; i < n; i++) {
-        const int32_t a = node_ids ? node_ids[i] : i;
-        if (a < 0 || a >= nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: node id out of range");
+        const int32_t a = internal_node(c, node_ids ? node_ids[i] : i);
+        if (a < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: node id out of range");
         if (mask6[i] & ~0x3Fu) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_dirichlet: mask has bits above dof 5");
-        m[c->iperm.empty() ? a : c->iperm[a]] |= mask6[i];
+        m[(size_t)a] |= mask6[i];
     }
     int rc = select_device(c);
     if (rc) return rc;
@@ -971,10 +1130,7 @@ int femshell_set_prescribed(femshell_ctx *c, int32_t n, const int32_t *node_ids,
     if (c->cfg.world_size != 1)
         return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_set_prescribed: single-rank contexts only (a row partition would need the ghost values of the prescribed displacements and a halo exchange in front of the element product)");
     if (n > 0 && !u6) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: call femshell_set_mesh first");
     if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: not while dynamics is active (femshell_dynamics_end first)");
     if (n < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: n < 0");
@@ -989,11 +1145,11 @@ int femshell_set_prescribed(femshell_ctx *c, int32_t n, const int32_t *node_ids,
     if (!node_ids && n != nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: dense form needs n == n_nodes");
     std::vector<double> l((size_t)nn * 6, 0.0);
     for (int32_t i = 0; i < n; i++) {
-        const int32_t a = node_ids ? node_ids[i] : i;
-        if (a < 0 || a >= nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: node id out of range");
+        const int32_t a = internal_node(c, node_ids ? node_ids[i] : i);
+        if (a < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: node id out of range");
         for (int v = 0; v < 6; v++) {
             if (!std::isfinite(u6[6ll * i + v])) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: non-finite value");
-            l[6ull * (size_t)(c->iperm.empty() ? a : c->iperm[a]) + v] = u6[6ll * i + v];
+            l[6ull * (size_t)a + v] = u6[6ll * i + v];
         }
     }
     c->prescribed_global.swap(l);
@@ -1030,10 +1186,7 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
                           const int32_t *quad_section)
 {
     if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: null context");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: call femshell_set_mesh first");
     if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: not while dynamics is active (femshell_dynamics_end first)");
     if (n_sections < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_sections: n_sections < 0");
@@ -1145,10 +1298,7 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
 int femshell_set_loads(femshell_ctx *c, int32_t n, const int32_t *node_ids, const double *f6)
 {
     if (!c || (n > 0 && !f6)) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_loads: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_loads: call femshell_set_mesh first");
     const int32_t nn = c->plan.n_nodes;
     if (!node_ids && n != nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_loads: dense form needs n == n_nodes");
@@ -1166,11 +1316,11 @@ int femshell_set_loads(femshell_ctx *c, int32_t n, const int32_t *node_ids, cons
     } else {
         parallel_chunks((int64_t)l.size(), [&](int64_t b, int64_t e) { std::fill(l.begin() + b, l.begin() + e, 0.0); }, 1 << 18);
         for (int32_t i = 0; i < n; i++) {
-            const int32_t a = node_ids ? node_ids[i] : i;
-            if (a < 0 || a >= nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_loads: node id out of range");
+            const int32_t a = internal_node(c, node_ids ? node_ids[i] : i);
+            if (a < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_loads: node id out of range");
             for (int v = 0; v < 6; v++) {
                 if (!std::isfinite(f6[6ll * i + v])) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_loads: non-finite load");
-                l[6ull * (size_t)(c->iperm.empty() ? a : c->iperm[a]) + v] = f6[6ll * i + v];
+                l[6ull * (size_t)a + v] = f6[6ll * i + v];
             }
         }
     }
@@ -1388,198 +1538,9 @@ int64_t femshell_amg_export(femshell_ctx *c, int32_t level, int32_t which, void 
     }
 }
 
-// What a solve needs in HBM before its Krylov loop: K and F assembled (again, with FEMSHELL_REASSEMBLE_EACH_SOLVE), the
-// block-Jacobi inverse.  *asm_s / *setup_s: seconds of the assembly and of the block-Jacobi setup done here (0: none needed).
-static int prepare_system(femshell_ctx *c, double *asm_s, double *setup_s)
-{
-    int rc = FEMSHELL_OK;
-    *asm_s = *setup_s = 0.0;
-    if (!c->matrix_valid || (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)) {
-        rc = do_assemble(c);
-        if (rc) return rc;
-        *asm_s = c->last_assemble_s;
-    } else if (!c->rhs_valid) {
-        rc = do_rhs(c);
-        if (rc) return rc;
-    }
-    if (!c->jacobi_valid) {
-        rc = do_jacobi(c);
-        if (rc) return rc;
-        *setup_s = c->last_setup_s;
-    }
-    return rc;
-}
-
-// The multigrid hierarchy of the K in HBM, built where there is none (first solve, K changed, the all-FP64 rebuild): on one rank,
-// or row-partitioned and collective when the context has a communicator.  *pc_setup_s += its seconds.
-static int ensure_amg_hierarchy(femshell_ctx *c, double *pc_setup_s)
-{
-    if (c->amg && c->amg->valid) return FEMSHELL_OK;
-    int rc = FEMSHELL_OK;
-    if (c->comm.active()) {
-        const double t0 = wall_s();
-        // row-partitioned hierarchy (amg_dist.cpp); a failure only one rank sees must reach the others
-        rc = agree_status(c, amg_setup_dist(c), "multigrid setup", true);
-        if (rc) {
-            c->amg.reset();
-            return rc;
-        }
-        *pc_setup_s += wall_s() - t0;
-    } else {
-        rc = amg_setup(c);
-        if (rc) {
-            c->amg.reset();
-            return rc;
-        }
-        *pc_setup_s += c->amg->setup_seconds;
-    }
-    return rc;
-}
-
-// dynamic: the solve of a Newmark step -- the right-hand side is F_eff, built from the F of the loads in force and the
-// committed state by k_newmark_rhs behind the (re)assembly, instead of F itself
-static int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic);
-
 int femshell_solve(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info)
 {
     return solve_system(c, rtol, max_it, u_out, info, false);
-}
-
-static int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic)
-{
-    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: null context");
-    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: no mesh set");
-    if (max_it < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_solve: max_it < 0");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
-    TraceRange trace("femshell_solve");
-    // (the CG loops report progress at every poll of the convergence flag: CommWatch::heartbeat)
-    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_solve (halo exchanges and all-reduces of the solve)");
-    int rc = select_device(c);
-    if (rc) return rc;
-    double asm_s = 0.0, setup_s = 0.0;
-    rc = prepare_system(c, &asm_s, &setup_s);
-    if (rc) return rc;
-    double pc_setup_s = 0.0;
-    const bool use_amg = c->pc.type == FEMSHELL_PC_AMG;
-    hipStream_t st = c->stream;
-    TraceRange trace_cg(use_amg ? "femshell_solve: multigrid-preconditioned CG" : "femshell_solve: block-Jacobi CG");
-    FS_HIP(c->hist.alloc((size_t)std::min<int64_t>(std::max(max_it, 1), 1 << 22))); // history of the first 4M iterations
-    CgVectors v = cg_vectors(c);
-    const DeviceMatrix &m = c->dm;
-    if (dynamic) {
-        femshell_ctx::Dynamics &d = c->dyn;
-        launch_newmark_rhs(m, d.k, c->mass.p, c->F.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.b.p, st);
-        FS_HIP(hipGetLastError());
-        v.b = d.b.p;
-    }
-    const bool single_reduction = !use_amg && use_single_reduction(c);
-    const double *x0 = c->warm_next ? c->x0.p : nullptr; // femshell_set_initial_guess: this solve's, and only this one's
-    c->warm_next = false;
-    double amg_true_rr = -1.0, amg_rec_rr = -1.0;
-    CgScalars hs{};
-    bool fp64_fallback = false;
-    float ms_abandoned = 0.f; // device time of an attempt that ended in the breakdown below: part of solve_seconds
-    for (int attempt = 0;; attempt++) {
-        if (use_amg) {
-            rc = ensure_amg_hierarchy(c, &pc_setup_s);
-            if (rc) return rc;
-        }
-        // a previous solve leaves done = 1 behind; the reduction launch in front of an all-reduce carries no phase and
-        // would skip its work on it (multi-rank re-solves, e.g. every coupling iteration)
-        FS_HIP(hipEventRecord(c->ev0, st)); // (behind the multigrid setup: solve_seconds is the time of the Krylov loop)
-        FS_HIP(c->scal.zero(st));
-        amg_true_rr = amg_rec_rr = -1.0;
-        // (from an initial guess the block-Jacobi method runs its classic recurrence: the single-reduction form has no such start)
-        rc = use_amg ? cg_amg(c, v, rtol, max_it, &amg_true_rr, &amg_rec_rr, x0)
-                     : (single_reduction && !x0) ? cg_single_reduction(c, v, rtol, max_it) : cg_classic(c, v, rtol, max_it, x0);
-        if (rc) return rc;
-        FS_HIP(hipMemcpyAsync(&hs, v.s, sizeof hs, hipMemcpyDeviceToHost, st));
-        FS_HIP(hipStreamSynchronize(st));
-        // A breakdown of the flexible CG (p.Ap <= 0, the same all-reduced number on every rank) under a hierarchy that keeps
-        // single-precision copies: on very thin shells the rounded preconditioner is not positive definite any more.  Once:
-        // the hierarchy again, everything FP64, and the solve from the start.  The context stays that way until a new mesh
-        // or preconditioner is set; femshell_solve_info::pc_fp64_fallback says it happened.
-        // (row-partitioned contexts decide by what every rank knows alike -- the rebuild is collective --, not by what this
-        //  rank's part of the hierarchy happens to hold: a rank without rows on a split level keeps no copies)
-        const bool had_copies = use_amg && (c->comm.active() || amg_uses_single_precision(*c->amg));
-        if (use_amg && hs.done < 0 && attempt == 0 && !c->amg_fp64_only && had_copies) {
-            FS_HIP(hipEventRecord(c->ev1, st));
-            FS_HIP(hipEventSynchronize(c->ev1));
-            FS_HIP(hipEventElapsedTime(&ms_abandoned, c->ev0, c->ev1));
-            c->amg_fp64_only = true;
-            c->amg.reset();
-            fp64_fallback = true;
-            continue;
-        }
-        break;
-    }
-    const bool recurrence_converged = hs.done == 1;
-    const double recurrence_rr = (use_amg && amg_rec_rr >= 0.0) ? amg_rec_rr : hs.rr;
-    double true_rel = -1.0;
-    if (use_amg && amg_true_rr >= 0.0 && hs.bb > 0.0) {
-        true_rel = std::sqrt(amg_true_rr / hs.bb); // computed by the residual replacement of cg_amg
-    } else if (recurrence_converged && rtol > 0.0 && hs.bb > 0.0) {
-        // explicit residual r = b - K x (reported, not enforced): q = K x through the SpMV kernel, whose
-        // input vector carries the ghost entries; the CG state is dead at this point
-        launch_copy_x_to_p(m, v, st);
-        rc = halo_exchange(c, v.p, st);
-        if (rc) return rc;
-        launch_spmv(m, v.p, v.q, nullptr, nullptr, st);
-        launch_cg_init(m, v, true, st);
-        rc = scalar_step(c, v, 2, CG_PHASE_RESTART, rtol);
-        if (rc) return rc;
-        CgScalars hv{};
-        FS_HIP(hipMemcpyAsync(&hv, v.s, sizeof hv, hipMemcpyDeviceToHost, st));
-        FS_HIP(hipStreamSynchronize(st));
-        true_rel = std::sqrt(hv.rr / hv.bb);
-    }
-    FS_HIP(hipEventRecord(c->ev1, st));
-    FS_HIP(hipMemcpyAsync(&hs, v.s, sizeof hs, hipMemcpyDeviceToHost, st));
-    FS_HIP(hipStreamSynchronize(st));
-    FS_HIP(hipGetLastError());
-    float ms = 0.f;
-    FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    ms += ms_abandoned;
-    c->last_iters = hs.iters;
-    c->hist_host.assign((size_t)std::min<int64_t>(hs.iters, (int64_t)c->hist.n), 0.0);
-    if (!c->hist_host.empty())
-        FS_HIP(hipMemcpy(c->hist_host.data(), c->hist.p, c->hist_host.size() * sizeof(double), hipMemcpyDeviceToHost));
-    c->have_solution = true;
-    if (info) {
-        info->iterations = hs.iters;
-        info->converged = recurrence_converged ? 1 : 0;
-        info->rel_residual = hs.bb > 0.0 ? std::sqrt(recurrence_rr / hs.bb) : 0.0;
-        info->true_rel_residual = true_rel;
-        info->assemble_seconds = asm_s;
-        info->setup_seconds = setup_s;
-        info->solve_seconds = 1e-3 * ms;
-        // (multigrid: the Krylov product, the update with its start of the smoothing, the two dot products and the new direction
-        //  around the cycle: x, p, r, q read, x, r, q, z written, D^-1; z, r, q; z, p read, p written)
-        info->bytes_per_iteration = use_amg ? bytes_spmv(c) + (8.0 + 3.0 + 3.0) * 48.0 * c->plan.n_own + amg_cycle_bytes(c)
-                                    : single_reduction ? bytes_spmv(c) + bytes_update_single_reduction(c)
-                                                       : bytes_spmv(c) + bytes_update(c) + bytes_direction(c);
-        info->pc_type = c->pc.type;
-        info->amg_levels = use_amg ? (int32_t)c->amg->levels.size() : 0;
-        info->pc_setup_seconds = pc_setup_s;
-        info->operator_complexity = 0.0;
-        info->refine_passes_done = use_amg ? c->refine.passes : 0;
-        info->pc_fp64_fallback = fp64_fallback ? 1 : 0;
-        info->refine_correction_rel = use_amg ? c->refine.correction_rel : -1.0;
-        info->refine_residual_reduction = use_amg ? c->refine.residual_reduction : 0.0;
-        info->error_estimate = (use_amg && c->refine.passes > 0) ? c->refine.correction_rel * c->refine.residual_reduction : -1.0;
-        if (use_amg) {
-            double tot = 0.0;
-            for (auto &L : c->amg->levels) tot += (double)L->nnzb;
-            info->operator_complexity = tot / (double)c->amg->levels[0]->nnzb;
-        }
-    }
-    if (hs.done < 0)
-        return set_err(FEMSHELL_ERR_BREAKDOWN, "femshell_solve: CG breakdown, p.Ap <= 0 (matrix not positive definite)");
-    if (u_out) return femshell_get_solution(c, u_out);
-    return FEMSHELL_OK;
 }
 
 int femshell_set_initial_guess(femshell_ctx *c, const double *u0)
@@ -1595,10 +1556,10 @@ int femshell_set_initial_guess(femshell_ctx *c, const double *u0)
         FS_HIP(c->x0.alloc(n6));
         FS_HIP(hipMemcpyAsync(c->x0.p, c->x.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     } else {
-        // the rank's own rows, internal numbering
-        std::vector<double> h(n6, 0.0);
+        // the rank's own rows, internal numbering: checked and masked on the way
+        std::vector<double> h((size_t)p.n_own * 6);
         for (int32_t i = 0; i < p.n_own; i++) {
-            const int32_t row = p.row_begin + i, node = c->perm.empty() ? row : c->perm[(size_t)row];
+            const int32_t row = p.row_begin + i, node = caller_node(c, row);
             for (int v = 0; v < 6; v++) {
                 const double val = u0[6ull * (size_t)node + v];
                 if (!std::isfinite(val)) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_initial_guess: non-finite entry");
@@ -1607,15 +1568,13 @@ int femshell_set_initial_guess(femshell_ctx *c, const double *u0)
             }
         }
         FS_HIP(c->x0.alloc(n6));
-        FS_HIP(hipMemcpyAsync(c->x0.p, h.data(), n6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        rc = upload_node_block(c, NodeOrder::internal, 1, h.data(), c->x0.p, n6, nullptr);
+        if (rc) return rc;
         FS_HIP(hipStreamSynchronize(c->stream)); // (h goes out of scope)
     }
     c->warm_next = true;
     return FEMSHELL_OK;
 }
-
-// a vector of the owned rows in HBM (6 per node, internal numbering) as n_nodes x 6 in the caller's numbering, on every rank
-static int gather_node_vector(femshell_ctx *c, const double *owned, double *u_out);
 
 int femshell_get_solution(femshell_ctx *c, double *u_out)
 {
@@ -1630,43 +1589,10 @@ int femshell_get_solution(femshell_ctx *c, double *u_out)
     if (rc) return rc;
     for (int32_t a = 0; a < c->plan.n_nodes && c->ubar_nonzero; a++) {
         const uint32_t fixed = c->dmask_global[(size_t)a];
-        const int32_t node = c->perm.empty() ? a : c->perm[(size_t)a];
+        const int32_t node = caller_node(c, a);
         for (int v = 0; v < 6 && fixed; v++)
             if ((fixed >> v) & 1u) u_out[6ull * (size_t)node + v] = c->ubar_host[6ull * (size_t)a + v];
     }
-    return FEMSHELL_OK;
-}
-
-static int gather_node_vector(femshell_ctx *c, const double *owned, double *u_out)
-{
-    const Plan &p = c->plan;
-    if (!c->comm.active()) {
-        if (c->perm.empty()) {
-            FS_HIP(hipMemcpyAsync(u_out, owned, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            FS_HIP(hipStreamSynchronize(c->stream));
-            return FEMSHELL_OK;
-        }
-        std::vector<double> h((size_t)p.n_own * 6); // internal numbering -> the caller's
-        FS_HIP(hipMemcpyAsync(h.data(), owned, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        FS_HIP(hipStreamSynchronize(c->stream));
-        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(u_out + 6ull * c->perm[i], &h[6ull * i], 6 * sizeof(double));
-        return FEMSHELL_OK;
-    }
-    FS_HIP(c->ufull.alloc((size_t)p.n_nodes * 6));
-    std::string e;
-    if (!comm_gather_rows(c->comm, owned, c->ufull.p, c->all_begin, c->all_end, c->stream, &e))
-        return set_err(FEMSHELL_ERR_COMM, e);
-    if (c->perm.empty()) {
-        FS_HIP(hipMemcpyAsync(u_out, c->ufull.p, (size_t)p.n_nodes * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        FS_HIP(hipStreamSynchronize(c->stream));
-        return FEMSHELL_OK;
-    }
-    std::vector<double> h((size_t)p.n_nodes * 6); // internal numbering -> the caller's
-    FS_HIP(hipMemcpyAsync(h.data(), c->ufull.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream));
-    parallel_chunks(p.n_nodes, [&](int64_t b, int64_t e) {
-        for (int64_t i = b; i < e; i++) std::memcpy(u_out + 6ull * c->perm[(size_t)i], &h[6ull * (size_t)i], 6 * sizeof(double));
-    }, 1 << 16);
     return FEMSHELL_OK;
 }
 
@@ -1692,10 +1618,7 @@ int femshell_element_matrices(femshell_ctx *c, int32_t first, int32_t count, dou
         return set_err(FEMSHELL_ERR_INVALID, "femshell_element_matrices: range mixes triangles and quads");
     int rc = select_device(c);
     if (rc) return rc;
-    if (c->assembly_pending) { // (its status word is the one this call checks below)
-        rc = finish_pending_assembly(c);
-        if (rc) return rc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc; // (its status word is the one this call checks below)
     DevBuf<double> out;
     const size_t per = quads ? 576 : 324;
     FS_HIP(out.alloc((size_t)count * per));
@@ -1712,10 +1635,7 @@ int64_t femshell_nnz_blocks(femshell_ctx *c) { return (c && c->have_mesh) ? real
 int femshell_export_bsr(femshell_ctx *c, int32_t *rowptr, int32_t *colidx, double *vals, double *F)
 {
     if (!c || !rowptr || !colidx || !vals) return set_err(FEMSHELL_ERR_INVALID, "femshell_export_bsr: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_export_bsr: call femshell_assemble first");
     int rc = select_device(c);
     if (rc) return rc;
@@ -1736,41 +1656,27 @@ int femshell_export_bsr(femshell_ctx *c, int32_t *rowptr, int32_t *colidx, doubl
     }
     rc = download_matrix(c, &A);
     if (rc) return rc;
-    if (c->cfg.world_size > 1) {
-        // a renumbered row partition: the rank's rows in the order of femshell_owned_nodes (the stretch of the internal
-        // numbering it owns), columns ascending in the caller's ids; F already is in that order
+    // a renumbered row partition: the rank's rows in the order of femshell_owned_nodes (the stretch of the internal numbering it
+    // owns); F already is in that order.  One rank: rows in the caller's order.  Columns ascending in the caller's ids in both.
+    const bool partitioned = c->cfg.world_size > 1;
+    if (partitioned) {
         FS_HIP(hipStreamSynchronize(c->stream));
         for (int32_t a = 0; a <= p.n_own; a++) rowptr[a] = (int32_t)A.ptr[a];
-        parallel_chunks(p.n_own, [&](int64_t a0, int64_t a1) {
-            std::vector<std::pair<int32_t, int64_t>> order;
-            for (int64_t a = a0; a < a1; a++) {
-                order.clear();
-                for (int64_t q = A.ptr[a]; q < A.ptr[a + 1]; q++) order.push_back({c->perm[A.col[(size_t)q]], q});
-                std::sort(order.begin(), order.end());
-                int64_t w = A.ptr[a];
-                for (auto &o : order) {
-                    colidx[w] = o.first;
-                    std::memcpy(vals + 36 * w, &A.val[(size_t)o.second * 36], 36 * sizeof(double));
-                    w++;
-                }
-            }
-        });
-        return FEMSHELL_OK;
-    }
-    // internal numbering -> the caller's: rows in the caller's order, columns ascending in the caller's ids
-    if (F) {
-        std::vector<double> Fi(F, F + (size_t)p.n_own * 6);
-        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(F + 6ull * c->perm[i], &Fi[6ull * i], 6 * sizeof(double));
-    }
-    rowptr[0] = 0;
-    for (int32_t u = 0; u < p.n_own; u++) {
-        const int32_t i = c->iperm[u];
-        rowptr[u + 1] = rowptr[u] + (int32_t)(A.ptr[i + 1] - A.ptr[i]);
+    } else {
+        if (F) {
+            std::vector<double> Fi(F, F + (size_t)p.n_own * 6);
+            for (int32_t i = 0; i < p.n_own; i++) std::memcpy(F + 6ull * c->perm[i], &Fi[6ull * i], 6 * sizeof(double));
+        }
+        rowptr[0] = 0;
+        for (int32_t u = 0; u < p.n_own; u++) {
+            const int32_t i = c->iperm[u];
+            rowptr[u + 1] = rowptr[u] + (int32_t)(A.ptr[i + 1] - A.ptr[i]);
+        }
     }
     parallel_chunks(p.n_own, [&](int64_t u0, int64_t u1) {
         std::vector<std::pair<int32_t, int64_t>> order;
         for (int64_t u = u0; u < u1; u++) {
-            const int32_t i = c->iperm[(size_t)u];
+            const int64_t i = partitioned ? u : c->iperm[(size_t)u];
             order.clear();
             for (int64_t q = A.ptr[i]; q < A.ptr[i + 1]; q++) order.push_back({c->perm[A.col[(size_t)q]], q});
             std::sort(order.begin(), order.end());
@@ -1788,66 +1694,36 @@ int femshell_export_bsr(femshell_ctx *c, int32_t *rowptr, int32_t *colidx, doubl
 int femshell_spmv(femshell_ctx *c, const double *x, double *y)
 {
     if (!c || !x || !y) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmv: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmv: call femshell_assemble first");
     if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_spmv: single-rank contexts only");
     int rc = select_device(c);
     if (rc) return rc;
-    const Plan &p = c->plan;
-    DevBuf<double> dx, dy;
-    FS_HIP(dx.alloc((size_t)p.n_local_nodes() * 6));
-    FS_HIP(dy.alloc((size_t)p.n_pad * 6));
-    FS_HIP(dx.zero(c->stream));
-    std::vector<double> xi, yi; // internal numbering when the library renumbered the nodes
-    if (!c->perm.empty()) {
-        xi.resize((size_t)p.n_own * 6);
-        yi.resize((size_t)p.n_own * 6);
-        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(&xi[6ull * i], x + 6ull * c->perm[i], 6 * sizeof(double));
-    }
-    FS_HIP(hipMemcpyAsync(dx.p, xi.empty() ? x : xi.data(), (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    launch_spmv(c->dm, dx.p, dy.p, nullptr, nullptr, c->stream);
+    ProductBuffers b;
+    rc = b.upload(c, NodeOrder::caller, x);
+    if (rc) return rc;
+    launch_spmv(c->dm, b.x.p, b.y.p, nullptr, nullptr, c->stream);
     FS_HIP(hipGetLastError());
-    FS_HIP(hipMemcpyAsync(yi.empty() ? y : yi.data(), dy.p, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream));
-    for (int32_t i = 0; i < p.n_own && !yi.empty(); i++) std::memcpy(y + 6ull * c->perm[i], &yi[6ull * i], 6 * sizeof(double));
-    return FEMSHELL_OK;
+    return download_node_block(c, NodeOrder::caller, 1, b.y.p, 0, y);
 }
-
-static int upload_owned_rows(femshell_ctx *c, const double *full, double *dst);
-static bool all_finite(const double *x, int64_t n);
-static int gather_node_vector(femshell_ctx *c, const double *owned, double *u_out);
 
 int femshell_element_product(femshell_ctx *c, const double *x, double *y)
 {
     if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_element_product: null context");
     if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_element_product: single-rank contexts only");
     if (!x || !y) return set_err(FEMSHELL_ERR_INVALID, "femshell_element_product: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_element_product: no mesh set");
     int rc = select_device(c);
     if (rc) return rc;
-    const Plan &p = c->plan;
-    DevBuf<double> dx, dy;
-    FS_HIP(dx.alloc((size_t)p.n_local_nodes() * 6));
-    FS_HIP(dy.alloc((size_t)p.n_pad * 6));
-    FS_HIP(dx.zero(c->stream));
-    std::vector<double> xi; // internal numbering when the library renumbered the nodes
-    if (!c->perm.empty()) {
-        xi.resize((size_t)p.n_own * 6);
-        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(&xi[6ull * i], x + 6ull * c->perm[i], 6 * sizeof(double));
-    }
-    FS_HIP(hipMemcpyAsync(dx.p, xi.empty() ? x : xi.data(), (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    launch_element_product(c->dm, c->mc, c->sections_or_null(), dx.p, nullptr, nullptr, dy.p, false, c->stream);
-    FS_HIP(hipGetLastError());
-    rc = check_status(c, "femshell_element_product"); // (synchronises: xi may go)
+    ProductBuffers b;
+    rc = b.upload(c, NodeOrder::caller, x);
     if (rc) return rc;
-    return gather_node_vector(c, dy.p, y);
+    launch_element_product(c->dm, c->mc, c->sections_or_null(), b.x.p, nullptr, nullptr, b.y.p, false, c->stream);
+    FS_HIP(hipGetLastError());
+    rc = check_status(c, "femshell_element_product");
+    if (rc) return rc;
+    return gather_node_vector(c, b.y.p, y);
 }
 
 int femshell_reactions(femshell_ctx *c, const double *u, double *r6_out)
@@ -1856,105 +1732,34 @@ int femshell_reactions(femshell_ctx *c, const double *u, double *r6_out)
     if (c->cfg.world_size != 1)
         return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_reactions: single-rank contexts only (a row partition would need a halo exchange in front of the element product)");
     if (!r6_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: no mesh set");
     if (!u && !c->have_solution) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: no solve has run (pass u)");
     const Plan &p = c->plan;
     if (u && !all_finite(u, 6ll * p.n_nodes)) return set_err(FEMSHELL_ERR_INVALID, "femshell_reactions: non-finite entry in u");
     int rc = select_device(c);
     if (rc) return rc;
-    DevBuf<double> dx, dy;
-    FS_HIP(dy.alloc((size_t)p.n_pad * 6));
-    const double *x = c->x.p, *xp = nullptr;
-    if (u) {
-        FS_HIP(dx.alloc((size_t)p.n_local_nodes() * 6));
-        FS_HIP(dx.zero(c->stream));
-        rc = upload_owned_rows(c, u, dx.p);
-        if (rc) return rc;
-        x = dx.p;
-    } else if (c->have_prescribed) { // the solution in HBM is the homogeneous part: the kernel adds u_bar entry by entry
+    ProductBuffers b;
+    rc = b.upload(c, NodeOrder::caller, u);
+    if (rc) return rc;
+    const double *x = u ? b.x.p : c->x.p, *xp = nullptr;
+    if (!u && c->have_prescribed) { // the solution in HBM is the homogeneous part: the kernel adds u_bar entry by entry
         rc = resolve_prescribed(c);
         if (rc) return rc;
         if (c->ubar_nonzero) xp = c->ubar.p;
     }
     // r = K_unc u - loads, the loads as set (not masked)
-    launch_element_product(c->dm, c->mc, c->sections_or_null(), x, xp, c->loads.p, dy.p, false, c->stream);
+    launch_element_product(c->dm, c->mc, c->sections_or_null(), x, xp, c->loads.p, b.y.p, false, c->stream);
     FS_HIP(hipGetLastError());
     rc = check_status(c, "femshell_reactions");
     if (rc) return rc;
-    return gather_node_vector(c, dy.p, r6_out);
-}
-
-// n_cols columns of n_nodes x 6 in the caller's numbering -> a block in HBM (column j at dst + j * ld; padding and ghost space zero)
-static int upload_block(femshell_ctx *c, int32_t n_cols, const double *X, femshell::DevBuf<double> *dst)
-{
-    const Plan &p = c->plan;
-    const size_t ld = (size_t)p.n_local_nodes() * 6;
-    FS_HIP(dst->alloc((size_t)n_cols * ld));
-    FS_HIP(dst->zero(c->stream));
-    std::vector<double> xi; // internal numbering when the library renumbered the nodes
-    for (int32_t j = 0; j < n_cols; j++) {
-        const double *xj = X + (size_t)j * p.n_nodes * 6;
-        if (!c->perm.empty()) {
-            xi.resize((size_t)p.n_own * 6);
-            for (int32_t i = 0; i < p.n_own; i++) std::memcpy(&xi[6ull * i], xj + 6ull * c->perm[i], 6 * sizeof(double));
-            xj = xi.data();
-        }
-        FS_HIP(hipMemcpyAsync(dst->p + (size_t)j * ld, xj, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        FS_HIP(hipStreamSynchronize(c->stream)); // (xi is filled again)
-    }
-    return FEMSHELL_OK;
-}
-// ... and back: the owned rows of n_cols columns of a block in HBM as n_nodes x 6 each, the caller's numbering
-static int download_block(femshell_ctx *c, int32_t n_cols, const double *src, double *Y)
-{
-    const Plan &p = c->plan;
-    const size_t ld = (size_t)p.n_local_nodes() * 6;
-    std::vector<double> yi;
-    for (int32_t j = 0; j < n_cols; j++) {
-        double *yj = Y + (size_t)j * p.n_nodes * 6;
-        if (!c->perm.empty()) yi.resize((size_t)p.n_own * 6);
-        FS_HIP(hipMemcpyAsync(yi.empty() ? yj : yi.data(), src + (size_t)j * ld, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        FS_HIP(hipStreamSynchronize(c->stream));
-        for (int32_t i = 0; i < p.n_own && !yi.empty(); i++) std::memcpy(yj + 6ull * c->perm[i], &yi[6ull * i], 6 * sizeof(double));
-    }
-    return FEMSHELL_OK;
-}
-
-int femshell_spmm(femshell_ctx *c, int32_t n_cols, const double *X, double *Y)
-{
-    if (!c || !X || !Y) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: null argument");
-    if (n_cols < 1 || n_cols > kModalMaxCols) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: n_cols must be in 1 .. 96");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
-    if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: call femshell_assemble first");
-    if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_spmm: single-rank contexts only");
-    int rc = select_device(c);
-    if (rc) return rc;
-    const Plan &p = c->plan;
-    const int64_t ld = (int64_t)p.n_local_nodes() * 6;
-    DevBuf<double> dx, dy, tb;
-    rc = upload_block(c, n_cols, X, &dx);
-    if (rc) return rc;
-    FS_HIP(dy.alloc((size_t)n_cols * (size_t)ld));
-    if (c->dm.symmetric) FS_HIP(tb.alloc((size_t)kSpmmMaxCols * (size_t)p.total_slots() * 6));
-    block_product(c->dm, dx.p, dy.p, ld, n_cols, tb.p, p.total_slots() * 6, c->stream, nullptr);
-    FS_HIP(hipGetLastError());
-    return download_block(c, n_cols, dy.p, Y);
+    return gather_node_vector(c, b.y.p, r6_out);
 }
 
 int femshell_residual(femshell_ctx *c, const double *x, double *r)
 {
     if (!c || !x || !r) return set_err(FEMSHELL_ERR_INVALID, "femshell_residual: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_residual: call femshell_assemble first");
     if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_residual: single-rank contexts only");
     int rc = select_device(c);
@@ -1963,24 +1768,12 @@ int femshell_residual(femshell_ctx *c, const double *x, double *r)
         rc = do_rhs(c);
         if (rc) return rc;
     }
-    const Plan &p = c->plan;
-    DevBuf<double> dx, dr;
-    FS_HIP(dx.alloc((size_t)p.n_local_nodes() * 6));
-    FS_HIP(dr.alloc((size_t)p.n_pad * 6));
-    FS_HIP(dx.zero(c->stream));
-    std::vector<double> xi, ri;
-    if (!c->perm.empty()) {
-        xi.resize((size_t)p.n_own * 6);
-        ri.resize((size_t)p.n_own * 6);
-        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(&xi[6ull * i], x + 6ull * c->perm[i], 6 * sizeof(double));
-    }
-    FS_HIP(hipMemcpyAsync(dx.p, xi.empty() ? x : xi.data(), (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    launch_residual_dd(c->dm, dx.p, c->F.p, dr.p, c->stream);
+    ProductBuffers b;
+    rc = b.upload(c, NodeOrder::caller, x);
+    if (rc) return rc;
+    launch_residual_dd(c->dm, b.x.p, c->F.p, b.y.p, c->stream);
     FS_HIP(hipGetLastError());
-    FS_HIP(hipMemcpyAsync(ri.empty() ? r : ri.data(), dr.p, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream));
-    for (int32_t i = 0; i < p.n_own && !ri.empty(); i++) std::memcpy(r + 6ull * c->perm[i], &ri[6ull * i], 6 * sizeof(double));
-    return FEMSHELL_OK;
+    return download_node_block(c, NodeOrder::caller, 1, b.y.p, 0, r);
 }
 
 int femshell_pc_apply(femshell_ctx *c, const double *r, double *z)
@@ -1989,10 +1782,7 @@ int femshell_pc_apply(femshell_ctx *c, const double *r, double *z)
     if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_pc_apply: no mesh set");
     if (c->pc.type != FEMSHELL_PC_AMG)
         return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_pc_apply: multigrid contexts only (block-Jacobi CG is followed iterate by iterate)");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
+    if (const int prc = finish_pending_assembly(c)) return prc;
     TraceRange trace("femshell_pc_apply");
     CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_pc_apply (halo exchanges and all-reduces of one cycle)");
     int rc = select_device(c);
@@ -2001,452 +1791,14 @@ int femshell_pc_apply(femshell_ctx *c, const double *r, double *z)
     rc = prepare_system(c, &asm_s, &setup_s);
     if (!rc) rc = ensure_amg_hierarchy(c, &pc_setup_s);
     if (rc) return rc;
-    const Plan &p = c->plan;
-    // the owned rows in the internal numbering; padding (and the ghost space a halo product might read) zero
-    const bool mapped = !c->perm.empty() && !c->comm.active();
-    std::vector<double> ri, zi((size_t)p.n_own * 6);
-    if (mapped) {
-        ri.resize((size_t)p.n_own * 6);
-        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(&ri[6ull * i], r + 6ull * c->perm[i], 6 * sizeof(double));
-    }
-    DevBuf<double> dr, dz;
-    FS_HIP(dr.alloc((size_t)std::max(p.n_local_nodes(), p.n_pad) * 6));
-    FS_HIP(dz.alloc((size_t)p.n_pad * 6));
-    FS_HIP(dr.zero(c->stream));
-    FS_HIP(dz.zero(c->stream));
-    FS_HIP(hipMemcpyAsync(dr.p, mapped ? ri.data() : r, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    rc = amg_apply(c, dr.p, dz.p, nullptr, /*pre_started=*/false);
+    // one rank: r and z in the caller's numbering; a row partition: the rank's owned rows as they lie in HBM, in and out
+    const NodeOrder order = c->comm.active() ? NodeOrder::internal : NodeOrder::caller;
+    ProductBuffers b;
+    rc = b.upload(c, order, r);
     if (rc) return rc;
-    FS_HIP(hipMemcpyAsync(mapped ? zi.data() : z, dz.p, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream));
-    if (mapped)
-        for (int32_t i = 0; i < p.n_own; i++) std::memcpy(z + 6ull * c->perm[i], &zi[6ull * i], 6 * sizeof(double));
-    return FEMSHELL_OK;
-}
-
-// ---- structural dynamics ------------------------------------------------------------------------------------------------
-
-// the diagonal of the lumped mass matrix of the owned rows in HBM (c->mass), computed where it is not there yet
-static int ensure_mass(femshell_ctx *c)
-{
-    if (c->mass_valid) return FEMSHELL_OK;
-    const Plan &p = c->plan;
-    hipStream_t st = c->stream;
-    FS_HIP(c->mass.alloc((size_t)p.n_pad * 6));
-    const double2 *sec = nullptr;
-    if (c->have_sections) {
-        std::vector<double2> table((size_t)c->n_sections);
-        for (int32_t s = 0; s < c->n_sections; s++) {
-            const double rho = c->sec_rho.empty() ? c->rho : c->sec_rho[(size_t)s], t = c->sec_thickness[(size_t)s];
-            table[(size_t)s] = make_double2(rho * t, rho * t * t * t / 12.0);
-        }
-        FS_HIP(c->sec_mass.upload(table, st));
-        FS_HIP(hipStreamSynchronize(st)); // the host table goes out of scope
-        sec = c->sec_mass.p;
-    }
-    const double t = c->cfg.thickness;
-    launch_lumped_mass(c->dm, make_double2(c->rho * t, c->rho * t * t * t / 12.0), sec, c->ds.slice_elem_section, c->mass.p, st);
-    FS_HIP(hipGetLastError());
-    c->mass_valid = true;
-    return FEMSHELL_OK;
-}
-
-// the rank's own rows of a whole vector in the caller's numbering (n_nodes x 6) into dst (n_pad x 6, padding zero)
-static int upload_owned_rows(femshell_ctx *c, const double *full, double *dst)
-{
-    const Plan &p = c->plan;
-    std::vector<double> h((size_t)p.n_pad * 6, 0.0);
-    for (int32_t i = 0; i < p.n_own; i++) {
-        const int32_t row = p.row_begin + i, node = c->perm.empty() ? row : c->perm[(size_t)row];
-        std::memcpy(&h[6ull * (size_t)i], full + 6ull * (size_t)node, 6 * sizeof(double));
-    }
-    FS_HIP(hipMemcpyAsync(dst, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream)); // (h goes out of scope)
-    return FEMSHELL_OK;
-}
-
-static bool all_finite(const double *x, int64_t n)
-{
-    std::atomic<int> bad{0};
-    parallel_chunks(n, [&](int64_t b, int64_t e) {
-        for (int64_t i = b; i < e; i++)
-            if (!std::isfinite(x[i])) bad.store(1);
-    }, 1 << 18);
-    return bad.load() == 0;
-}
-
-int femshell_set_density(femshell_ctx *c, double rho, int32_t n_sections, const double *section_rho)
-{
-    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: null context");
-    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: call femshell_set_mesh first");
-    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: not while dynamics is active (femshell_dynamics_end first)");
-    if (n_sections < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: n_sections < 0");
-    if (n_sections == 0) {
-        if (!(std::isfinite(rho) && rho > 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: need a finite rho > 0");
-        c->rho = rho;
-        c->sec_rho.clear();
-    } else {
-        if (!c->have_sections || n_sections != c->n_sections)
-            return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: n_sections must be the context's section count (" +
-                                                     std::to_string(c->have_sections ? c->n_sections : 0) + ")");
-        if (!section_rho) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: section_rho is null");
-        for (int32_t s = 0; s < n_sections; s++)
-            if (!(std::isfinite(section_rho[s]) && section_rho[s] > 0.0))
-                return set_err(FEMSHELL_ERR_INVALID, "femshell_set_density: section " + std::to_string(s) + ": need a finite density > 0");
-        c->sec_rho.assign(section_rho, section_rho + n_sections);
-        c->rho = 0.0;
-    }
-    c->have_density = true;
-    c->mass_valid = false;
-    return FEMSHELL_OK;
-}
-
-int femshell_lumped_mass(femshell_ctx *c, double *m6_out)
-{
-    if (!c || !m6_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_lumped_mass: null argument");
-    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_lumped_mass: no mesh set");
-    if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_lumped_mass: no density set (femshell_set_density)");
-    int rc = select_device(c);
+    rc = amg_apply(c, b.x.p, b.y.p, nullptr, /*pre_started=*/false);
     if (rc) return rc;
-    rc = ensure_mass(c);
-    if (rc) return rc;
-    return gather_node_vector(c, c->mass.p, m6_out);
-}
-
-int femshell_dynamics_defaults(femshell_dynamics_options *out)
-{
-    if (!out) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_defaults: null argument");
-    out->dt = 0.0;
-    out->beta = 0.25;
-    out->gamma = 0.5;
-    out->alpha = 0.0;
-    return FEMSHELL_OK;
-}
-
-int femshell_dynamics_begin(femshell_ctx *c, const femshell_dynamics_options *opt, const double *u0, const double *v0)
-{
-    if (!c || !opt) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: null argument");
-    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: no mesh set");
-    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: dynamics is active already (femshell_dynamics_end first)");
-    if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: no density set (femshell_set_density)");
-    if (c->have_prescribed)
-        return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: prescribed displacements are in force (femshell_set_prescribed with n = 0 clears them)");
-    const double dt = opt->dt, beta = opt->beta, gamma = opt->gamma, alpha = opt->alpha;
-    if (!(std::isfinite(dt) && dt > 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need a finite dt > 0");
-    if (!(std::isfinite(gamma) && gamma >= 0.5)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need gamma >= 1/2");
-    // (the limit itself is allowed as written in decimals: beta 0.3025 with gamma 0.6, where 0.25 * 1.1 * 1.1 rounds upwards)
-    if (!(std::isfinite(beta) && beta * (1.0 + 1e-12) >= 0.25 * (gamma + 0.5) * (gamma + 0.5)))
-        return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need beta >= (gamma + 1/2)^2 / 4 (the unconditionally stable schemes)");
-    if (!(std::isfinite(alpha) && alpha >= 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: need a finite alpha >= 0");
-    const Plan &p = c->plan;
-    if (u0 && !all_finite(u0, 6ll * p.n_nodes)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: non-finite entry in u0");
-    if (v0 && !all_finite(v0, 6ll * p.n_nodes)) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_begin: non-finite entry in v0");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
-    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_dynamics_begin (assembly, halo exchange of K u0)");
-    int rc = select_device(c);
-    if (rc) return rc;
-    rc = ensure_mass(c);
-    if (rc) return rc;
-    if (!c->matrix_valid) rc = do_assemble(c); // K itself: dynamics is not active yet
-    else if (!c->rhs_valid) rc = do_rhs(c);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    femshell_ctx::Dynamics &d = c->dyn;
-    const size_t n6 = (size_t)p.n_pad * 6;
-    for (int i = 0; i < 2; i++) {
-        FS_HIP(d.u[i].alloc(n6));
-        FS_HIP(d.v[i].alloc(n6));
-        FS_HIP(d.a[i].alloc(n6));
-    }
-    FS_HIP(d.b.alloc(n6));
-    FS_HIP(d.e_partials.alloc(3 * (size_t)kEnergyGrid));
-    FS_HIP(d.e_sums.alloc(3));
-    // the caller's vectors land in the candidate's buffers; K u0 with the K in HBM, before the shift
-    if (u0) {
-        rc = upload_owned_rows(c, u0, d.u[1].p);
-        if (rc) return rc;
-        FS_HIP(hipMemcpyAsync(c->p.p, d.u[1].p, n6 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        rc = halo_exchange(c, c->p.p, st);
-        if (rc) return rc;
-        launch_spmv(c->dm, c->p.p, c->q.p, nullptr, nullptr, st);
-    }
-    if (v0) {
-        rc = upload_owned_rows(c, v0, d.v[1].p);
-        if (rc) return rc;
-    }
-    launch_newmark_init(c->dm, c->mass.p, c->F.p, u0 ? c->q.p : nullptr, u0 ? d.u[1].p : nullptr, v0 ? d.v[1].p : nullptr, alpha, d.u[0].p,
-                        d.v[0].p, d.a[0].p, st);
-    d.k.a0 = 1.0 / (beta * dt * dt);
-    d.k.a1 = gamma / (beta * dt);
-    d.k.a2 = 1.0 / (beta * dt);
-    d.k.a3 = 1.0 / (2.0 * beta) - 1.0;
-    d.k.a4 = gamma / beta - 1.0;
-    d.k.a5 = 0.5 * dt * (gamma / beta - 2.0);
-    d.k.alpha = alpha;
-    d.k.dt = dt;
-    d.k.gamma = gamma;
-    d.k.shift = d.k.a0 + alpha * d.k.a1;
-    launch_mass_shift(c->dm, c->mass.p, d.k.shift, st); // the matrix in HBM is K_eff from here on
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipStreamSynchronize(st));
-    d.cur = 0;
-    d.have_candidate = false;
-    d.active = true;
-    c->jacobi_valid = false; // block-Jacobi and the multigrid hierarchy: from K_eff, at the first step
-    c->amg.reset();
-    c->warm_next = false;
-    return FEMSHELL_OK;
-}
-
-int femshell_dynamics_step(femshell_ctx *c, double rtol, int32_t max_it, femshell_solve_info *info)
-{
-    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_step: null context");
-    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_step: call femshell_dynamics_begin first");
-    int rc = select_device(c);
-    if (rc) return rc;
-    femshell_ctx::Dynamics &d = c->dyn;
-    const size_t n6 = (size_t)c->plan.n_pad * 6;
-    // the solve starts from the committed u (the hand-over of femshell_set_initial_guess)
-    FS_HIP(c->x0.alloc(n6));
-    FS_HIP(hipMemcpyAsync(c->x0.p, d.u[d.cur].p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->warm_next = true;
-    rc = solve_system(c, rtol, max_it, nullptr, info, true);
-    if (rc) return rc;
-    launch_newmark_update(c->dm, d.k, c->x.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.u[d.cur ^ 1].p, d.v[d.cur ^ 1].p, d.a[d.cur ^ 1].p,
-                          c->stream);
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipStreamSynchronize(c->stream));
-    d.have_candidate = true;
-    return FEMSHELL_OK;
-}
-
-int femshell_dynamics_accept(femshell_ctx *c)
-{
-    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_accept: null context");
-    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_accept: call femshell_dynamics_begin first");
-    if (!c->dyn.have_candidate) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_accept: no candidate (femshell_dynamics_step first)");
-    c->dyn.cur ^= 1; // the candidate's buffers become the committed ones: no copy
-    c->dyn.have_candidate = false;
-    return FEMSHELL_OK;
-}
-
-int femshell_dynamics_state(femshell_ctx *c, int32_t which, double *u, double *v, double *a)
-{
-    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_state: null context");
-    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_state: call femshell_dynamics_begin first");
-    if (which != 0 && which != 1) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_state: which must be 0 (committed) or 1 (candidate)");
-    if (which == 1 && !c->dyn.have_candidate) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_state: no candidate (femshell_dynamics_step first)");
-    int rc = select_device(c);
-    if (rc) return rc;
-    const femshell_ctx::Dynamics &d = c->dyn;
-    const int i = which == 0 ? d.cur : d.cur ^ 1;
-    if (u) rc = gather_node_vector(c, d.u[i].p, u);
-    if (!rc && v) rc = gather_node_vector(c, d.v[i].p, v);
-    if (!rc && a) rc = gather_node_vector(c, d.a[i].p, a);
-    return rc;
-}
-
-int femshell_dynamics_energy(femshell_ctx *c, int32_t which, double out[2])
-{
-    if (!c || !out) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_energy: null argument");
-    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_energy: call femshell_dynamics_begin first");
-    if (which != 0 && which != 1) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_energy: which must be 0 (committed) or 1 (candidate)");
-    if (which == 1 && !c->dyn.have_candidate) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_energy: no candidate (femshell_dynamics_step first)");
-    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_dynamics_energy (halo exchange and all-reduce)");
-    int rc = select_device(c);
-    if (rc) return rc;
-    if (!c->matrix_valid) {
-        rc = do_assemble(c);
-        if (rc) return rc;
-    }
-    femshell_ctx::Dynamics &d = c->dyn;
-    const int i = which == 0 ? d.cur : d.cur ^ 1;
-    hipStream_t st = c->stream;
-    // q = K_eff u through the SpMV kernel, whose input carries the ghost entries (the CG vectors are free between solves);
-    // u.K u = u.q - shift u.M u: u is zero on the constrained dofs, where K_eff has no shift
-    FS_HIP(hipMemcpyAsync(c->p.p, d.u[i].p, (size_t)c->plan.n_pad * 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    rc = halo_exchange(c, c->p.p, st);
-    if (rc) return rc;
-    launch_spmv(c->dm, c->p.p, c->q.p, nullptr, nullptr, st);
-    launch_newmark_energy(c->dm, c->mass.p, d.u[i].p, d.v[i].p, c->q.p, d.e_partials.p, d.e_sums.p, st);
-    FS_HIP(hipGetLastError());
-    if (c->comm.active()) {
-        std::string e;
-        if (!comm_allreduce_sum(c->comm, d.e_sums.p, 3, st, &e)) return set_err(FEMSHELL_ERR_COMM, e);
-    }
-    double h[3] = {0.0, 0.0, 0.0};
-    FS_HIP(hipMemcpyAsync(h, d.e_sums.p, sizeof h, hipMemcpyDeviceToHost, st));
-    FS_HIP(hipStreamSynchronize(st));
-    out[0] = 0.5 * h[0];
-    out[1] = 0.5 * h[1] - 0.5 * d.k.shift * h[2];
-    return FEMSHELL_OK;
-}
-
-int femshell_dynamics_end(femshell_ctx *c)
-{
-    if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_end: null context");
-    if (!c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_dynamics_end: dynamics is not active");
-    int rc = select_device(c);
-    if (rc) return rc;
-    FS_HIP(hipStreamSynchronize(c->stream));
-    c->dyn.reset();
-    c->matrix_valid = c->rhs_valid = c->jacobi_valid = false; // K and F again at the next use
-    c->amg.reset();
-    c->warm_next = false;
-    return FEMSHELL_OK;
-}
-
-// ---- modal analysis (modal.cpp, modal.hip) ----------------------------------------------------------------------------------
-
-int femshell_modal_defaults(femshell_modal_options *out)
-{
-    if (!out) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_defaults: null argument");
-    out->n_modes = 6;
-    out->guard = 4;
-    out->max_it = 500;
-    out->reserved = 0;
-    out->tol = 1e-6;
-    out->shift = 0.0;
-    return FEMSHELL_OK;
-}
-
-int femshell_modal_gram(femshell_ctx *c, int32_t qa, const double *A, int32_t qb, const double *B, int32_t weighted, double *G)
-{
-    if (!c || !A || !B || !G) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_gram: null argument");
-    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_gram: no mesh set");
-    if (qa < 1 || qa > kModalMaxCols || qb < 1 || qb > kModalMaxCols) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_gram: qa, qb must be in 1 .. 96");
-    if (weighted && !c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_modal_gram: no density set (femshell_set_density)");
-    if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_modal_gram: single-rank contexts only");
-    int rc = select_device(c);
-    if (rc) return rc;
-    if (weighted && (rc = ensure_mass(c))) return rc;
-    DevBuf<double> da, db, partials, dg;
-    if ((rc = upload_block(c, qa, A, &da))) return rc;
-    if ((rc = upload_block(c, qb, B, &db))) return rc;
-    FS_HIP(partials.alloc((size_t)kGramGrid * qa * qb));
-    FS_HIP(dg.alloc((size_t)qa * qb));
-    launch_gram(c->dm, qa, da.p, qb, db.p, (int64_t)c->plan.n_local_nodes() * 6, weighted ? c->mass.p : nullptr, partials.p, dg.p, c->stream);
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipMemcpyAsync(G, dg.p, (size_t)qa * qb * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream));
-    return FEMSHELL_OK;
-}
-
-int femshell_modes(femshell_ctx *c, const femshell_modal_options *opt, double *lambda_out, double *modes_out, double *residual_out,
-                   femshell_modal_info *info)
-{
-    if (!c || !opt || !lambda_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: null argument");
-    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: no mesh set");
-    if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: no density set (femshell_set_density)");
-    if (c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: not while dynamics is active (femshell_dynamics_end first)");
-    if (opt->n_modes < 1 || opt->guard < 0 || opt->n_modes + opt->guard > kModalMaxBlock)
-        return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: need n_modes >= 1, guard >= 0 and n_modes + guard <= 32");
-    if (!(std::isfinite(opt->tol) && opt->tol > 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: need a finite tol > 0");
-    if (!(std::isfinite(opt->shift) && opt->shift >= 0.0)) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: need a finite shift >= 0");
-    if (opt->max_it < 1) return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: max_it < 1");
-    if (c->cfg.world_size != 1)
-        return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_modes: single-rank contexts only (row-partitioned modal analysis is not implemented)");
-    const Plan &p = c->plan;
-    const int mb = opt->n_modes + opt->guard;
-    {
-        int64_t fixed = 0;
-        for (uint8_t b : c->dmask_global) fixed += __builtin_popcount((unsigned)(b & 0x3Fu));
-        if (6ll * p.n_nodes - fixed < 3ll * mb)
-            return set_err(FEMSHELL_ERR_INVALID, "femshell_modes: fewer than 3 (n_modes + guard) free dofs");
-    }
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
-    TraceRange trace("femshell_modes");
-    const double t_begin = wall_s();
-    int rc = select_device(c);
-    if (rc) return rc;
-    rc = ensure_mass(c);
-    if (rc) return rc;
-    if (!c->matrix_valid || (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)) rc = do_assemble(c); // K itself
-    else if (!c->rhs_valid) rc = do_rhs(c);
-    if (rc) return rc;
-    hipStream_t st = c->stream;
-    const bool shifted = opt->shift > 0.0;
-    // from here on the matrix in HBM is K + shift M; whatever happens, it is gone when the call returns (femshell_dynamics_end)
-    auto leave = [&](int code) {
-        if (shifted) {
-            (void)hipStreamSynchronize(st);
-            c->matrix_valid = c->rhs_valid = c->jacobi_valid = false;
-            c->amg.reset();
-        }
-        return code;
-    };
-    if (shifted) {
-        launch_mass_shift(c->dm, c->mass.p, opt->shift, st);
-        c->jacobi_valid = false;
-        c->amg.reset();
-        if (hipGetLastError() != hipSuccess) return leave(set_err(FEMSHELL_ERR_HIP, "femshell_modes: the mass shift could not be launched"));
-    }
-    double pc_setup_s = 0.0;
-    if (!c->jacobi_valid && (rc = do_jacobi(c))) return leave(rc);
-    if (c->pc.type == FEMSHELL_PC_AMG && (rc = ensure_amg_hierarchy(c, &pc_setup_s))) return leave(rc);
-
-    ModalProblem mp;
-    mp.dm = c->dm;
-    mp.mass = c->mass.p;
-    mp.ld = (int64_t)p.n_local_nodes() * 6;
-    mp.total_slots = p.total_slots();
-    mp.stream = st;
-    mp.block_jacobi = c->pc.type != FEMSHELL_PC_AMG;
-    if (!mp.block_jacobi) mp.precond = [c](const double *r, double *z) { return amg_apply(c, r, z, nullptr, false); };
-    mp.n_modes = opt->n_modes;
-    mp.guard = opt->guard;
-    mp.max_it = opt->max_it;
-    mp.tol = opt->tol;
-    mp.shift = opt->shift;
-    DevBuf<int32_t> node_ids;
-    if (!c->perm.empty()) {
-        if (hipSuccess != node_ids.upload(c->perm, st) || hipSuccess != hipStreamSynchronize(st))
-            return leave(set_err(FEMSHELL_ERR_HIP, "femshell_modes: upload of the node numbering failed"));
-        mp.node_ids = node_ids.p;
-    }
-    ModalResult res;
-    std::unique_ptr<ModalWork, ModalWorkDeleter> work;
-    rc = modal_lobpcg(mp, &res, &work);
-    if (rc) return leave(rc);
-
-    for (int j = 0; j < opt->n_modes; j++) lambda_out[j] = res.theta[(size_t)j] - opt->shift;
-    if (residual_out)
-        for (int j = 0; j < opt->n_modes; j++) residual_out[j] = res.residual[(size_t)j];
-    if (modes_out) {
-        rc = download_block(c, opt->n_modes, res.X, modes_out);
-        if (rc) return leave(rc);
-        const size_t n6 = (size_t)p.n_nodes * 6;
-        for (int j = 0; j < opt->n_modes; j++) { // the entry of largest magnitude (lowest index on ties) is positive
-            double *x = modes_out + (size_t)j * n6;
-            size_t big = 0;
-            for (size_t i = 1; i < n6; i++)
-                if (std::fabs(x[i]) > std::fabs(x[big])) big = i;
-            if (x[big] < 0.0)
-                for (size_t i = 0; i < n6; i++) x[i] = -x[i];
-        }
-    }
-    if (info) {
-        info->iterations = res.iterations;
-        info->converged = res.converged;
-        info->block = res.block;
-        info->restarts = res.restarts;
-        info->fused_product = res.fused_product;
-        info->pc_type = c->pc.type;
-        info->residual_max = res.residual_max;
-        info->seconds_product = res.seconds_product;
-        info->seconds_precond = res.seconds_precond;
-        info->seconds_gram = res.seconds_gram;
-        info->seconds_update = res.seconds_update;
-        info->pc_setup_seconds = pc_setup_s;
-        info->seconds_total = wall_s() - t_begin;
-    }
-    return leave(FEMSHELL_OK);
+    return download_node_block(c, order, 1, b.y.p, 0, z);
 }
 
 int32_t femshell_owned_nodes(femshell_ctx *c, int32_t *ids_out)
@@ -2457,7 +1809,7 @@ int32_t femshell_owned_nodes(femshell_ctx *c, int32_t *ids_out)
         for (int32_t i = 0; i < p.n_own; i++) {
             // (one rank with a renumbering: femshell_export_bsr gives the rows in the caller's order)
             const int32_t row = p.row_begin + i;
-            ids_out[i] = (c->perm.empty() || c->cfg.world_size == 1) ? row : c->perm[(size_t)row];
+            ids_out[i] = c->cfg.world_size == 1 ? row : caller_node(c, row);
         }
     return p.n_own;
 }
@@ -2465,244 +1817,13 @@ int32_t femshell_owned_nodes(femshell_ctx *c, int32_t *ids_out)
 int32_t femshell_row_begin(femshell_ctx *c) { return (c && c->have_mesh) ? c->plan.row_begin : 0; }
 int32_t femshell_row_end(femshell_ctx *c) { return (c && c->have_mesh) ? c->plan.row_end : 0; }
 
-int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, double *mean_ms_out, double *bytes_out)
-{
-    if (!c || !mean_ms_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: null argument");
-    if (c->assembly_pending) {
-        const int prc = finish_pending_assembly(c);
-        if (prc) return prc;
-    }
-    if (!c->have_mesh || reps <= 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no mesh or reps <= 0");
-    int rc = select_device(c);
-    if (rc) return rc;
-    if (which >= FEMSHELL_KERNEL_LUMPED_MASS && which <= FEMSHELL_KERNEL_NEWMARK_UPDATE) {
-        // the kernels of the dynamics, back to back between one event pair (they stream vectors only; k_lumped_mass and
-        // k_mass_shift run once per mesh and per dt)
-        if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no density set");
-        if (which != FEMSHELL_KERNEL_LUMPED_MASS && !c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: dynamics is not active");
-        rc = ensure_mass(c);
-        if (rc) return rc;
-        hipStream_t st = c->stream;
-        femshell_ctx::Dynamics &d = c->dyn;
-        const Plan &p = c->plan;
-        const double t = c->cfg.thickness;
-        FS_HIP(hipStreamSynchronize(st));
-        FS_HIP(hipEventRecord(c->ev0, st));
-        for (int32_t i = 0; i < reps; i++) {
-            if (which == FEMSHELL_KERNEL_LUMPED_MASS)
-                launch_lumped_mass(c->dm, make_double2(c->rho * t, c->rho * t * t * t / 12.0), c->have_sections ? c->sec_mass.p : nullptr,
-                                   c->ds.slice_elem_section, c->mass.p, st);
-            else if (which == FEMSHELL_KERNEL_MASS_SHIFT) launch_mass_shift(c->dm, c->mass.p, d.k.shift, st);
-            else if (which == FEMSHELL_KERNEL_NEWMARK_RHS) launch_newmark_rhs(c->dm, d.k, c->mass.p, c->F.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.b.p, st);
-            else launch_newmark_update(c->dm, d.k, c->x.p, d.u[d.cur].p, d.v[d.cur].p, d.a[d.cur].p, d.u[d.cur ^ 1].p, d.v[d.cur ^ 1].p, d.a[d.cur ^ 1].p, st);
-        }
-        FS_HIP(hipEventRecord(c->ev1, st));
-        FS_HIP(hipStreamSynchronize(st));
-        FS_HIP(hipGetLastError());
-        float ms = 0.f;
-        FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *mean_ms_out = (double)ms / reps;
-        if (which == FEMSHELL_KERNEL_MASS_SHIFT) {
-            c->matrix_valid = c->jacobi_valid = false; // (the shift was added `reps` times)
-            c->amg.reset();
-        }
-        if (which == FEMSHELL_KERNEL_NEWMARK_UPDATE) d.have_candidate = false;
-        if (bytes_out) {
-            const double n = p.n_own, ne = p.n_ltri() + p.n_lquad();
-            // mass: node ids of the slices' element lists (16 B per entry, about six entries per element on a structured mesh:
-            // counted as listed), coordinates once per node, 48 B written; shift: 48 B of M, the six diagonal words read and
-            // written, the mask; right-hand side: M, F, u, v, a read, b written; update: x, u, v, a read, u', v', a' written
-            *bytes_out = which == FEMSHELL_KERNEL_LUMPED_MASS ? 16.0 * (double)p.slice_elem_nodes.size() / 4.0 + 24.0 * n + 48.0 * n + (c->have_sections ? 4.0 * ne : 0.0)
-                         : which == FEMSHELL_KERNEL_MASS_SHIFT ? (48.0 + 96.0 + 1.0) * n
-                         : which == FEMSHELL_KERNEL_NEWMARK_RHS ? (6.0 * 48.0 + 1.0) * n
-                                                                : (7.0 * 48.0 + 1.0) * n;
-        }
-        return FEMSHELL_OK;
-    }
-    if (which >= FEMSHELL_KERNEL_SPMM && which <= FEMSHELL_KERNEL_BLOCK_COMBINE) {
-        // the block kernels of the modal analysis on scratch blocks of hashed vectors, back to back between one event pair
-        if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_time_kernel: the block kernels run on single-rank contexts");
-        if (which == FEMSHELL_KERNEL_GRAM && !c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no density set");
-        const char *e = getenv("FEMSHELL_TIME_KERNEL_COLS");
-        const int nc = e ? atoi(e) : 4;
-        if (nc < 1 || nc > kModalMaxBlock) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: FEMSHELL_TIME_KERNEL_COLS must be in 1 .. 32");
-        if (which == FEMSHELL_KERNEL_GRAM && (rc = ensure_mass(c))) return rc;
-        if (which == FEMSHELL_KERNEL_SPMM && !c->matrix_valid && (rc = do_assemble(c))) return rc;
-        hipStream_t st = c->stream;
-        const Plan &p = c->plan;
-        const int64_t ld = (int64_t)p.n_local_nodes() * 6;
-        const int q = 3 * nc, n_out = 2 * nc;
-        DevBuf<double> S, Y, tb, partials, G, coef;
-        FS_HIP(S.alloc((size_t)q * (size_t)ld));
-        FS_HIP(S.zero(st));
-        launch_modal_init(c->dm, nullptr, which == FEMSHELL_KERNEL_SPMM ? nc : q, S.p, ld, st);
-        if (which == FEMSHELL_KERNEL_SPMM) {
-            FS_HIP(Y.alloc((size_t)nc * (size_t)ld));
-            if (c->dm.symmetric) FS_HIP(tb.alloc((size_t)kSpmmMaxCols * (size_t)p.total_slots() * 6));
-        } else if (which == FEMSHELL_KERNEL_GRAM) {
-            FS_HIP(partials.alloc((size_t)kGramGrid * q * q));
-            FS_HIP(G.alloc((size_t)q * q));
-        } else {
-            FS_HIP(Y.alloc((size_t)n_out * (size_t)ld));
-            const std::vector<double> ones((size_t)q * n_out, 1.0 / q);
-            FS_HIP(coef.upload(ones, st));
-            FS_HIP(hipStreamSynchronize(st)); // (the host array goes out of scope)
-        }
-        CombineSources src;
-        src.S[0] = S.p;
-        src.C[0] = coef.p;
-        src.q[0] = q;
-        int fused = 0;
-        FS_HIP(hipStreamSynchronize(st));
-        FS_HIP(hipEventRecord(c->ev0, st));
-        for (int32_t i = 0; i < reps; i++) {
-            if (which == FEMSHELL_KERNEL_SPMM) block_product(c->dm, S.p, Y.p, ld, nc, tb.p, p.total_slots() * 6, st, &fused);
-            else if (which == FEMSHELL_KERNEL_GRAM) launch_gram(c->dm, q, S.p, q, S.p, ld, c->mass.p, partials.p, G.p, st);
-            else launch_block_combine(c->dm, src, n_out, n_out, Y.p, ld, st);
-        }
-        FS_HIP(hipEventRecord(c->ev1, st));
-        FS_HIP(hipStreamSynchronize(st));
-        FS_HIP(hipGetLastError());
-        float ms = 0.f;
-        FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *mean_ms_out = (double)ms / reps;
-        if (bytes_out) {
-            const double n = p.n_own;
-            // product: every stored block once per pass of four columns (fused) or once per column, indices alike, x read and y
-            // written per column (the transposed products beside the slots are overhead of the method, as in bytes_spmv); Gram:
-            // the operand and the mass once (A = B); combine: 3c columns read, 2c written
-            const double passes = fused ? (double)((nc + spmm_pass_cols(c->dm) - 1) / spmm_pass_cols(c->dm)) : (double)nc;
-            *bytes_out = which == FEMSHELL_KERNEL_SPMM ? passes * (bytes_spmv(c) - 96.0 * n) + 96.0 * n * nc
-                         : which == FEMSHELL_KERNEL_GRAM ? 48.0 * n * (q + 1)
-                                                         : 48.0 * n * (q + n_out);
-        }
-        return FEMSHELL_OK;
-    }
-    if (which == FEMSHELL_KERNEL_ELEMENT_PRODUCT) {
-        // the matrix-free product with the unconstrained element matrices on a hashed vector, back to back between one event pair
-        if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_time_kernel: the element product runs on single-rank contexts");
-        hipStream_t st = c->stream;
-        const Plan &p = c->plan;
-        const int64_t ld = (int64_t)p.n_local_nodes() * 6;
-        DevBuf<double> S, Y;
-        FS_HIP(S.alloc((size_t)ld));
-        FS_HIP(S.zero(st));
-        FS_HIP(Y.alloc((size_t)p.n_pad * 6));
-        launch_modal_init(c->dm, nullptr, 1, S.p, ld, st);
-        FS_HIP(hipStreamSynchronize(st));
-        FS_HIP(hipEventRecord(c->ev0, st));
-        for (int32_t i = 0; i < reps; i++) launch_element_product(c->dm, c->mc, c->sections_or_null(), S.p, nullptr, nullptr, Y.p, false, st);
-        FS_HIP(hipEventRecord(c->ev1, st));
-        FS_HIP(hipGetLastError());
-        rc = check_status(c, "femshell_time_kernel");
-        if (rc) return rc;
-        float ms = 0.f;
-        FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *mean_ms_out = (double)ms / reps;
-        // coordinates once per node, the node ids of the slices' element lists (16 B per entry, counted as listed, as for the
-        // lumped mass; a section index beside each where the context has sections), x read and y written once per node.  (What
-        // the lanes of phase B gather of x beyond that comes from the caches: overhead of the method, not algorithmic traffic.)
-        if (bytes_out)
-            *bytes_out = 24.0 * p.n_own + (16.0 + (c->have_sections ? 4.0 : 0.0)) * (double)p.slice_elem_nodes.size() / 4.0 + 96.0 * p.n_own;
-        return FEMSHELL_OK;
-    }
-    if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->matrix_valid) {
-        rc = do_assemble(c);
-        if (rc) return rc;
-    }
-    if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->rhs_valid) {
-        rc = do_rhs(c);
-        if (rc) return rc;
-    }
-    if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->jacobi_valid) {
-        rc = do_jacobi(c);
-        if (rc) return rc;
-    }
-    hipStream_t st = c->stream;
-    const Plan &p = c->plan;
-    const size_t nrow = (size_t)p.n_pad * 6, nrow_ext = (size_t)p.n_local_nodes() * 6;
-    CgVectors v;
-    if (which != FEMSHELL_KERNEL_ASSEMBLE) {
-        FS_HIP(c->bx.alloc(nrow));
-        FS_HIP(c->br.alloc(nrow));
-        FS_HIP(c->bz.alloc(nrow));
-        FS_HIP(c->bq.alloc(nrow));
-        FS_HIP(c->bp.alloc(nrow_ext));
-        FS_HIP(c->bpart.alloc(2 * (size_t)slice_grid(c->dm)));
-        FS_HIP(c->bscal.alloc(1));
-        FS_HIP(c->bscal.zero(st)); // the reduction's ticket counter must start at 0 (recycled memory is not)
-        v.x = c->bx.p; v.r = c->br.p; v.z = c->bz.p; v.p = c->bp.p; v.q = c->bq.p;
-        v.b = c->F.p; v.partials = c->bpart.p; v.s = c->bscal.p; v.hist = nullptr; v.hist_cap = 0;
-        FS_HIP(c->bp.zero(st));
-        launch_cg_init(c->dm, v, false, st);                // x=0, r=b, z=M^-1 b, p=z
-        launch_cg_scalar(c->dm, v, true, 2, CG_PHASE_INIT, 0.0, st);
-        launch_spmv(c->dm, v.p, v.q, v.partials, v.s, st);  // q = A p
-        launch_cg_scalar(c->dm, v, true, 1, CG_PHASE_ALPHA, 0.0, st);
-    }
-    FS_HIP(hipStreamSynchronize(st));
-    double bytes = 0.0;
-    if (which == FEMSHELL_KERNEL_ASSEMBLE) {
-        FS_HIP(hipEventRecord(c->ev0, st));
-        for (int32_t i = 0; i < reps; i++)
-            if (!launch_assemble(c->dm, c->mc, st, c->sections_or_null()))
-                return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: the context's sections have no table in HBM");
-        FS_HIP(hipEventRecord(c->ev1, st));
-        FS_HIP(hipStreamSynchronize(st));
-        FS_HIP(hipGetLastError());
-        float ms = 0.f;
-        FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        *mean_ms_out = (double)ms / reps;
-        bytes = bytes_assemble(c);
-    } else {
-        // the CG kernels are timed where they run: `reps` iterations of the local recurrence (this rank's rows, no
-        // communication, no stopping test), an event pair around the chosen kernel of every iteration.  A kernel
-        // launched back to back with itself finds different cache contents and measured up to 13 % faster.
-        if (which != FEMSHELL_KERNEL_SPMV && which != FEMSHELL_KERNEL_CG_UPDATE && which != FEMSHELL_KERNEL_CG_DIRECTION)
-            return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: unknown kernel");
-        double sum_ms = 0.0;
-        for (int32_t i = 0; i < reps; i++) {
-            // (as cg_classic runs them: with symmetric storage the SpMV is its first phase and the update kernel
-            // collects the transposed products)
-            if (which == FEMSHELL_KERNEL_SPMV) FS_HIP(hipEventRecord(c->ev0, st));
-            if (c->dm.symmetric) launch_spmv_direct(c->dm, v.p, v.q, v.partials, v.s, st);
-            else launch_spmv(c->dm, v.p, v.q, v.partials, v.s, st);
-            if (which == FEMSHELL_KERNEL_SPMV) FS_HIP(hipEventRecord(c->ev1, st));
-            launch_cg_scalar(c->dm, v, true, 1, CG_PHASE_ALPHA, 0.0, st);
-            if (which == FEMSHELL_KERNEL_CG_UPDATE) FS_HIP(hipEventRecord(c->ev0, st));
-            launch_cg_update(c->dm, v, st, c->dm.symmetric != 0);
-            if (which == FEMSHELL_KERNEL_CG_UPDATE) FS_HIP(hipEventRecord(c->ev1, st));
-            launch_cg_scalar(c->dm, v, true, 2, CG_PHASE_BETA, 0.0, st);
-            if (which == FEMSHELL_KERNEL_CG_DIRECTION) FS_HIP(hipEventRecord(c->ev0, st));
-            launch_cg_direction(c->dm, v, st);
-            if (which == FEMSHELL_KERNEL_CG_DIRECTION) FS_HIP(hipEventRecord(c->ev1, st));
-            FS_HIP(hipStreamSynchronize(st));
-            float ms = 0.f;
-            FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            sum_ms += ms;
-        }
-        FS_HIP(hipGetLastError());
-        *mean_ms_out = sum_ms / reps;
-        bytes = which == FEMSHELL_KERNEL_SPMV ? bytes_spmv(c) : which == FEMSHELL_KERNEL_CG_UPDATE ? bytes_update(c) : bytes_direction(c);
-    }
-    if (bytes_out) *bytes_out = bytes;
-    if (which == FEMSHELL_KERNEL_ASSEMBLE) {
-        rc = check_status(c, "femshell_time_kernel");
-        if (rc) return rc;
-        c->matrix_valid = true;
-        c->jacobi_valid = false;
-        if (c->have_prescribed) c->rhs_valid = false; // (the assembly kernel wrote the masked loads over F)
-    }
-    return FEMSHELL_OK;
-}
-
 int femshell_sync(femshell_ctx *c)
 {
     if (!c) return set_err(FEMSHELL_ERR_INVALID, "femshell_sync: null context");
     int rc = select_device(c);
     if (rc) return rc;
-    if (c->assembly_pending) return finish_pending_assembly(c); // (synchronises)
-    FS_HIP(hipStreamSynchronize(c->stream));
-    return FEMSHELL_OK;
+    if (!c->assembly_pending) FS_HIP(hipStreamSynchronize(c->stream));
+    return finish_pending_assembly(c); // (synchronises where an assembly is pending)
 }
 
 } // extern "C"

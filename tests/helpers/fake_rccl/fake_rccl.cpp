@@ -3,7 +3,7 @@
 //
 // A test box has one MI355X, and RCCL refuses two ranks on one device, so the multi-rank driver of
 // libfemshell (halo packing, ghost placement, all-reduce points, row gather -- csrc/api.cpp,
-// csrc/comm.cpp) could otherwise never run before the 8-GPU benchmark.  libfemshell opens the library
+// csrc/node_io.cpp, csrc/comm.cpp) could otherwise never run before the 8-GPU benchmark.  libfemshell opens the library
 // named by FEMSHELL_RCCL_LIB instead of librccl.so.1 when that variable is set (tests only).
 // Implements exactly the entry points comm.cpp resolves, with RCCL's signatures and semantics
 // (stream-ordered, grouped send/recv/broadcast); reductions add the ranks' contributions in rank order.
