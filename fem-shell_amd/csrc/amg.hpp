@@ -129,7 +129,7 @@ void pack_sliced_ell(const Bsr &A, bool diag_first, SlicedEll *out);
 
 // symmetric storage of a square operator with a symmetric pattern (coarse level matrices): the diagonal block in slot
 // 0 and the blocks (a, c) with c > a; the in-lists tell row c which stored blocks (a, c) act on it through their
-// transpose (plan.hpp describes the layout; k_spmv_sym / k_sym_gather multiply with it)
+// transpose (plan.hpp describes the layout; k_spmv_sym / k_sym_gather_node multiply with it)
 struct SlicedEllSym : SlicedEll {
     int32_t max_in_width = 0;
     std::vector<int32_t> in_width;

@@ -204,7 +204,7 @@ bool amg_uses_single_precision(const Amg &H);
 double amg_lambda_safety();
 int amg_power_iterations();
 // z = M(r): one multigrid cycle on the context's stream (all launches are no-ops once gate->done != 0)
-// (pre_started: the caller's kernel took the first step of the pre-smoothing on level 0 already -- k_pcg_update_start: the
+// (pre_started: the caller's kernel took the first step of the pre-smoothing on level 0 already -- k_pcg_update_start_node: the
 //  direction in the level's d vector, the iterate = that direction in amg_apply_iterate(c, z))
 int amg_apply(femshell_ctx *c, const double *r, double *z, const CgScalars *gate, bool pre_started = false);
 // the vector the cycle on level 0 iterates in: z itself, or -- row-partitioned contexts -- the work vector with ghost space

@@ -760,7 +760,7 @@ int power_iteration_dist(femshell_ctx *c, AmgLevel &L, const DeviceMatrix &A, in
     for (int it = 0; it < iterations; it++) {
         int rc = level_halo_exchange(c, *L.halo, x, 6, st);
         if (rc) return rc;
-        launch_spmv(A, x, L.q.p, nullptr, nullptr, st);
+        launch_spmv(A, x, L.q.p, SpmvEpilogue(), nullptr, st);
         launch_minv_apply_norm(A, L.q.p, z, part.p + (size_t)(it & 1) * G, st);
         if (L.patches) { // the level's smoother applies the cluster blocks: lambda_max of THAT operator (amg_solve.cpp)
             launch_patch_correct(L.patches->view(), L.q.p, 1.0, z, false, nullptr, nullptr, st);

@@ -1,147 +1,16 @@
 // amg_kernels.hip -- gfx950 vector kernels of the multigrid preconditioner (amg.hpp) and of the flexible PCG
-// around it.  All of them are HBM streaming kernels with one lane per scalar row of a 32-node slice, like the
-// CG kernels of kernels.hip; the level operators, restrictions and prolongations are multiplied by k_spmv.
+// around it.  All of them are HBM streaming kernels: those that apply the block-Jacobi inverse with one lane per node
+// (device_common.hpp, the _node kernels), the others with one lane per scalar row of a 32-node slice like the CG kernels of
+// cg_kernels.hip; the level operators, restrictions and prolongations are multiplied by the products of spmv_kernels.hip.
 #include "amg_kernels.hpp"
 
 #include "device_common.hpp"
 
 namespace femshell {
 
-// ---- Chebyshev smoother ------------------------------------------------------------------------------------
-
+// ---- Chebyshev smoother: one lane per node (device_common.hpp), no LDS, no barriers -------------------------------------------
+// first step of a smoothing: d = inv_theta D^-1 r, x = d or (accumulate) x += d
 // (kD32: the direction is kept in single precision -- the input of a smoothing product with DeviceMatrix::vec32 == 2)
-template <bool kD32>
-__global__ __launch_bounds__(192) void k_cheb_start(DeviceMatrix m, const double *__restrict__ rin, double *__restrict__ d,
-                                                    double *x, double inv_theta, int accumulate, const CgScalars *gate)
-{
-    __shared__ double rs[kSliceRows];
-    if (gate != nullptr && gate->done != 0) return;
-    const int t = threadIdx.x;
-    for (SliceWalk w(m.n_slices); w.valid(); w.next()) {
-        const int sl = w.s;
-        const int64_t row = (int64_t)sl * kSliceRows + t;
-        const MinvRow mr = load_minv_smoother(m, sl, t);
-        const double rv = rin[row];
-        const double xv = accumulate ? x[row] : 0.0;
-        __syncthreads();
-        rs[t] = rv;
-        __syncthreads();
-        const double dv = inv_theta * apply_minv(mr, t, rs);
-        if (kD32) reinterpret_cast<float *>(d)[row] = (float)dv;
-        else d[row] = dv;
-        x[row] = xv + dv;
-    }
-}
-
-bool node_kernels();
-int node_grid(const DeviceMatrix &m);
-template <bool kD32>
-__global__ __launch_bounds__(64) void k_cheb_start_node(DeviceMatrix m, const double *__restrict__ rin, double *__restrict__ d, double *x, double inv_theta,
-                                  int accumulate, const CgScalars *gate);
-template <bool kGather, int kVec>
-__global__ __launch_bounds__(64) void k_cheb_step_node(DeviceMatrix m, const double *rin, const double *__restrict__ q, double *rout, double *__restrict__ d,
-                                 double *__restrict__ x, double a, double c, const CgScalars *gate);
-
-void launch_cheb_start(const DeviceMatrix &m, const double *rin, double *d, double *x, double inv_theta, bool accumulate,
-                       const CgScalars *gate, hipStream_t st, int vec32)
-{
-    if (node_kernels()) {
-        const dim3 g(node_grid(m)), b(64);
-        if (vec32 == 2) hipLaunchKernelGGL(k_cheb_start_node<true>, g, b, 0, st, m, rin, d, x, inv_theta, accumulate ? 1 : 0, gate);
-        else hipLaunchKernelGGL(k_cheb_start_node<false>, g, b, 0, st, m, rin, d, x, inv_theta, accumulate ? 1 : 0, gate);
-        return;
-    }
-    if (vec32 == 2) hipLaunchKernelGGL(k_cheb_start<true>, dim3(slice_grid(m)), dim3(192), 0, st, m, rin, d, x, inv_theta, accumulate ? 1 : 0, gate);
-    else hipLaunchKernelGGL(k_cheb_start<false>, dim3(slice_grid(m)), dim3(192), 0, st, m, rin, d, x, inv_theta, accumulate ? 1 : 0, gate);
-}
-
-// (kGather: symmetric storage, q holds the direct part of A d only -- launch_spmv_direct -- and the row adds the
-// transposed products of its in-list here, as k_cg_update<true> does for the CG iteration)
-// (kVec: what the smoothing product left in single precision, DeviceMatrix::vec32 -- 1: q and the transposed products are
-// floats in their buffers, 2: the direction d is kept as floats too; residual and iterate stay FP64)
-template <bool kGather, int kVec>
-__global__ __launch_bounds__(192) void k_cheb_step(DeviceMatrix m, const double *rin, const double *__restrict__ q,
-                                                   double *rout, double *__restrict__ d, double *__restrict__ x, double a,
-                                                   double c, const CgScalars *gate)
-{
-    __shared__ double rs[kSliceRows];
-    if (gate != nullptr && gate->done != 0) return;
-    const int t = threadIdx.x;
-    const float *qf = reinterpret_cast<const float *>(q), *tf = reinterpret_cast<const float *>(m.tbuf);
-    float *df = reinterpret_cast<float *>(d);
-    for (SliceWalk w(m.n_slices); w.valid(); w.next()) {
-        const int sl = w.s;
-        const int64_t row = (int64_t)sl * kSliceRows + t;
-        const MinvRow mr = load_minv_smoother(m, sl, t);
-        double qv = kVec >= 1 ? (double)qf[row] : q[row];
-        if (kGather) {
-            const int Wi = m.in_width[sl], n = t / 6, j = t % 6;
-            const int64_t ib = m.in_base[sl];
-            // the slot indices of the first entries together, then their products together (as in k_cg_update): one entry
-            // at a time is two dependent memory round trips per entry; the order of the additions is the same
-            int32_t slot4[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) slot4[k] = (k < Wi) ? m.gat_slots[ib + (int64_t)k * kSliceNodes + n] : -1;
-            double t4[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                t4[k] = slot4[k] < 0 ? 0.0 : (kVec >= 1 ? (double)tf[(int64_t)slot4[k] * 6 + j] : m.tbuf[(int64_t)slot4[k] * 6 + j]);
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (slot4[k] >= 0) qv += t4[k];
-            for (int k = 4; k < Wi; k++) {
-                const int32_t slot = m.gat_slots[ib + (int64_t)k * kSliceNodes + n];
-                if (slot >= 0) qv += kVec >= 1 ? (double)tf[(int64_t)slot * 6 + j] : m.tbuf[(int64_t)slot * 6 + j];
-            }
-        }
-        const double rn = rin[row] - qv;
-        const double dv = kVec == 2 ? (double)df[row] : d[row], xv = x[row];
-        rout[row] = rn;
-        __syncthreads();
-        rs[t] = rn;
-        __syncthreads();
-        const double dn = a * dv + c * apply_minv(mr, t, rs);
-        if (kVec == 2) df[row] = (float)dn;
-        else d[row] = dn;
-        x[row] = xv + dn;
-    }
-}
-
-void launch_cheb_step(const DeviceMatrix &m, const double *rin, const double *q, double *rout, double *d, double *x,
-                      double a, double c, const CgScalars *gate, hipStream_t st, bool gather, int vec32)
-{
-    if (node_kernels()) {
-        const dim3 g(node_grid(m)), b(64);
-        if (gather && vec32 == 2) hipLaunchKernelGGL((k_cheb_step_node<true, 2>), g, b, 0, st, m, rin, q, rout, d, x, a, c, gate);
-        else if (gather && vec32 == 1) hipLaunchKernelGGL((k_cheb_step_node<true, 1>), g, b, 0, st, m, rin, q, rout, d, x, a, c, gate);
-        else if (gather) hipLaunchKernelGGL((k_cheb_step_node<true, 0>), g, b, 0, st, m, rin, q, rout, d, x, a, c, gate);
-        else hipLaunchKernelGGL((k_cheb_step_node<false, 0>), g, b, 0, st, m, rin, q, rout, d, x, a, c, gate);
-        return;
-    }
-    const dim3 grid(slice_grid(m)), block(192);
-    if (gather && vec32 == 2) hipLaunchKernelGGL((k_cheb_step<true, 2>), grid, block, 0, st, m, rin, q, rout, d, x, a, c, gate);
-    else if (gather && vec32 == 1) hipLaunchKernelGGL((k_cheb_step<true, 1>), grid, block, 0, st, m, rin, q, rout, d, x, a, c, gate);
-    else if (gather) hipLaunchKernelGGL((k_cheb_step<true, 0>), grid, block, 0, st, m, rin, q, rout, d, x, a, c, gate);
-    else hipLaunchKernelGGL((k_cheb_step<false, 0>), grid, block, 0, st, m, rin, q, rout, d, x, a, c, gate);
-}
-
-// ---- one lane per node (device_common.hpp): the smoother's vector kernels without LDS and barriers -------------------------
-// FEMSHELL_NODE_KERNELS=0: the one-lane-per-scalar-row kernels of rounds 1-4 (A/B runs)
-bool node_kernels()
-{
-    static const bool on = [] {
-        const char *e = getenv("FEMSHELL_NODE_KERNELS");
-        return !(e && atoi(e) == 0);
-    }();
-    return on;
-}
-// workgroups of a node kernel: 64 lanes = two slices; never more than the per-slice kernels of the same matrix launch
-int node_grid(const DeviceMatrix &m)
-{
-    const int g = 8 * ((node_pairs(m.n_slices) + 7) / 8), cap = slice_grid(m);
-    return g < cap ? g : cap;
-}
-
 template <bool kD32>
 __global__ __launch_bounds__(64) void k_cheb_start_node(DeviceMatrix m, const double *__restrict__ rin, double *__restrict__ d, double *x,
                                                         double inv_theta, int accumulate, const CgScalars *gate)
@@ -168,6 +37,19 @@ __global__ __launch_bounds__(64) void k_cheb_start_node(DeviceMatrix m, const do
     }
 }
 
+void launch_cheb_start(const DeviceMatrix &m, const double *rin, double *d, double *x, double inv_theta, bool accumulate,
+                       const CgScalars *gate, hipStream_t st, int vec32)
+{
+    const dim3 g(node_grid(m)), b(64);
+    if (vec32 == 2) hipLaunchKernelGGL(k_cheb_start_node<true>, g, b, 0, st, m, rin, d, x, inv_theta, accumulate ? 1 : 0, gate);
+    else hipLaunchKernelGGL(k_cheb_start_node<false>, g, b, 0, st, m, rin, d, x, inv_theta, accumulate ? 1 : 0, gate);
+}
+
+// a later step: r_out = r_in - q; d = a d + c D^-1 r_out; x += d
+// (kGather: symmetric storage, q holds the direct part of A d only -- launch_spmv_sym_phase1 -- and the node adds the
+// transposed products of its in-list here, as k_cg_update_node<true> does for the CG iteration)
+// (kVec: what the smoothing product left in single precision, DeviceMatrix::vec32 -- 1: q and the transposed products are
+// floats in their buffers, 2: the direction d is kept as floats too; residual and iterate stay FP64)
 template <bool kGather, int kVec>
 __global__ __launch_bounds__(64) void k_cheb_step_node(DeviceMatrix m, const double *rin, const double *__restrict__ q, double *rout,
                                                        double *__restrict__ d, double *__restrict__ x, double a, double c,
@@ -201,40 +83,24 @@ __global__ __launch_bounds__(64) void k_cheb_step_node(DeviceMatrix m, const dou
     }
 }
 
+void launch_cheb_step(const DeviceMatrix &m, const double *rin, const double *q, double *rout, double *d, double *x,
+                      double a, double c, const CgScalars *gate, hipStream_t st, bool gather, int vec32)
+{
+    const dim3 g(node_grid(m)), b(64);
+    if (gather && vec32 == 2) hipLaunchKernelGGL((k_cheb_step_node<true, 2>), g, b, 0, st, m, rin, q, rout, d, x, a, c, gate);
+    else if (gather && vec32 == 1) hipLaunchKernelGGL((k_cheb_step_node<true, 1>), g, b, 0, st, m, rin, q, rout, d, x, a, c, gate);
+    else if (gather) hipLaunchKernelGGL((k_cheb_step_node<true, 0>), g, b, 0, st, m, rin, q, rout, d, x, a, c, gate);
+    else hipLaunchKernelGGL((k_cheb_step_node<false, 0>), g, b, 0, st, m, rin, q, rout, d, x, a, c, gate);
+}
+
 // ---- fused passes of the cycle (round 5) ---------------------------------------------------------------------
 // The first step of a Chebyshev smoothing -- d = inv_theta D^-1 r, x (+)= d -- is a block-diagonal operation on the residual it
 // starts from: it belongs in the epilogue of the kernel that PRODUCES that residual, not in a pass of its own that reads the
-// residual back (k_cheb_start: 0.41 GB and 106 us per call on level 0 of the 4M-triangle panel).  Same arithmetic, same bits.
+// residual back (k_cheb_start_node's predecessor: 0.41 GB and 106 us per call on level 0 of the 4M-triangle panel).  Same arithmetic, same bits.
 
-// second phase of a symmetric-storage product (k_sym_gather) + the start of the post-smoothing:
+// second phase of a symmetric-storage product (k_sym_gather_node) + the start of the post-smoothing:
 //   out = base_vec + sign (y + transposed products);  d = inv_theta D^-1 out;  x += d
 // (kQ32: y and the transposed products are floats; kD32: d is stored as floats -- DeviceMatrix::vec32 of the smoother's matrix m)
-template <bool kQ32, bool kD32>
-__global__ __launch_bounds__(192) void k_sym_gather_start(DeviceMatrix m, const double *y, double *out, const double *base_vec, double sign,
-                                                          double *__restrict__ d, double *__restrict__ x, double inv_theta, const CgScalars *s)
-{
-    __shared__ double rs[kSliceRows];
-    if (s != nullptr && s->done != 0) return;
-    const int t = threadIdx.x, n = t / 6, j = t % 6;
-    const float *yf = reinterpret_cast<const float *>(y);
-    for (SliceWalk w(m.n_slices); w.valid(); w.next()) {
-        const int sl = w.s;
-        const int64_t row = (int64_t)sl * kSliceRows + t;
-        const MinvRow mr = load_minv_smoother(m, sl, t);
-        const double bv = base_vec[row], xv = x[row];
-        const double acc = gather_transposed<kQ32>(m, sl, n, j, kQ32 ? (double)yf[row] : y[row]);
-        const double rn = bv + sign * acc;
-        out[row] = rn;
-        __syncthreads();
-        rs[t] = rn;
-        __syncthreads();
-        const double dv = inv_theta * apply_minv(mr, t, rs);
-        if (kD32) reinterpret_cast<float *>(d)[row] = (float)dv;
-        else d[row] = dv;
-        x[row] = xv + dv;
-    }
-}
-
 template <bool kQ32, bool kD32>
 __global__ __launch_bounds__(64) void k_sym_gather_start_node(DeviceMatrix m, const double *y, double *out, const double *base_vec, double sign,
                                                               double *__restrict__ d, double *__restrict__ x, double inv_theta,
@@ -270,68 +136,17 @@ __global__ __launch_bounds__(64) void k_sym_gather_start_node(DeviceMatrix m, co
 void launch_sym_gather_start(const DeviceMatrix &m, const double *y, double *out, const double *base_vec, double sign, double *d, double *x,
                              double inv_theta, bool q32, bool d32, const CgScalars *s, hipStream_t st)
 {
-    if (node_kernels()) {
-        const dim3 g(node_grid(m)), b(64);
-        if (q32 && d32) hipLaunchKernelGGL((k_sym_gather_start_node<true, true>), g, b, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
-        else if (q32) hipLaunchKernelGGL((k_sym_gather_start_node<true, false>), g, b, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
-        else if (d32) hipLaunchKernelGGL((k_sym_gather_start_node<false, true>), g, b, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
-        else hipLaunchKernelGGL((k_sym_gather_start_node<false, false>), g, b, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
-        return;
-    }
-    const dim3 grid(slice_grid(m)), block(192);
-    if (q32 && d32) hipLaunchKernelGGL((k_sym_gather_start<true, true>), grid, block, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
-    else if (q32) hipLaunchKernelGGL((k_sym_gather_start<true, false>), grid, block, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
-    else if (d32) hipLaunchKernelGGL((k_sym_gather_start<false, true>), grid, block, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
-    else hipLaunchKernelGGL((k_sym_gather_start<false, false>), grid, block, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
+    const dim3 g(node_grid(m)), b(64);
+    if (q32 && d32) hipLaunchKernelGGL((k_sym_gather_start_node<true, true>), g, b, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
+    else if (q32) hipLaunchKernelGGL((k_sym_gather_start_node<true, false>), g, b, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
+    else if (d32) hipLaunchKernelGGL((k_sym_gather_start_node<false, true>), g, b, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
+    else hipLaunchKernelGGL((k_sym_gather_start_node<false, false>), g, b, 0, st, m, y, out, base_vec, sign, d, x, inv_theta, s);
 }
 
 // the update of the flexible PCG (k_pcg_update: x += alpha p, r -= alpha q, partial sums of r.r) + what stands on both sides
-// of it: in front, the second phase of q = K p on symmetric storage (kGather: q arrives as the direct part, the row adds the
-// transposed products of its in-list as k_sym_gather does, and stores the whole q for the z.q of k_pcg_dots); behind, the start
+// of it: in front, the second phase of q = K p on symmetric storage (kGather: q arrives as the direct part, the node adds the
+// transposed products of its in-list as k_sym_gather_node does, and stores the whole q for the z.q of k_pcg_dots); behind, the start
 // of the cycle's pre-smoothing on the new residual: d = inv_theta D^-1 r, z = d (m: level 0 as the smoother sees it)
-template <bool kGather, bool kD32>
-__global__ __launch_bounds__(192) void k_pcg_update_start(DeviceMatrix m, CgVectors v, double *__restrict__ d, double *__restrict__ z,
-                                                          double inv_theta)
-{
-    __shared__ double rs[kSliceRows];
-    __shared__ double sh[3];
-    if (v.s->done != 0) return;
-    const int t = threadIdx.x, n = t / 6, j = t % 6;
-    const double alpha = v.s->alpha;
-    double d1 = 0.0, d2 = 0.0; // r.r and x.x (the refinement pass's stopping rule: CG_PHASE_FLEX_CONV)
-    for (SliceWalk w(m.n_slices); w.valid(); w.next()) {
-        const int sl = w.s;
-        const int64_t row = (int64_t)sl * kSliceRows + t;
-        const MinvRow mr = load_minv_smoother(m, sl, t);
-        const double pv = v.p[row], xv = v.x[row], rv = v.r[row];
-        double qv = v.q[row];
-        if (kGather) {
-            qv = gather_transposed<false>(m, sl, n, j, qv);
-            v.q[row] = qv;
-        }
-        const double xn = xv + alpha * pv;
-        v.x[row] = xn;
-        d2 += xn * xn;
-        const double rn = rv - alpha * qv;
-        v.r[row] = rn;
-        d1 += rn * rn;
-        __syncthreads();
-        rs[t] = rn;
-        __syncthreads();
-        const double dv = inv_theta * apply_minv(mr, t, rs);
-        if (kD32) reinterpret_cast<float *>(d)[row] = (float)dv;
-        else d[row] = dv;
-        z[row] = dv;
-    }
-    const double t1 = block_sum(d1, sh);
-    __syncthreads();
-    const double t2 = block_sum(d2, sh);
-    if (threadIdx.x == 0) {
-        v.partials[blockIdx.x] = t1;
-        v.partials[gridDim.x + blockIdx.x] = t2;
-    }
-}
-
 // (launched with the grid of the per-slice kernels, slice_grid(m): the scalar step reduces that many partial sums)
 template <bool kGather, bool kD32>
 __global__ __launch_bounds__(64) void k_pcg_update_start_node(DeviceMatrix m, CgVectors v, double *__restrict__ d, double *__restrict__ z,
@@ -381,19 +196,11 @@ __global__ __launch_bounds__(64) void k_pcg_update_start_node(DeviceMatrix m, Cg
 void launch_pcg_update_start(const DeviceMatrix &m, const CgVectors &v, double *d, double *z, double inv_theta, bool gather, bool d32,
                              hipStream_t st)
 {
-    if (node_kernels()) {
-        const dim3 g(slice_grid(m)), b(64);
-        if (gather && d32) hipLaunchKernelGGL((k_pcg_update_start_node<true, true>), g, b, 0, st, m, v, d, z, inv_theta);
-        else if (gather) hipLaunchKernelGGL((k_pcg_update_start_node<true, false>), g, b, 0, st, m, v, d, z, inv_theta);
-        else if (d32) hipLaunchKernelGGL((k_pcg_update_start_node<false, true>), g, b, 0, st, m, v, d, z, inv_theta);
-        else hipLaunchKernelGGL((k_pcg_update_start_node<false, false>), g, b, 0, st, m, v, d, z, inv_theta);
-        return;
-    }
-    const dim3 grid(slice_grid(m)), block(192);
-    if (gather && d32) hipLaunchKernelGGL((k_pcg_update_start<true, true>), grid, block, 0, st, m, v, d, z, inv_theta);
-    else if (gather) hipLaunchKernelGGL((k_pcg_update_start<true, false>), grid, block, 0, st, m, v, d, z, inv_theta);
-    else if (d32) hipLaunchKernelGGL((k_pcg_update_start<false, true>), grid, block, 0, st, m, v, d, z, inv_theta);
-    else hipLaunchKernelGGL((k_pcg_update_start<false, false>), grid, block, 0, st, m, v, d, z, inv_theta);
+    const dim3 g(slice_grid(m)), b(64);
+    if (gather && d32) hipLaunchKernelGGL((k_pcg_update_start_node<true, true>), g, b, 0, st, m, v, d, z, inv_theta);
+    else if (gather) hipLaunchKernelGGL((k_pcg_update_start_node<true, false>), g, b, 0, st, m, v, d, z, inv_theta);
+    else if (d32) hipLaunchKernelGGL((k_pcg_update_start_node<false, true>), g, b, 0, st, m, v, d, z, inv_theta);
+    else hipLaunchKernelGGL((k_pcg_update_start_node<false, false>), g, b, 0, st, m, v, d, z, inv_theta);
 }
 
 // ---- power iteration ---------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // amg_kernels.hpp -- launchers of the multigrid cycle's vector kernels (amg_kernels.hip).  The matrix products of
-// the cycle (level operators, restriction, prolongation) all run through k_spmv of kernels.hip: every operator of
+// the cycle (level operators, restriction, prolongation) all run through launch_spmv of spmv_kernels.hip: every operator of
 // the hierarchy is a sliced block ELL matrix of 6x6 blocks.
 #pragma once
 
@@ -19,7 +19,7 @@ namespace femshell {
 //  products, 2: the direction d as well; d and q are then arrays of floats in the same buffers)
 void launch_cheb_start(const DeviceMatrix &m, const double *rin, double *d, double *x, double inv_theta, bool accumulate,
                        const CgScalars *gate, hipStream_t st, int vec32 = 0);
-// (gather: symmetric storage, q is the direct part of A d from launch_spmv_direct; the kernel collects the transposed products)
+// (gather: symmetric storage, q is the direct part of A d from launch_spmv_sym_phase1; the kernel collects the transposed products)
 void launch_cheb_step(const DeviceMatrix &m, const double *rin, const double *q, double *rout, double *d, double *x,
                       double a, double c, const CgScalars *gate, hipStream_t st, bool gather = false, int vec32 = 0);
 

@@ -277,7 +277,7 @@ int power_iteration_start(femshell_ctx *c, AmgLevel &L, const DeviceMatrix &A, i
     if (iterations < 2) iterations = 2;
     pw->iterations = iterations;
     for (int it = 0; it < iterations; it++) {
-        launch_spmv(A, x, L.q.p, nullptr, nullptr, st);
+        launch_spmv(A, x, L.q.p, SpmvEpilogue(), nullptr, st);
         launch_minv_apply_norm(A, L.q.p, z, pw->part.p + (size_t)(it & 1) * pw->G, st);
         if (L.patches) { // the level's smoother applies the cluster blocks: lambda_max of THAT operator
             launch_patch_correct(L.patches->view(), L.q.p, 1.0, z, false, nullptr, nullptr, st);
@@ -447,7 +447,7 @@ int dense_inverse_defect(femshell_ctx *c, AmgLevel &L, const DeviceMatrix &A, Am
     const int64_t n6 = 6ll * L.n_pad;
     launch_fill_hash(L.r.p, 6ll * L.n, n6, st);
     launch_dense_gemv_big(H.coarse_inv.p, H.coarse_inv32.p, H.coarse_lda, L.r.p, L.d.p, 6 * L.n, 6 * L.n_pad, nullptr, st);
-    launch_spmv(A, L.d.p, L.q.p, nullptr, nullptr, st);
+    launch_spmv(A, L.d.p, L.q.p, SpmvEpilogue(), nullptr, st);
     launch_sub(L.q.p, L.r.p, L.q.p, n6, st);
     DevBuf<double> scratch;
     FS_HIP(scratch.alloc(3 * 128));
@@ -925,11 +925,8 @@ int amg_finish_hierarchy(femshell_ctx *c, Bsr &A, std::vector<double> &B, DevBuf
             // every such shell tried, and the all-FP64 rebuild of femshell_solve did what this line does at once)
             if (L.patches) continue;
             const int64_t nv = (l == 0 ? (int64_t)pl.total_slots() : (int64_t)L.A.vals.n / 36) * 36;
-            {
-                FS_HIP(L.A32.alloc((size_t)nv));
-                launch_to_f32(A.vals, L.A32.p, nv, st);
-                if (const char *sb = getenv("FEMSHELL_AMG_SMOOTH_SIGBITS")) launch_round_sig(L.A32.p, nv, atoi(sb), st); // (experiment)
-            }
+            FS_HIP(L.A32.alloc((size_t)nv));
+            launch_to_f32(A.vals, L.A32.p, nv, st);
             // the block-Jacobi inverse the smoothers apply, and the transfer operators (R = P^T value by value, so the
             // rounded pair is still a transposed pair and the cycle stays symmetric)
             const int64_t nm = (int64_t)A.n_slices * 21 * kSliceNodes;
@@ -999,8 +996,8 @@ bool residual_increment()
 bool has_lowp(const DeviceMatrix &A) { return A.vals32 != nullptr; }
 
 // FEMSHELL_AMG_FUSE (bit mask; A/B runs and tests): the first step of a Chebyshev smoothing runs in the epilogue of the kernel that
-// produces its residual.  1: k_pcg_update_start (the update of the flexible PCG + the second phase of q = K p + the start of the
-// cycle's pre-smoothing on level 0); 2: k_sym_gather_start (second phase of the increment product in front of a post-smoothing,
+// produces its residual.  1: k_pcg_update_start_node (the update of the flexible PCG + the second phase of q = K p + the start of the
+// cycle's pre-smoothing on level 0); 2: k_sym_gather_start_node (second phase of the increment product in front of a post-smoothing,
 // symmetric-storage levels) -- both repeat the arithmetic of the passes they replace bit for bit; 4: the same in the epilogue of
 // k_spmv on full-storage levels (rounds x + c z as one multiply-add: not the same bits).  Default 3: measured on the 4M-triangle
 // panel, with the one-lane-per-node vector kernels the fused passes take as long as the passes they replace (147 against 65 + 81
@@ -1030,7 +1027,7 @@ struct Cycle {
     int rc = FEMSHELL_OK;
     const int fuse = fuse_mask();
     const int k_mask = k_cycle_mask();
-    // level 0: the caller's kernel (k_pcg_update_start) has taken the first step of the pre-smoothing already -- d in L.d, x = d
+    // level 0: the caller's kernel (k_pcg_update_start_node) has taken the first step of the pre-smoothing already -- d in L.d, x = d
     bool pre_started0 = false;
 
     bool dist(int l) const { return H.levels[(size_t)l]->dist; }
@@ -1077,24 +1074,21 @@ struct Cycle {
     {
         if (overlap(l)) {
             const int32_t *order = H.levels[(size_t)l]->order.p;
-            overlapped(l, x, [&](int b, int n) { (void)launch_spmv_span(A, x, y, nullptr, gate, order, b, n, 0, st); });
+            overlapped(l, x, [&](int b, int n) { launch_spmv_sym_phase1(A, x, y, nullptr, gate, st, SpmvSpan{order, b, n}, has_lowp(A)); });
             return;
         }
         halo(l, x);
-        launch_spmv_direct(A, x, y, nullptr, gate, st, has_lowp(A));
+        launch_spmv_sym_phase1(A, x, y, nullptr, gate, st, SpmvSpan(), has_lowp(A));
     }
     void full_product(int l, const DeviceMatrix &A, double *x, double *y, const SpmvEpilogue &e)
     {
         if (overlap(l)) {
             const int32_t *order = H.levels[(size_t)l]->order.p;
-            overlapped(l, x, [&](int b, int n) { launch_spmv_epilogue_span(A, x, y, e, order, b, n, gate, st); });
+            overlapped(l, x, [&](int b, int n) { launch_spmv(A, x, y, e, gate, st, SpmvSpan{order, b, n}); });
             return;
         }
         halo(l, x);
-        if (e.d_out != nullptr && e.start) launch_spmv_start(A, x, e.base_vec, y, e.d_out, e.xsol, e.c, gate, st);
-        else if (e.d_out != nullptr) launch_spmv_cheb(A, x, e.base_vec, y, e.d_out, e.xsol, e.a, e.c, gate, st);
-        else if (e.base_vec != nullptr) launch_spmv_axpy(A, x, y, e.base_vec, e.sign, gate, st);
-        else launch_spmv(A, x, y, nullptr, gate, st);
+        launch_spmv(A, x, y, e, gate, st);
     }
     // y = K x on level 0 of a row-partitioned context: the halo exchange beside the interior slices (symmetric storage with
     // defer: the direct part only, the consumer collects the transposed products)
@@ -1124,7 +1118,10 @@ struct Cycle {
             return;
         }
         halo(l, x);
-        launch_spmv_axpy(A, x, out, b, -1.0, gate, st);
+        SpmvEpilogue e;
+        e.base_vec = b;
+        e.sign = -1.0;
+        launch_spmv(A, x, out, e, gate, st);
     }
 
     // (r_given: the residual of x, where the caller has it -- in L.r or a vector of its own, never L.q or L.d)
@@ -1176,7 +1173,7 @@ struct Cycle {
                 std::swap(d_cur, d_next);
             } else {
                 halo(l, L.d.p);
-                launch_spmv(amg_level_matrix(c, l), L.d.p, L.q.p, nullptr, gate, st);
+                launch_spmv(amg_level_matrix(c, l), L.d.p, L.q.p, SpmvEpilogue(), gate, st);
                 launch_cheb_step(A, rcur, L.q.p, L.r.p, L.d.p, x, L.cheb_a[k], L.cheb_c[k], gate, st);
                 patch(l, L.r.p, L.cheb_c[k], L.d.p, false, x);
             }
@@ -1277,10 +1274,10 @@ struct Cycle {
         if (dist(l)) {
             halo(l, rf); // (R = P^T reaches the rows of the neighbours' nodes along the cut)
             if (N.dist) {
-                launch_spmv(L.R.dm, rf, N.b.p, nullptr, gate, st);
+                launch_spmv(L.R.dm, rf, N.b.p, SpmvEpilogue(), gate, st);
             } else {
                 // the rank's rows of the restricted residual, all-gathered into the replicated level
-                launch_spmv(L.R.dm, rf, L.bown.p, nullptr, gate, st);
+                launch_spmv(L.R.dm, rf, L.bown.p, SpmvEpilogue(), gate, st);
                 if (N.part_begin.size() + 1 != N.part.size()) { // (once per hierarchy, not per restriction)
                     N.part_begin.assign(N.part.begin(), N.part.end() - 1);
                     N.part_end.assign(N.part.begin() + 1, N.part.end());
@@ -1289,7 +1286,7 @@ struct Cycle {
                 if (!rc && !comm_gather_rows(c->comm, L.bown.p, N.b.p, N.part_begin, N.part_end, st, &e)) rc = set_err(FEMSHELL_ERR_COMM, e);
             }
         } else {
-            launch_spmv(L.R.dm, rf, N.b.p, nullptr, gate, st);
+            launch_spmv(L.R.dm, rf, N.b.p, SpmvEpilogue(), gate, st);
         }
         const bool next_is_coarsest = (size_t)l + 2 == H.levels.size();
         if (H.opt.cycle == FEMSHELL_CYCLE_K && !next_is_coarsest && ((k_mask >> (l + 1)) & 1)) kcycle(l + 1);
@@ -1300,13 +1297,19 @@ struct Cycle {
             // and the residual the post-smoothing starts from is the restricted one minus A e
             const DeviceMatrix &A = L.smooth_ready ? L.smooth_dm : amg_level_matrix(c, l);
             const bool e32 = A.symmetric && has_lowp(A) && A.vec32 == 2;
-            launch_spmv_axpy_keep(L.P.dm, N.x.p, x, x, 1.0, L.d.p, e32, gate, st);
+            SpmvEpilogue keep;
+            keep.base_vec = x;
+            keep.prod_out = L.d.p;
+            keep.prod_float = e32 ? 1 : 0;
+            launch_spmv(L.P.dm, N.x.p, x, keep, gate, st);
             double *d_started = nullptr;
             const double *r2 = residual_minus_product(l, rf, L.d.p, x, &d_started);
             smooth(l, b, x, false, r2, d_started);
             return;
         }
-        launch_spmv_axpy(L.P.dm, N.x.p, x, x, 1.0, gate, st); // x += P x_c
+        SpmvEpilogue add;
+        add.base_vec = x;
+        launch_spmv(L.P.dm, N.x.p, x, add, gate, st); // x += P x_c
         smooth(l, b, x, false);
     }
 
@@ -1449,7 +1452,7 @@ static int squared_norm(femshell_ctx *c, const double *a, int64_t n6, double *ou
 // with one pass.  femshell_pc_options::refine_passes passes at most (default 1; 0 = off).  A pass stops on the drop of its
 // own right-hand side, whatever the residual tolerance of the solve: ||e|| / ||x|| of the pass is the displacement error of
 // the iterate before it (manufactured solutions at 4M triangles: 4.8e-8 estimated, 4.8e-8 true) and the pass leaves about
-// that times its drop -- it runs until that product, with the ||e_k|| so far, is a fifth of rtol (kernels.hip: kRefineTarget;
+// that times its drop -- it runs until that product, with the ||e_k|| so far, is a fifth of rtol (cg_kernels.hip: kRefineTarget;
 // 1e-4 flat with FEMSHELL_REFINE_ADAPTIVE=0); passes after the first run while the product exceeds rtol.
 // *true_rr_out = ||b - K x||^2 (double-double) of the returned iterate.
 int cg_amg(femshell_ctx *c, const CgVectors &v0, double rtol, int32_t max_it, double *true_rr_out, double *rec_rr_out, const double *x0)
@@ -1508,7 +1511,7 @@ int cg_amg(femshell_ctx *c, const CgVectors &v0, double rtol, int32_t max_it, do
             launch_residual_dd(m, c->xacc.p, v0.b, c->rres.p, st);
             v.b = c->rres.p;
             if (adaptive_pass) {
-                // ||x||^2 of the iterate this pass corrects, for the pass's own stopping rule (kernels.hip: kRefineTarget)
+                // ||x||^2 of the iterate this pass corrects, for the pass's own stopping rule (cg_kernels.hip: kRefineTarget)
                 double xx = 0.0;
                 rc = squared_norm(c, c->xacc.p, n6, &xx);
                 if (rc) return rc;
@@ -1548,7 +1551,7 @@ int cg_amg(femshell_ctx *c, const CgVectors &v0, double rtol, int32_t max_it, do
         poll.next_check = it + 1;
         bool finished = false;
         // FEMSHELL_AMG_FUSE bit 0: the update kernel also finishes q = K p (second phase of the symmetric-storage product) and
-        // takes the first step of the cycle's pre-smoothing on the new residual (k_pcg_update_start: three passes become one)
+        // takes the first step of the cycle's pre-smoothing on the new residual (k_pcg_update_start_node: three passes become one)
         AmgLevel &L0 = *c->amg->levels[0];
         const bool fused_update = (fuse_mask() & 1) != 0 && c->amg->levels.size() > 1;
         const DeviceMatrix &S0 = L0.smooth_ready ? L0.smooth_dm : m;
@@ -1557,8 +1560,8 @@ int cg_amg(femshell_ctx *c, const CgVectors &v0, double rtol, int32_t max_it, do
             int n_partials = 0;
             const bool defer = fused_update && m.symmetric != 0;
             if (c->comm.active()) rc = spmv_with_halo(c, v, v.p, v.q, v.partials, &n_partials, defer);
-            else if (defer) launch_spmv_direct(m, v.p, v.q, v.partials, v.s, st);
-            else launch_spmv(m, v.p, v.q, v.partials, v.s, st);
+            else if (defer) launch_spmv_sym_phase1(m, v.p, v.q, v.partials, v.s, st);
+            else launch_spmv(m, v.p, v.q, SpmvEpilogue(), v.s, st, SpmvSpan(), v.partials);
             if (rc) return rc;
             rc = scalar_step(c, v, 1, CG_PHASE_ALPHA, rtol, n_partials);
             if (rc) return rc;

@@ -1,7 +1,7 @@
 // api.cpp -- the C ABI of libfemshell (include/femshell.h): context, communication, mesh and the data on it, assembly, solve,
 // export and products.  Dynamics: api_dynamics.cpp; modal analysis: api_modal.cpp; measurement hooks: api_timing.cpp; node ids and
 // node vectors across the boundary: node_io.cpp.  The CG driver is cg_driver.cpp, the plan inspection entry points plan_api.cpp.
-// All arithmetic of the hot path runs in the kernels of kernels.hip; there is no CPU fallback anywhere in this library.
+// All arithmetic of the hot path runs in the kernels of the .hip files; there is no CPU fallback anywhere in this library.
 #include "api_internal.hpp"
 #include "reorder.hpp"
 
@@ -475,7 +475,7 @@ int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, fe
         launch_copy_x_to_p(m, v, st);
         rc = halo_exchange(c, v.p, st);
         if (rc) return rc;
-        launch_spmv(m, v.p, v.q, nullptr, nullptr, st);
+        launch_spmv(m, v.p, v.q, SpmvEpilogue(), nullptr, st);
         launch_cg_init(m, v, true, st);
         rc = scalar_step(c, v, 2, CG_PHASE_RESTART, rtol);
         if (rc) return rc;
@@ -1702,7 +1702,7 @@ int femshell_spmv(femshell_ctx *c, const double *x, double *y)
     ProductBuffers b;
     rc = b.upload(c, NodeOrder::caller, x);
     if (rc) return rc;
-    launch_spmv(c->dm, b.x.p, b.y.p, nullptr, nullptr, c->stream);
+    launch_spmv(c->dm, b.x.p, b.y.p, SpmvEpilogue(), nullptr, c->stream);
     FS_HIP(hipGetLastError());
     return download_node_block(c, NodeOrder::caller, 1, b.y.p, 0, y);
 }

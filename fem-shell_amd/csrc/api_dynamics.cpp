@@ -130,7 +130,7 @@ int femshell_dynamics_begin(femshell_ctx *c, const femshell_dynamics_options *op
         FS_HIP(hipMemcpyAsync(c->p.p, d.u[1].p, n6 * sizeof(double), hipMemcpyDeviceToDevice, st));
         rc = halo_exchange(c, c->p.p, st);
         if (rc) return rc;
-        launch_spmv(c->dm, c->p.p, c->q.p, nullptr, nullptr, st);
+        launch_spmv(c->dm, c->p.p, c->q.p, SpmvEpilogue(), nullptr, st);
     }
     if (v0) {
         rc = upload_node_block(c, NodeOrder::caller, 1, v0, d.v[1].p, n6, &stage_v);
@@ -229,7 +229,7 @@ int femshell_dynamics_energy(femshell_ctx *c, int32_t which, double out[2])
     FS_HIP(hipMemcpyAsync(c->p.p, d.u[i].p, (size_t)c->plan.n_pad * 6 * sizeof(double), hipMemcpyDeviceToDevice, st));
     rc = halo_exchange(c, c->p.p, st);
     if (rc) return rc;
-    launch_spmv(c->dm, c->p.p, c->q.p, nullptr, nullptr, st);
+    launch_spmv(c->dm, c->p.p, c->q.p, SpmvEpilogue(), nullptr, st);
     launch_newmark_energy(c->dm, c->mass.p, d.u[i].p, d.v[i].p, c->q.p, d.e_partials.p, d.e_sums.p, st);
     FS_HIP(hipGetLastError());
     if (c->comm.active()) {

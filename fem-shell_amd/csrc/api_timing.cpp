@@ -205,7 +205,7 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         FS_HIP(c->bp.zero(st));
         launch_cg_init(c->dm, v, false, st);                // x=0, r=b, z=M^-1 b, p=z
         launch_cg_scalar(c->dm, v, true, 2, CG_PHASE_INIT, 0.0, st);
-        launch_spmv(c->dm, v.p, v.q, v.partials, v.s, st);  // q = A p
+        launch_spmv(c->dm, v.p, v.q, SpmvEpilogue(), v.s, st, SpmvSpan(), v.partials);  // q = A p
         launch_cg_scalar(c->dm, v, true, 1, CG_PHASE_ALPHA, 0.0, st);
     }
     FS_HIP(hipStreamSynchronize(st));
@@ -233,8 +233,8 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
             // (as cg_classic runs them: with symmetric storage the SpMV is its first phase and the update kernel
             // collects the transposed products)
             if (which == FEMSHELL_KERNEL_SPMV) FS_HIP(hipEventRecord(c->ev0, st));
-            if (c->dm.symmetric) launch_spmv_direct(c->dm, v.p, v.q, v.partials, v.s, st);
-            else launch_spmv(c->dm, v.p, v.q, v.partials, v.s, st);
+            if (c->dm.symmetric) launch_spmv_sym_phase1(c->dm, v.p, v.q, v.partials, v.s, st);
+            else launch_spmv(c->dm, v.p, v.q, SpmvEpilogue(), v.s, st, SpmvSpan(), v.partials);
             if (which == FEMSHELL_KERNEL_SPMV) FS_HIP(hipEventRecord(c->ev1, st));
             launch_cg_scalar(c->dm, v, true, 1, CG_PHASE_ALPHA, 0.0, st);
             if (which == FEMSHELL_KERNEL_CG_UPDATE) FS_HIP(hipEventRecord(c->ev0, st));

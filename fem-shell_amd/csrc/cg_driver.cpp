@@ -28,7 +28,7 @@ int halo_exchange(femshell_ctx *c, double *p, hipStream_t st)
 // columns only; the slices with ghost columns follow once the halo has landed.  Returns the number of
 // partial sums written through *n_partials (0 = slice_grid).
 // (xin: input vector with ghost space, yout = K xin, partial sums of xin.yout from partials[0] on)
-// (defer_gather: symmetric storage, the caller's next kernel collects the transposed products -- k_cg_update<true>)
+// (defer_gather: symmetric storage, the caller's next kernel collects the transposed products -- k_cg_update_node<true>)
 int spmv_with_halo(femshell_ctx *c, const CgVectors &v, double *xin, double *yout, double *partials, int *n_partials,
                    bool defer_gather, const float *vals32, int vec32)
 {
@@ -42,8 +42,8 @@ int spmv_with_halo(femshell_ctx *c, const CgVectors &v, double *xin, double *you
     if (!c->halo_overlap) {
         int rc = halo_exchange(c, xin, st);
         if (rc) return rc;
-        if (defer_gather) launch_spmv_direct(dm, xin, yout, partials, v.s, st, lowp);
-        else launch_spmv(c->dm, xin, yout, partials, v.s, st);
+        if (defer_gather) launch_spmv_sym_phase1(dm, xin, yout, partials, v.s, st, SpmvSpan(), lowp);
+        else launch_spmv(c->dm, xin, yout, SpmvEpilogue(), v.s, st, SpmvSpan(), partials);
         return FEMSHELL_OK;
     }
     const Plan &pl = c->plan;
@@ -53,9 +53,15 @@ int spmv_with_halo(femshell_ctx *c, const CgVectors &v, double *xin, double *you
     if (rc) return rc;
     FS_HIP(hipEventRecord(c->ev_halo_done, c->halo_stream));
     const int ni = pl.n_interior_slices, nb = pl.n_slices - ni;
-    const int gi = launch_spmv_span(dm, xin, yout, partials, v.s, c->spmv_order.p, 0, ni, 0, st);
+    // the slices spmv_order[begin, begin + count); partial sums from part on.  Symmetric storage: the first phase only
+    auto span_product = [&](int begin, int count, double *part) {
+        const SpmvSpan span{c->spmv_order.p, begin, count};
+        return dm.symmetric ? launch_spmv_sym_phase1(dm, xin, yout, part, v.s, st, span, lowp)
+                            : launch_spmv(dm, xin, yout, SpmvEpilogue(), v.s, st, span, part);
+    };
+    const int gi = span_product(0, ni, partials);
     FS_HIP(hipStreamWaitEvent(st, c->ev_halo_done, 0));
-    const int gb = launch_spmv_span(dm, xin, yout, partials, v.s, c->spmv_order.p, ni, nb, gi, st);
+    const int gb = span_product(ni, nb, partials != nullptr ? partials + gi : nullptr);
     if (c->dm.symmetric && !defer_gather) launch_sym_gather(c->dm, yout, nullptr, 1.0, v.s, st); // all transposed products are in place
     *n_partials = gi + gb;
     return FEMSHELL_OK;
@@ -113,7 +119,7 @@ int cg_classic(femshell_ctx *c, const CgVectors &v, double rtol, int32_t max_it,
         launch_copy_x_to_p(m, v, st);
         rc = halo_exchange(c, v.p, st);
         if (rc) return rc;
-        launch_spmv(m, v.p, v.q, nullptr, nullptr, st);
+        launch_spmv(m, v.p, v.q, SpmvEpilogue(), nullptr, st);
         launch_cg_init(m, v, true, st);
         rc = scalar_step(c, v, 2, CG_PHASE_RESTART, rtol);
         if (rc) return rc;
@@ -146,7 +152,7 @@ int cg_single_reduction(femshell_ctx *c, const CgVectors &v, double rtol, int32_
     hipStream_t st = c->stream;
     const int G = slice_grid(m);
     double *spmv_partials = v.partials + 2 * (size_t)G; // third partial array
-    // FEMSHELL_CG_FOLD=0: the unfolded sequence (k_sym_gather pass, scalar step as a launch of its own) for A/B runs
+    // FEMSHELL_CG_FOLD=0: the unfolded sequence (k_sym_gather_node pass, scalar step as a launch of its own) for A/B runs
     const char *fold_env = getenv("FEMSHELL_CG_FOLD");
     const bool fold = !(fold_env && atoi(fold_env) == 0);
     const bool gather = fold && m.symmetric != 0; // the update kernel collects the transposed products of w = A z

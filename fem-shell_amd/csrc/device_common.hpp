@@ -1,4 +1,5 @@
-// device_common.hpp -- device helpers shared by the kernel translation units (kernels.hip, amg_kernels.hip):
+// device_common.hpp -- device helpers shared by the kernel translation units (kernels.hip, spmv_kernels.hip, cg_kernels.hip,
+// amg_kernels.hip, ...):
 // the XCD-aware slice walk, workgroup sums, the packed block-Jacobi inverse.
 #pragma once
 
@@ -74,17 +75,6 @@ __device__ __forceinline__ MinvRow load_minv(const DeviceMatrix &m, int sl, int 
     for (int j = 0; j < 6; j++) r.a[j] = mi[minv_word(i < j ? i : j, i < j ? j : i) * kSliceNodes];
     return r;
 }
-// the smoothers of the multigrid cycle: from the single-precision copy when the level has one
-__device__ __forceinline__ MinvRow load_minv_smoother(const DeviceMatrix &m, int sl, int t)
-{
-    if (m.minv32 == nullptr) return load_minv(m, sl, t);
-    const int n = t / 6, i = t % 6;
-    const float *mi = m.minv32 + (int64_t)sl * kMinvWords * kSliceNodes + n;
-    MinvRow r;
-#pragma unroll
-    for (int j = 0; j < 6; j++) r.a[j] = (double)mi[minv_word(i < j ? i : j, i < j ? j : i) * kSliceNodes];
-    return r;
-}
 __device__ __forceinline__ double apply_minv(const MinvRow &mr, int t, const double *rs)
 {
     const int nb = (t / 6) * 6;
@@ -92,32 +82,6 @@ __device__ __forceinline__ double apply_minv(const MinvRow &mr, int t, const dou
 #pragma unroll
     for (int j = 0; j < 6; j++) z += mr.a[j] * rs[nb + j];
     return z;
-}
-
-// Symmetric storage, second phase of a product for scalar row (node n, component j) of slice sl: acc + the transposed products
-// of the row's in-list, in the plan's fixed order (the loop of k_sym_gather / k_cg_update<true> / k_cheb_step<true>: the slot
-// indices of the first four entries together, then their products together -- one entry at a time is two dependent memory
-// round trips per entry; the order of the additions is the same).  kT32: the products were stored as floats (DeviceMatrix::vec32)
-template <bool kT32> __device__ __forceinline__ double gather_transposed(const DeviceMatrix &m, int sl, int n, int j, double acc)
-{
-    const float *tf = reinterpret_cast<const float *>(m.tbuf);
-    const int Wi = m.in_width[sl];
-    const int64_t ib = m.in_base[sl];
-    int32_t slot4[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) slot4[k] = (k < Wi) ? m.gat_slots[ib + (int64_t)k * kSliceNodes + n] : -1;
-    double t4[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        t4[k] = slot4[k] < 0 ? 0.0 : (kT32 ? (double)tf[(int64_t)slot4[k] * 6 + j] : m.tbuf[(int64_t)slot4[k] * 6 + j]);
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-        if (slot4[k] >= 0) acc += t4[k];
-    for (int k = 4; k < Wi; k++) {
-        const int32_t slot = m.gat_slots[ib + (int64_t)k * kSliceNodes + n];
-        if (slot >= 0) acc += kT32 ? (double)tf[(int64_t)slot * 6 + j] : m.tbuf[(int64_t)slot * 6 + j];
-    }
-    return acc;
 }
 
 // ---- one lane per NODE (round 5) ---------------------------------------------------------------------------------------
@@ -177,7 +141,8 @@ __device__ __forceinline__ void node_minv_apply(const double mv[kMinvWords], con
     }
 }
 // symmetric storage, second phase of a product for the six rows of node n of slice sl: acc += the transposed products of the
-// node's in-list in the plan's fixed order (per row the additions of gather_transposed); two entries' loads in flight together
+// node's in-list in the plan's fixed order (per row the additions of k_cgcg_update<true>, entry after entry); two entries' loads
+// in flight together.  kT32: the products were stored as floats (DeviceMatrix::vec32)
 template <bool kT32> __device__ __forceinline__ void node_gather(const DeviceMatrix &m, int sl, int n, double acc[6])
 {
     const int Wi = m.in_width[sl];
@@ -204,5 +169,11 @@ template <bool kT32> __device__ __forceinline__ void node_gather(const DeviceMat
 //  partial-line stores the counters show -- 312 MB written where 240 MB are due -- are not what bounds these kernels.)
 // the slices a 64-lane workgroup of a node kernel walks: pairs of slices, one per half-wave (the walk of k_spmv_sym)
 __host__ __device__ __forceinline__ int node_pairs(int n_slices) { return (n_slices + 1) >> 1; }
+// workgroups of a node kernel: 64 lanes = two slices; never more than the per-slice kernels of the same matrix launch
+inline int node_grid(const DeviceMatrix &m)
+{
+    const int g = 8 * ((node_pairs(m.n_slices) + 7) / 8), cap = slice_grid(m);
+    return g < cap ? g : cap;
+}
 
 } // namespace femshell

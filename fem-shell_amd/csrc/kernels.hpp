@@ -1,4 +1,5 @@
-// kernels.hpp -- host-callable launchers of the gfx950 kernels (defined in kernels.hip).
+// kernels.hpp -- host-callable launchers of the gfx950 kernels: assembly (kernels.hip), sparse products (spmv_kernels.hip),
+// conjugate gradients (cg_kernels.hip), structural dynamics (dynamics_kernels.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -49,7 +50,7 @@ struct DeviceMatrix {
     const float *vals32 = nullptr;      // the same in single precision (smoothing products of the multigrid cycle only)
     // ... and what such a product (symmetric storage) keeps in single precision besides: 1 = its results -- the direct part
     // y and the transposed products in tbuf, six floats where the FP64 product writes six doubles, in the same buffers --,
-    // 2 = its input vector as well.  The arithmetic stays FP64.  k_cheb_start / k_cheb_step / k_sym_gather are told the
+    // 2 = its input vector as well.  The arithmetic stays FP64.  k_cheb_start_node / k_cheb_step_node / k_sym_gather_node are told the
     // same number (amg_solve.cpp Cycle::smooth).
     int32_t vec32 = 0;
     const double *rhs_loads = nullptr;  // n_pad x 6 nodal loads and
@@ -188,70 +189,69 @@ void launch_element_matrices(const DeviceMatrix &m, const MatConst &mc, int32_t 
 void launch_element_product(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const double *x, const double *xp,
                             const double *sub, double *y, bool rhs, hipStream_t st);
 
-// y = K x; when partials != nullptr also partials[wg] = sum over the workgroup's rows of x*y
-// (s != nullptr: no-op once s->done != 0)
-void launch_spmv(const DeviceMatrix &m, const double *x, double *y, double *partials, const CgScalars *s,
-                 hipStream_t st);
-// y = base_vec + sign * K x (base_vec may be y itself): residuals b - K x and prolongations x + P x_c of the
-// multigrid cycle; K may be rectangular (x indexed by the block columns, y and base_vec by the block rows)
-// One Chebyshev step of the smoother in D^-1 A on a full-storage operator, fused with its product (multigrid levels that
-// are bound by the latency between launches): r_out = r_in - A d_in; d_out = a d_in + c D^-1 r_out; x += d_out.
-// d_out must not be d_in (other workgroups still read d_in); r_out may be r_in.
-void launch_spmv_cheb(const DeviceMatrix &m, const double *d_in, const double *r_in, double *r_out, double *d_out, double *x,
-                      double a, double c, const CgScalars *s, hipStream_t st);
-// The residual in front of a post-smoothing and the smoothing's FIRST step in one launch (full storage): r_out = r_in - A v_in;
-// d_out = inv_theta D^-1 r_out; x += d_out  (d_out must not be v_in; r_out may be r_in)
-void launch_spmv_start(const DeviceMatrix &m, const double *v_in, const double *r_in, double *r_out, double *d_out, double *x,
-                       double inv_theta, const CgScalars *s, hipStream_t st);
-void launch_spmv_axpy(const DeviceMatrix &m, const double *x, double *y, const double *base_vec, double sign,
-                      const CgScalars *s, hipStream_t st);
-// full storage only: the same, and the product itself (K x, without the base vector) into prod_out -- as floats in that buffer
-// when prod_float (the coarse correction P x_c, which the cycle adds to its iterate and then multiplies with the level operator)
-void launch_spmv_axpy_keep(const DeviceMatrix &m, const double *x, double *y, const double *base_vec, double sign, double *prod_out,
-                           bool prod_float, const CgScalars *s, hipStream_t st);
-// symmetric storage only: second phase of a product whose first phase ran through launch_spmv_span (the transposed
-// products of all slices must be in place): y = base_vec + sign * (y + sum of the row's transposed products)
+// ---- sparse products (spmv_kernels.hip) ----
+// What a product does with its result besides storing it: what the callers fill and what k_spmv receives.
+struct SpmvEpilogue {
+    // y = base_vec + sign * K x (nullptr: y = K x): residuals b - K x and prolongations x + P x_c of the multigrid cycle; on full
+    // storage base_vec may be y itself
+    const double *base_vec = nullptr;
+    double sign = 1.0;
+    // full storage only -- one Chebyshev step of the smoother in D^-1 A fused with its product (multigrid levels that are bound by
+    // the latency between launches), x the direction d_in, base_vec the residual r_in with sign -1, y the new residual r_out:
+    // d_out = a d_in + c D^-1 r_out; xsol += d_out.  d_out must not be x (other workgroups still read it); y may be base_vec.
+    // start != 0: the FIRST step of a smoothing instead, x the vector the residual is taken of: d_out = c D^-1 r_out (c = 1 / theta);
+    // xsol += d_out -- or xsol = d_out from a zero guess (start == 2)
+    double *d_out = nullptr, *xsol = nullptr;
+    double a = 0.0, c = 0.0;
+    int start = 0;
+    // full storage only: the product itself, K x without the base vector, is stored as well -- as floats in that buffer when
+    // prod_float (the coarse correction P x_c, which the cycle adds to its iterate and then multiplies with the level operator)
+    double *prod_out = nullptr;
+    int prod_float = 0;
+};
+// the slices a launch works on: order[begin, begin + count) -- the interior / boundary halves of a product whose halo exchange runs
+// beside the interior half -- or, by default (count < 0), all of them in their own order.  A span of count 0 launches nothing.
+struct SpmvSpan {
+    const int32_t *order = nullptr;
+    int begin = 0, count = -1;
+    bool all() const { return count < 0; }
+};
+// y = K x with epilogue e; partials != nullptr: also partials[wg] = sum over the workgroup's rows of x * (K x), the p.Ap of CG.
+// (s != nullptr: no-op once s->done != 0.)  K may be rectangular (x indexed by the block columns, y and base_vec by the block rows).
+// Over all slices: symmetric storage runs both phases (launch_spmv_sym_phase1 + launch_sym_gather); full-storage operators with
+// narrow rows (FEMSHELL_SPMV_NODE_WIDTH) that come with a base vector or a kept product go through k_spmv_node; k_spmv otherwise.
+// Over a span: full storage only, k_spmv.  Returns the number of partial sums a launch with partials writes (0: nothing launched,
+// or k_spmv_node, which writes none); -1, having launched nothing, for a Chebyshev step or a kept product on symmetric storage,
+// whose second phase has no such epilogue.
+int launch_spmv(const DeviceMatrix &m, const double *x, double *y, const SpmvEpilogue &e, const CgScalars *s, hipStream_t st,
+                const SpmvSpan &span = SpmvSpan(), double *partials = nullptr);
+// symmetric storage: first phase of y = K x only (direct part of y, transposed products into m.tbuf, fused x.Kx sums).  The caller
+// runs launch_sym_gather once every span is through, or a kernel that collects the transposed products itself (k_cg_update_node<true>,
+// k_cheb_step_node<true, *>, ...).  single_precision_values: a smoothing product of the multigrid cycle on m.vals32, storing what
+// m.vec32 says in single precision.  Returns the number of partial sums written.
+int launch_spmv_sym_phase1(const DeviceMatrix &m, const double *x, double *y, double *partials, const CgScalars *s, hipStream_t st,
+                           const SpmvSpan &span = SpmvSpan(), bool single_precision_values = false);
+// symmetric storage: second phase of a product whose transposed products are all in place:
+// y = base_vec + sign * (y + sum of the row's transposed products)
 // (q32: y and the transposed products come from a smoothing product that stored them in single precision -- DeviceMatrix::vec32 --
 //  and the result goes to `out`, FP64, which may be base_vec)
 void launch_sym_gather(const DeviceMatrix &m, double *y, const double *base_vec, double sign, const CgScalars *s, hipStream_t st,
                        bool q32 = false, double *out = nullptr);
 // r = b - K x with double-double products and row sums (accurate residual for the residual replacement; r != x)
 void launch_residual_dd(const DeviceMatrix &m, const double *x, const double *b, double *r, hipStream_t st);
-// what a full-storage product does with its result besides storing it (the epilogues of launch_spmv_axpy / _cheb / _start /
-// _axpy_keep as one description), for launch_spmv_epilogue_span
-struct SpmvEpilogue {
-    const double *base_vec = nullptr; // y = base_vec + sign * K x (nullptr: y = K x)
-    double sign = 1.0;
-    double *d_out = nullptr, *xsol = nullptr; // Chebyshev step: d_out = a x + c D^-1 y, xsol += d_out (start != 0: the first step)
-    double a = 0.0, c = 0.0;
-    int start = 0;
-    double *prod_out = nullptr;       // K x itself as well (as floats: prod_float)
-    bool prod_float = false;
-};
-// the product with such an epilogue over the slices order[begin, begin + count) only
-void launch_spmv_epilogue_span(const DeviceMatrix &m, const double *x, double *y, const SpmvEpilogue &e, const int32_t *order, int begin,
-                               int count, const CgScalars *s, hipStream_t st);
-// the same over the slices order[begin, begin+count) only (interior / boundary halves of an overlapped
-// halo exchange); the partial sums go to partials[partial_offset ...]; returns the number written
-int launch_spmv_span(const DeviceMatrix &m, const double *x, double *y, double *partials, const CgScalars *s,
-                     const int32_t *order, int begin, int count, int partial_offset, hipStream_t st);
+// dst = (float)src
+void launch_to_f32(const double *src, float *dst, int64_t n, hipStream_t st);
 
+// ---- conjugate gradients (cg_kernels.hip) ----
 // CG steps; every kernel is a no-op once s->done != 0
 // restart = false: x=0, r=b;  restart = true: x kept, r = b - q (q = K x computed by the caller);
 // then z = M^-1 r, p = z, partial sums of r.z and (b.b | r.r)
 void launch_cg_init(const DeviceMatrix &m, const CgVectors &v, bool restart, hipStream_t st);
 // p[owned rows] = x (to run q = K x through the SpMV kernel, whose input carries the ghost entries)
 void launch_copy_x_to_p(const DeviceMatrix &m, const CgVectors &v, hipStream_t st);
-// x,r,z + partial r.z, r.r.  gather (symmetric storage): v.q holds the direct part of K p only (launch_spmv_direct or
-// spans without launch_sym_gather); the kernel adds the transposed products of each row's in-list itself
+// x += alpha p, r -= alpha q, z = M^-1 r + partial sums of r.z, r.r.  gather (symmetric storage): v.q holds the direct part of
+// K p only (launch_spmv_sym_phase1); the kernel adds the transposed products of each row's in-list itself
 void launch_cg_update(const DeviceMatrix &m, const CgVectors &v, hipStream_t st, bool gather = false);
-// symmetric storage: first phase of y = K x only (direct part of y, transposed products into m.tbuf, fused x.Kx sums)
-void launch_spmv_direct(const DeviceMatrix &m, const double *x, double *y, double *partials, const CgScalars *s, hipStream_t st,
-                        bool single_precision_values = false);
-// dst = (float)src
-void launch_to_f32(const double *src, float *dst, int64_t n, hipStream_t st);
-// v rounded to `sig` (< 24) significant bits in place: FEMSHELL_AMG_SMOOTH_SIGBITS, an experiment knob
-void launch_round_sig(float *v, int64_t n, int sig, hipStream_t st);
 
 void launch_cg_direction(const DeviceMatrix &m, const CgVectors &v, hipStream_t st); // p = z + beta p
 // single-workgroup scalar step: optional reduction of `nsums` partial arrays into s->red, then the
@@ -273,7 +273,7 @@ void launch_cgcg_init(const DeviceMatrix &m, const CgVectors &v, hipStream_t st)
 // rows add the transposed products of their in-lists
 void launch_cgcg_update(const DeviceMatrix &m, const CgVectors &v, hipStream_t st, int step = -1, bool gather = false);
 
-// ---- structural dynamics (femshell_dynamics_*): lumped mass and the vector kernels of a Newmark step.  One lane per node, 48
+// ---- structural dynamics (dynamics_kernels.hip; femshell_dynamics_*): lumped mass and the vector kernels of a Newmark step.  One lane per node, 48
 // bytes per node and vector, no LDS, no barriers; every kernel is row-local (owned rows of the rank).
 struct NewmarkCoef {
     double a0, a1, a2, a3, a4, a5; // include/femshell.h

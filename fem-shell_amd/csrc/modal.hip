@@ -1,6 +1,6 @@
 // modal.hip -- gfx950 kernels of the modal analysis (femshell_modes, modal.hpp): K times a block of vectors with symmetric
 // storage, Gram matrices of two blocks, the Rayleigh-Ritz rotation, block residuals, block-Jacobi on a block, start vectors.
-// All FP64, HBM-bound streaming kernels like those of kernels.hip; no atomics, no device-side waiting, every loop bounded by plan
+// All FP64, HBM-bound streaming kernels like those of spmv_kernels.hip; no atomics, no device-side waiting, every loop bounded by plan
 // data or by an argument.
 #include "modal.hpp"
 #include "plan.hpp"
@@ -12,7 +12,7 @@ namespace femshell {
 
 typedef double v2d __attribute__((ext_vector_type(2)));
 
-// the 18 words (jp, i) of block slot k, non-temporal (kernels.hip load_block_words: wd[jp * 6 + i] = columns 2jp, 2jp+1 of row i;
+// the 18 words (jp, i) of block slot k, non-temporal (spmv_kernels.hip load_block_words: wd[jp * 6 + i] = columns 2jp, 2jp+1 of row i;
 // kDiag: only the words of the upper triangle, the others stay unset)
 // v: the 16-byte words of m.vals; slot = slot_base + k * 32 + n, so word e of the block lies at (slot_base + k * 32) * 18 + e * 32 + n
 template <bool kDiag> __device__ __forceinline__ void load_block_words_nt(const v2d *v, int64_t slot, int n, v2d wd[18])
@@ -210,7 +210,7 @@ void block_product(const DeviceMatrix &m, const double *X, double *Y, int64_t ld
         return;
     }
     // full storage: the existing product, column by column
-    for (int j = 0; j < n_cols; j++) launch_spmv(m, X + (int64_t)j * ld, Y + (int64_t)j * ld, nullptr, nullptr, st);
+    for (int j = 0; j < n_cols; j++) launch_spmv(m, X + (int64_t)j * ld, Y + (int64_t)j * ld, SpmvEpilogue(), nullptr, st);
 }
 
 // =====================================================================================

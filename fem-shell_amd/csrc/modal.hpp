@@ -22,7 +22,7 @@ constexpr int kSpmmMaxCols = 4;   // columns one pass of the fused block product
 // for the lane's own row and as K_ac^T for row c (k_spmv_sym's mapping: a wave per slice pair, a lane per node row).  A block of
 // n_cols columns runs ceil(n_cols / 4) passes of 4 columns and a narrower one for the tail.  tbuf: kSpmmMaxCols planes of
 // `plane` = total_slots * 6 doubles for the transposed products that leave their slice (those that stay go through LDS).
-// Per column the additions are those of k_spmv_sym + k_sym_gather in their order: column j of Y is bitwise launch_spmv's.
+// Per column the additions are those of k_spmv_sym + k_sym_gather_node in their order: column j of Y is bitwise launch_spmv's.
 // Returns false, having launched nothing, when m is not in symmetric storage.
 bool launch_spmm_sym(const DeviceMatrix &m, const double *X, double *Y, int64_t ld, int n_cols, double *tbuf, int64_t plane, hipStream_t st);
 // columns one pass takes with this operator: 4 unless the in-slice products of four columns exceed the LDS of a workgroup

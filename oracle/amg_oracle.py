@@ -631,7 +631,7 @@ def kcycle_solve(levels, li, rc):
 def flexible_pcg(A, b, M, rtol=1e-10, max_it=1000, pass_of=None):
     """beta = z.(r - r_old) / r_old.z_old = -alpha z.q / rz_old; stops at ||r|| <= rtol ||b||.
     pass_of = (||x||^2 of the iterate this solve corrects, tolerance of the whole solve): the stopping rule of a refinement pass
-    (csrc/kernels.hip kRefineTarget) -- the drop asked of the residual is 0.2 tol ||x|| / ||e_k||, within [1e-6, 1e-2]."""
+    (csrc/cg_kernels.hip kRefineTarget) -- the drop asked of the residual is 0.2 tol ||x|| / ||e_k||, within [1e-6, 1e-2]."""
     x = np.zeros_like(b)
     r = b.copy()
     bb = b @ b
@@ -698,7 +698,7 @@ def solve(A, b, levels, kcycle=True, rtol=1e-10, max_it=1000, refine_passes=0, a
         if nr == 0.0 or len(hist) >= max_it or (k >= 1 and est <= rtol):
             break
         # the correction needs about four digits, not the full tolerance again: as many as put the estimate of what it leaves,
-        # ||e|| / ||x|| x its drop, at a fifth of the tolerance (csrc/kernels.hip: kRefineDrop, kRefineTarget)
+        # ||e|| / ||x|| x its drop, at a fifth of the tolerance (csrc/cg_kernels.hip: kRefineDrop, kRefineTarget)
         e, h = flexible_pcg(A, r, M, 1.0e-4, max_it - len(hist), pass_of=(x @ x, rtol) if adaptive else None)
         hist = hist + [v * nr / nb for v in h]
         est = np.linalg.norm(e) / np.linalg.norm(x) * (h[-1] if h else 1.0)

@@ -1,5 +1,5 @@
 """One multigrid cycle (femshell_pc_apply) in a process of its own, for the kernel choices a process reads once
-(FEMSHELL_NODE_KERNELS, FEMSHELL_SPMV_NODE_WIDTH, FEMSHELL_SPMV_CHUNK): tests/test_gpu_cycle.py starts it with the knob in the
+(FEMSHELL_SPMV_NODE_WIDTH, FEMSHELL_SPMV_CHUNK): tests/test_gpu_cycle.py starts it with the knob in the
 environment.  python -m tests.helpers.cycle_worker OUT.npz -- writes the cycle of the 48 x 48 panel (FP64 levels, K cycle) on the
 random and the load vector, and its errors against the reference built from this process's own exports."""
 import sys

@@ -173,7 +173,7 @@ def test_sliced_ell_image_of_a_level_operator(diag_first):
 
 def test_symmetric_storage_image_of_a_coarse_operator():
     """Coarse level operators are stored like K: diagonal + upper blocks, and per row the list of stored blocks that act on
-    it through their transpose.  Numpy model of the two phases of k_spmv_sym / k_sym_gather on the packed arrays against
+    it through their transpose.  Numpy model of the two phases of k_spmv_sym / k_sym_gather_node on the packed arrays against
     the full product."""
     ensure_built()
     m, dm, rp, ci, vals, F = _problem("panel")

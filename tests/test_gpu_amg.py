@@ -133,11 +133,11 @@ def test_single_precision_smoothing_products_leave_the_solution_alone(monkeypatc
 @pytest.mark.parametrize("f32,vec", [("0", "0"), ("3", "2"), ("3", "1"), ("1", "2")])
 def test_fused_smoother_starts_give_the_same_bits_as_the_separate_passes(monkeypatch, f32, vec):
     """FEMSHELL_AMG_FUSE (csrc/amg_solve.cpp): the first step of every Chebyshev smoothing runs in the epilogue of the kernel
-    that produces its residual -- k_pcg_update_start on level 0 (bit 0), k_sym_gather_start in front of the post-smoothing of a
-    symmetric-storage level (bit 1), the epilogue of k_spmv on a full-storage level (bit 2) -- instead of a k_cheb_start pass
+    that produces its residual -- k_pcg_update_start_node on level 0 (bit 0), k_sym_gather_start_node in front of the post-smoothing of a
+    symmetric-storage level (bit 1), the epilogue of k_spmv on a full-storage level (bit 2) -- instead of a k_cheb_start_node pass
     of its own.  The first two repeat the expressions of the kernels they replace: solution and iteration count are those of
     the unfused sequence bit for bit, on FP64 levels and on levels with single-precision copies.  The epilogue of k_spmv rounds
-    x + c z differently from k_cheb_start (a contracted multiply-add): same iterations, solution equal to rounding."""
+    x + c z differently from k_cheb_start_node (a contracted multiply-add): same iterations, solution equal to rounding."""
     m, mat = _make("roof", 64)
     monkeypatch.setenv("FEMSHELL_AMG_SMOOTH_F32", f32)
     monkeypatch.setenv("FEMSHELL_AMG_VEC_F32", vec)

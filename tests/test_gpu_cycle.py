@@ -224,8 +224,8 @@ def test_coarsest_solve_host_and_device_fp64_and_float(monkeypatch, device_min, 
 
 
 def test_fused_starts_give_the_bits_of_the_separate_passes(monkeypatch):
-    """FEMSHELL_AMG_FUSE bit 1 (k_sym_gather_start, symmetric-storage levels) repeats the arithmetic of k_sym_gather + k_cheb_start
-    bit for bit (csrc/amg_solve.cpp fuse_mask); bit 0 (k_pcg_update_start) is not on pc_apply's path.  Bit 2 (the epilogue of
+    """FEMSHELL_AMG_FUSE bit 1 (k_sym_gather_start_node, symmetric-storage levels) repeats the arithmetic of k_sym_gather_node + k_cheb_start_node
+    bit for bit (csrc/amg_solve.cpp fuse_mask); bit 0 (k_pcg_update_start_node) is not on pc_apply's path.  Bit 2 (the epilogue of
     k_spmv on full-storage levels) rounds x + c z as one multiply-add: the reference's tolerance, not the same bits."""
     monkeypatch.setenv("FEMSHELL_AMG_COARSE_SYM", "1")
     for mode, vec in (("0", "0"), ("3", "2")):
@@ -256,12 +256,12 @@ def _worker(tmp_path, name, env):
 
 
 def test_kernel_choices_a_process_reads_once(tmp_path):
-    """FEMSHELL_NODE_KERNELS, FEMSHELL_SPMV_NODE_WIDTH and FEMSHELL_SPMV_CHUNK are read once per process: each setting runs in a
+    """FEMSHELL_SPMV_NODE_WIDTH and FEMSHELL_SPMV_CHUNK are read once per process: each setting runs in a
     child process (tests/helpers/cycle_worker.py) and is held to the reference there.  k_spmv_node sums every row in the order
-    k_spmv does -- 'same bits' (csrc/kernels.hip) --: width 0 (never k_spmv_node) and 1000 (every full-storage product) against the
+    k_spmv does -- 'same bits' (csrc/spmv_kernels.hip) --: width 0 (never k_spmv_node) and 1000 (every full-storage product) against the
     default give the same z."""
     base = _worker(tmp_path, "default", {})
-    runs = {"nodek0": {"FEMSHELL_NODE_KERNELS": "0"}, "width0": {"FEMSHELL_SPMV_NODE_WIDTH": "0"},
+    runs = {"width0": {"FEMSHELL_SPMV_NODE_WIDTH": "0"},
             "width1000": {"FEMSHELL_SPMV_NODE_WIDTH": "1000"}, "chunk1": {"FEMSHELL_SPMV_CHUNK": "1"},
             "chunk2": {"FEMSHELL_SPMV_CHUNK": "2"}, "chunk4": {"FEMSHELL_SPMV_CHUNK": "4"}}
     for name, env in [("default", {})] + list(runs.items()):
