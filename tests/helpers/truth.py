@@ -136,22 +136,54 @@ def family_errors(fx, fam, K, K_moved=None, elements=None):
 # ------------------------------------------------------------------ the device's matrices
 
 KERNELS = {"k_assemble": "0", "k_assemble_pipe": "2"}  # FEMSHELL_ASM_PIPE: 0 two-phase, 2 pipelined wherever it can run
-# (kernel, FEMSHELL_SYMMETRIC, one section equal to the context's material)
-PATHS = [("k_element_matrices", None, False)] + [(k, s, sec) for sec in (False, True) for k in KERNELS for s in ("1", "0")]
+PRODUCT = "k_element_product"  # the matrix-free product (reactions, prescribed right-hand side): neither variable reaches it
+# (kernel, FEMSHELL_SYMMETRIC, sections): sections False: none; True: one section equal to the context's material; "own": every
+# element has a section with its own material, under a context whose material (OWN_CONTEXT) is none of theirs
+PATHS = ([("k_element_matrices", None, False)] + [(k, s, sec) for sec in (False, True) for k in KERNELS for s in ("1", "0")]
+         + [(PRODUCT, None, False), (PRODUCT, None, True)])
+OWN_PATHS = [("k_element_matrices", None, "own")] + [(k, s, "own") for k in KERNELS for s in ("1", "0")] + [(PRODUCT, None, "own")]
+OWN_FAMILIES = ("T3", "T6", "T7", "Q4")  # more than one material under one value of the flags
+OWN_CONTEXT = (0.25, 1.0, 1.0)  # (nu, E, t) of an "own" context: no element of the fixture has this nu, this E or this t
 MIN_ELEMENTS = 40  # a group is repeated up to this many elements: more than one slice of 32 nodes, lanes beyond the first
 
 
 def path_id(path):
     kernel, symmetric, sectioned = path
-    return kernel + ("" if symmetric is None else ("-sym" if symmetric == "1" else "-full")) + ("-sections" if sectioned else "")
+    return (kernel + ("" if symmetric is None else ("-sym" if symmetric == "1" else "-full"))
+            + ("-own" if sectioned == "own" else ("-sections" if sectioned else "")))
 
 
-def groups_of(fx, fam, elements=None):
-    """The family's elements by (nu, E, t, flags): a context has one material and one set of flags."""
+def groups_of(fx, fam, elements=None, own=False):
+    """The family's elements by (nu, E, t, flags): a context has one material and one set of flags.  own: by the flags alone,
+    under the material OWN_CONTEXT (the elements bring their materials along as sections)."""
     out = {}
     for e in (range(PER_FAMILY) if elements is None else elements):
-        out.setdefault(material_of(fx, fam, e), []).append(e)
+        m = material_of(fx, fam, e)
+        out.setdefault(OWN_CONTEXT + m[3:] if own else m, []).append(e)
     return out
+
+
+def isolated_mesh(tri_xyz=None, quad_xyz=None, reps=1):
+    """(xyz, tri, quad) of `reps` copies of the triangles tri_xyz (m, 3, 3) and quadrilaterals quad_xyz (m, 4, 3), every element
+    with nodes of its own; copy r of triangle k is triangle r * m + k, and likewise for the quadrilaterals."""
+    tri_xyz = np.zeros((0, 3, 3)) if tri_xyz is None else np.asarray(tri_xyz, dtype=np.float64).reshape(-1, 3, 3)
+    quad_xyz = np.zeros((0, 4, 3)) if quad_xyz is None else np.asarray(quad_xyz, dtype=np.float64).reshape(-1, 4, 3)
+    nt, nq = len(tri_xyz), len(quad_xyz)
+    xyz = np.concatenate([np.tile(tri_xyz, (reps, 1, 1)).reshape(-1, 3), np.tile(quad_xyz, (reps, 1, 1)).reshape(-1, 3)])
+    tri = np.arange(3 * nt * reps, dtype=np.int32).reshape(-1, 3)
+    quad = (3 * nt * reps + np.arange(4 * nq * reps, dtype=np.int32)).reshape(-1, 4)
+    return xyz, tri, quad
+
+
+def section_table(mats):
+    """The distinct (nu, E, t) of `mats` in the order of their first appearance, and every entry's row of that table."""
+    rows, index = [], []
+    for m in mats:
+        m = tuple(float(v) for v in m[:3])
+        if m not in rows:
+            rows.append(m)
+        index.append(rows.index(m))
+    return np.array(rows, dtype=np.float64).reshape(-1, 3), np.array(index, dtype=np.int32)
 
 
 def element_blocks(rowptr, colidx, vals, conn):
@@ -166,29 +198,63 @@ def element_blocks(rowptr, colidx, vals, conn):
     return K
 
 
-def device_matrices(pkg, setenv, path, material, tri_xyz=None, quad_xyz=None):
-    """Element matrices (node-major, global axes) of triangles tri_xyz (m, 3, 3) and quadrilaterals quad_xyz (m, 4, 3) of one
-    material through one device path; every element gets nodes of its own, so that after assembly every block of K holds
-    exactly one contribution; no Dirichlet nodes, no loads.  Returns (list for the triangles, list for the quadrilaterals)."""
+def probe_vector(n_nodes, conn_list, i, a):
+    """(n_nodes, 6): 1 at dof a of local node i of every element that has such a node, 0 elsewhere"""
+    x = np.zeros((n_nodes, 6))
+    x[[c[i] for c in conn_list if len(c) > i], a] = 1.0
+    return x
+
+
+def probe_element_matrices(product, n_nodes, conn_list):
+    """The matrices of elements that share no node with another, node-major (as element_blocks gives them), read back through
+    `product`, a function x (6 n_nodes,) -> K x: the product with probe_vector(i, a) is column (i, a) of every element's matrix at
+    once, 18 products for triangles, 24 where the mesh has a quadrilateral (a triangle has no local node 3 and ignores those).
+    Exact: every entry is one K_ab * 1 plus exact zeros, in a row with one contributing element.  Both triangles of a matrix are
+    read independently of each other."""
+    conn_list = [np.asarray(c, dtype=np.int64) for c in conn_list]
+    assert len(np.unique(np.concatenate(conn_list))) == sum(len(c) for c in conn_list), "the elements share nodes"
+    K = [np.zeros((6 * len(c), 6 * len(c))) for c in conn_list]
+    for i in range(max(len(c) for c in conn_list)):
+        for a in range(6):
+            y = np.asarray(product(probe_vector(n_nodes, conn_list, i, a).ravel()), dtype=np.float64).reshape(n_nodes, 6)
+            for k, c in enumerate(conn_list):
+                if len(c) > i:
+                    K[k][:, 6 * i + a] = y[c].ravel()
+    return K
+
+
+def device_matrices(pkg, setenv, path, material, tri_xyz=None, quad_xyz=None, tri_mat=None, quad_mat=None, reached=None):
+    """Element matrices (node-major, global axes) of triangles tri_xyz (m, 3, 3) and quadrilaterals quad_xyz (m, 4, 3) through
+    one device path, under a context of `material` = (nu, E, t, flags); every element gets nodes of its own, so that after
+    assembly every block of K holds exactly one contribution, and a product reads one element per row; no Dirichlet nodes, no
+    loads.  On an "own" path tri_mat / quad_mat give every element its (nu, E, t), which it gets as a section.  Returns (list for
+    the triangles, list for the quadrilaterals), each entry the list of the copies of one element.  reached: a list that gets
+    (the plan has quadrilaterals, sections are set) of a product path, the instantiation of k_element_product it launches."""
     kernel, symmetric, sectioned = path
     nu, E, t, flags = material
-    tri_xyz = np.zeros((0, 3, 3)) if tri_xyz is None else np.asarray(tri_xyz)
-    quad_xyz = np.zeros((0, 4, 3)) if quad_xyz is None else np.asarray(quad_xyz)
-    nt, nq = len(tri_xyz), len(quad_xyz)
+    nt, nq = (0 if tri_xyz is None else len(tri_xyz)), (0 if quad_xyz is None else len(quad_xyz))
     reps = -(-MIN_ELEMENTS // (nt + nq))
-    xyz = np.concatenate([np.tile(tri_xyz, (reps, 1, 1)).reshape(-1, 3), np.tile(quad_xyz, (reps, 1, 1)).reshape(-1, 3)])
-    tri = np.arange(3 * nt * reps, dtype=np.int32).reshape(-1, 3)
-    quad = (3 * nt * reps + np.arange(4 * nq * reps, dtype=np.int32)).reshape(-1, 4)
+    xyz, tri, quad = isolated_mesh(tri_xyz, quad_xyz, reps)
     if symmetric is not None:
         setenv("FEMSHELL_SYMMETRIC", symmetric)
         setenv("FEMSHELL_ASM_PIPE", KERNELS[kernel])  # (both read per femshell_set_mesh)
     fs = pkg.FemShell(nu, E, t, flags=flags)
     fs.set_mesh(xyz, tri, quad)
-    if sectioned:
+    if sectioned == "own":
+        table, index = section_table(list(tri_mat or []) + list(quad_mat or []))
+        assert len(index) == nt + nq and len(set(map(tuple, table))) > 1, table
+        assert all(table[:, k].tolist().count(material[k]) == 0 for k in range(3)), "the context's material is an element's"
+        fs.set_sections(table, np.tile(index[:nt], reps), np.tile(index[nt:], reps))
+    elif sectioned:
         fs.set_sections([[nu, E, t]], np.zeros(len(tri), np.int32), np.zeros(len(quad), np.int32))
     if kernel == "k_element_matrices":
         Kt = [to_node_major(k, 3) for k in fs.element_matrices(0, len(tri))] if nt else []
         Kq = [to_node_major(k, 4) for k in fs.element_matrices(len(tri), len(quad))] if nq else []
+    elif kernel == PRODUCT:
+        if reached is not None:
+            reached.append((pkg.build_plan(xyz, tri, quad)["n_lquad"] > 0, bool(sectioned)))
+        K = probe_element_matrices(fs.element_product, len(xyz), list(tri) + list(quad))
+        Kt, Kq = K[:len(tri)], K[len(tri):]
     else:
         assert fs.assembly_kernel() == kernel
         fs.assemble()
@@ -201,16 +267,21 @@ def device_matrices(pkg, setenv, path, material, tri_xyz=None, quad_xyz=None):
             [[Kq[r * nq + k] for r in range(reps)] for k in range(nq)])
 
 
-def device_family_errors(pkg, setenv, fx, fam, path, elements=None):
-    """metric -> the device's worst error over the family (all copies of every element) through one path"""
+def family_worst(fx, fam, path, evaluate, elements=None):
+    """metric -> the worst error over the family (all copies of every element) of the matrices that
+    evaluate(path, material, tri_xyz, quad_xyz, tri_mat, quad_mat) returns (as device_matrices does), context by context"""
     tri_fam = nodes_of(fam) == 3
+    own = path[2] == "own"
     names = metrics_of(fam) + (["spurious"] if fam in CLASSWISE else [])
     worst = {m: 0.0 for m in names}
-    for material, els in groups_of(fx, fam, elements).items():
+    for material, els in groups_of(fx, fam, elements, own).items():
         X = [fx[fam + "_xyz"][e] for e in els]
+        mats = [material_of(fx, fam, e)[:3] for e in els] if own else None
         if fam in FRAME:  # the moved copies ride in the same mesh, behind the originals
             X = X + [fx[fam + "_xyz_moved"][e] for e in els]
-        Kt, Kq = device_matrices(pkg, setenv, path, material, X if tri_fam else None, None if tri_fam else X)
+            mats = mats + mats if own else None
+        Kt, Kq = evaluate(path, material, X if tri_fam else None, None if tri_fam else X, mats if tri_fam else None,
+                          None if tri_fam else mats)
         K = Kt if tri_fam else Kq
         for r in range(len(K[0])):
             err = family_errors(fx, fam, [K[k][r] for k in range(len(els))],
@@ -218,6 +289,13 @@ def device_family_errors(pkg, setenv, fx, fam, path, elements=None):
             for m in names:
                 worst[m] = max(worst[m], float(err[m].max()))
     return worst
+
+
+def device_family_errors(pkg, setenv, fx, fam, path, elements=None, reached=None):
+    """metric -> the device's worst error over the family (all copies of every element) through one path"""
+    def evaluate(path, material, tri_xyz, quad_xyz, tri_mat, quad_mat):
+        return device_matrices(pkg, setenv, path, material, tri_xyz, quad_xyz, tri_mat, quad_mat, reached)
+    return family_worst(fx, fam, path, evaluate, elements)
 
 
 def check(fx, fam, worst, factors=None):

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.helpers import meshes, oracle, oracle_quad, truth
+from tests.helpers import meshes, oracle, oracle_quad, prescribed as pr, truth
 
 FX = dict(truth.load())
 
@@ -99,3 +99,131 @@ def test_quad_material_matrices_round_to_the_fp64_ones():
     mat = oracle.material(0.3, 2.1e5, 0.37)
     for a, b in zip(oracle.material_matrices(mat), oracle_quad.material_matrices(mat)):
         assert np.abs(a - b).max() <= 4 * truth.EPS * np.abs(b).max()
+
+
+# ------------------------------------------------------------------ the helpers of the GPU test, with the FP64 oracle as the device
+
+def test_paths_of_the_gpu_test():
+    """the product paths reach the four instantiations of k_element_product (triangles or quadrilaterals in the plan, sections
+    set or not; the GPU test asserts each from its mesh), and the "own" paths run where they can tell one material from another"""
+    product = [p for p in truth.PATHS + truth.OWN_PATHS if p[0] == truth.PRODUCT]
+    assert {(fam[0] == "Q", bool(p[2])) for fam in truth.FAMILIES for p in product if p[2] != "own"} == \
+        {(False, False), (False, True), (True, False), (True, True)}
+    ids = [truth.path_id(p) for p in truth.PATHS + truth.OWN_PATHS]
+    assert len(set(ids)) == len(ids) and "k_element_product" in ids and "k_element_product-sections" in ids
+    assert [i for i in ids if i.endswith("-own")] == ["k_element_matrices-own", "k_assemble-sym-own", "k_assemble-full-own",
+                                                     "k_assemble_pipe-sym-own", "k_assemble_pipe-full-own", "k_element_product-own"]
+    for fam in truth.FAMILIES:
+        by_flags = {}
+        for m in truth.groups_of(FX, fam):
+            by_flags.setdefault(m[3], set()).add(m[:3])
+        assert (fam in truth.OWN_FAMILIES) == any(len(v) > 1 for v in by_flags.values()), fam
+        for k in range(3):  # the material of an "own" context is no element's, in no component
+            assert truth.OWN_CONTEXT[k] not in FX[fam + "_mat"][:, k]
+    for fam in truth.OWN_FAMILIES:
+        (material, els), = truth.groups_of(FX, fam, own=True).items()
+        assert material == truth.OWN_CONTEXT + (3,) and els == list(range(truth.PER_FAMILY))
+
+
+def _dense_product(K, conn, n_nodes):
+    """x -> sum_e K_e x_e for node-major element matrices K_e on the nodes conn[e]"""
+    def product(x):
+        x = np.asarray(x, dtype=np.float64).reshape(n_nodes, 6)
+        y = np.zeros((n_nodes, 6))
+        for Ke, c in zip(K, conn):
+            y[c] += (Ke @ x[c].ravel()).reshape(-1, 6)
+        return y.ravel()
+    return product
+
+
+@pytest.mark.parametrize("kinds", ["triangles", "quadrilaterals", "mixed"])
+def test_probing_reads_the_element_matrices_back_exactly(kinds):
+    mat = oracle.material(*truth.material_of(FX, "T1", 0))
+    Xt = list(FX["T1_xyz"]) if kinds != "quadrilaterals" else None
+    Xq = list(FX["Q1_xyz"]) if kinds != "triangles" else None
+    xyz, tri, quad = truth.isolated_mesh(Xt, Xq, reps=2)
+    K_unc, _ = pr.matrices(xyz, tri, quad, mat, np.zeros(len(xyz), np.uint8))
+    calls = []
+
+    def product(x):
+        calls.append(1)
+        return oracle.spmv(*K_unc, x)
+
+    K = truth.probe_element_matrices(product, len(xyz), list(tri) + list(quad))
+    assert len(calls) == (18 if kinds == "triangles" else 24)
+    assert len(K) == len(tri) + len(quad) == 2 * truth.PER_FAMILY * (2 if kinds == "mixed" else 1)
+    for k, c in enumerate(tri):
+        np.testing.assert_array_equal(K[k], truth.to_node_major(oracle.element_tri3(xyz[c], mat), 3))
+    for k, c in enumerate(quad):
+        np.testing.assert_array_equal(K[len(tri) + k], truth.to_node_major(oracle.element_quad4(xyz[c], mat), 4))
+    # ... and what the assembly paths read from the blocks of K
+    for k, c in enumerate(list(tri) + list(quad)):
+        np.testing.assert_array_equal(K[k], truth.element_blocks(*K_unc, c))
+
+
+@pytest.mark.parametrize("planted", [1e-9, 0.0])
+def test_a_bending_error_the_product_test_accepts_is_over_the_budget(planted):
+    """The gap the product paths of the GPU test close: the bending entries of a thin flat triangle (T3, t = 1e-3) wrong by 1e-9
+    of themselves pass the bound of test_element_product_matches_the_oracle (1e-12 of a row scale that the membrane entries
+    make), and are over the bending budget; with nothing planted both pass."""
+    from tests import test_gpu_prescribed as product_test  # (its import builds the library where it is missing; no GPU)
+
+    e = int(np.flatnonzero(FX["T3_mat"][:, 2] == 1e-3)[0])
+    mat = oracle.material(*truth.material_of(FX, "T3", e))
+    xyz, tri, quad = truth.isolated_mesh([FX["T3_xyz"][e]])
+    K = truth.to_node_major(oracle.element_tri3(xyz, mat), 3)
+    K[truth.class_masks(3, int(FX["T3_normal"][e]))["bending"]] *= 1.0 + planted
+    product = _dense_product([K], tri, 3)
+    x = np.random.default_rng(7).uniform(-1.0, 1.0, 18)
+    K_unc, _ = pr.matrices(xyz, tri, quad, mat, np.zeros(3, np.uint8))
+    ratio = product_test.product_bound_ratio(product(x), oracle.spmv(*K_unc, x), K_unc, x)
+    print("planted %.0e: max |y - y_ref| / (1e-12 S_a) = %.2e" % (planted, ratio))
+    assert ratio <= 1.0
+    Kp = truth.probe_element_matrices(product, 3, tri)
+    worst = {m: float(v.max()) for m, v in truth.family_errors(FX, "T3", Kp, elements=[e]).items()}
+    over = [b[0] for b in truth.check(FX, "T3", worst)]
+    print("planted %.0e: over the budget %s, bending %.2e" % (planted, over, worst["bending"]))
+    if planted:  # (the whole-matrix norm may or may not see it: that depends on the element's size)
+        assert "bending" in over and "membrane" not in over and "drilling" not in over
+    else:
+        assert over == []
+
+
+def _oracle_own(bending_from_context):
+    """truth.family_worst's `evaluate` by the FP64 oracle for an "own" path: every element with its row of the section table;
+    bending_from_context: the bending entries scaled as if cp = E t^3 / 12 (1 - nu^2) were the context's"""
+    def cp(nu, E, t):
+        return E * t ** 3 / (12.0 * (1.0 - nu * nu))
+
+    def evaluate(path, material, tri_xyz, quad_xyz, tri_mat, quad_mat):
+        assert path[2] == "own" and material[:3] == truth.OWN_CONTEXT
+        X = list(tri_xyz or []) + list(quad_xyz or [])
+        table, index = truth.section_table(list(tri_mat or []) + list(quad_mat or []))
+        assert len(table) > 1 and len(index) == len(X)
+        out = []
+        for x, row in zip(X, index):
+            nodes = len(x)
+            m = oracle.material(*table[row], material[3])
+            K = truth.to_node_major((oracle.element_tri3 if nodes == 3 else oracle.element_quad4)(x, m), nodes)
+            if bending_from_context:
+                normal = int(np.argmax(np.abs(np.cross(x[1] - x[0], x[2] - x[0]))))
+                K[truth.class_masks(nodes, normal)["bending"]] *= cp(*material[:3]) / cp(*table[row])
+            out.append([K])
+        nt = 0 if tri_xyz is None else len(tri_xyz)
+        return out[:nt], out[nt:]
+    return evaluate
+
+
+def test_a_section_that_is_ignored_is_over_the_budget():
+    """Q4 in one mesh with a section per thickness: evaluated by the oracle it is within the budgets (they are made of the
+    oracle's own errors: the reference alone stays within them); with the bending constant of the context instead of the
+    section's it is not."""
+    path = ("k_element_matrices", None, "own")
+    right = truth.family_worst(FX, "Q4", path, _oracle_own(False))
+    assert truth.check(FX, "Q4", right) == []
+    for m in truth.metrics_of("Q4"):  # (the oracle through the helper's plumbing is the oracle of the fixture)
+        np.testing.assert_allclose(right[m], FX["Q4_err_" + m].max(), rtol=1e-9, atol=1e-30)
+    wrong = truth.family_worst(FX, "Q4", path, _oracle_own(True))
+    over = [b[0] for b in truth.check(FX, "Q4", wrong)]
+    print("bending constant of the context: over the budget", over, "bending %.2e" % wrong["bending"])
+    assert "bending" in over and "membrane" not in over and "drilling" not in over

@@ -19,7 +19,10 @@ def main():
     print("%-4s %-12s %-34s %10s %10s %8s %10s  %s" % ("fam", "metric", "path", "device", "oracle", "ratio", "bound", ""))
     over = 0
     for fam in truth.FAMILIES:
-        for path in truth.PATHS:
+        # (the "own" paths: the whole family in one mesh, a section per material, where the family has more than one)
+        for path in truth.PATHS + (truth.OWN_PATHS if fam in truth.OWN_FAMILIES else []):
+            for name in ("FEMSHELL_SYMMETRIC", "FEMSHELL_ASM_PIPE"):  # a path that sets neither runs under the defaults
+                os.environ.pop(name, None)
             worst = truth.device_family_errors(pkg, os.environ.__setitem__, fx, fam, path)
             for m in truth.metrics_of(fam):
                 o = float(fx["%s_err_%s" % (fam, m)].max())
