@@ -25,6 +25,7 @@ from .binding import (  # noqa: F401
     REORDER_RCM,
     build_library,
     comm_unique_id,
+    grid_cap,
     library_path,
     load_library,
     build_plan,

@@ -854,3 +854,11 @@ def reorder_host(kind, xyz, tri=None, quad=None):
     if rc:
         raise FemShellError(-1, "femshell_reorder_host: invalid mesh")
     return perm
+
+
+def grid_cap(text, fallback):
+    """The workgroup cap the library takes from the text of a grid knob (femshell_grid_cap; text None: not set).  CPU only."""
+    L = load_library()
+    L.femshell_grid_cap.argtypes = [C.c_char_p, C.c_int32]
+    L.femshell_grid_cap.restype = C.c_int32
+    return int(L.femshell_grid_cap(None if text is None else str(text).encode(), int(fallback)))

@@ -25,20 +25,15 @@ static_assert(kSliceNodes == 32 && kSliceRows == 192, "kernels assume 32-node sl
 
 static int assemble_grid(const DeviceMatrix &m)
 {
-    static const int cap = [] {
-        const char *e = getenv("FEMSHELL_ASM_GRID");
-        return e ? atoi(e) : 2048;
-    }();
+    static const int cap = grid_cap(getenv("FEMSHELL_ASM_GRID"), 2048); // (plan.hpp: a multiple of 8, at least 8)
     const int g = 8 * ((m.n_slices + 7) / 8);
     return g < cap ? g : cap;
 }
 
 int slice_grid(const DeviceMatrix &m)
 {
-    static const int cap = [] {
-        const char *e = getenv("FEMSHELL_SLICE_GRID"); // tuning knob
-        return e ? atoi(e) : 65536; // one slice per workgroup up to 2M node rows: best SpMV rate; more rows share workgroups
-    }();
+    // tuning knob; one slice per workgroup up to 2M node rows: best SpMV rate; more rows share workgroups
+    static const int cap = grid_cap(getenv("FEMSHELL_SLICE_GRID"), 65536);
     const int g = 8 * ((m.n_slices + 7) / 8);
     return g < cap ? g : cap;
 }
@@ -67,12 +62,10 @@ bool launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st, 
     if (sections && (!ds.table || !ds.slice_elem_section)) return false; // (nothing launched: the caller reports it)
     if (m.pipe) { // two workgroups per CU, b and b + G/2 on the same one: their roles complement each other
         static const int pipe_cap = [] { // two workgroups per CU of this device (FEMSHELL_ASM_PIPE_GRID overrides)
-            const char *e = getenv("FEMSHELL_ASM_PIPE_GRID");
-            if (e) return atoi(e);
             int dev = 0, cus = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
                 cus = 256;
-            return 8 * ((2 * cus + 7) / 8);
+            return grid_cap(getenv("FEMSHELL_ASM_PIPE_GRID"), 8 * ((2 * cus + 7) / 8));
         }();
         const int gp = g < pipe_cap ? g : pipe_cap;
         auto launch_pipe = [&](auto kernel) {

@@ -165,7 +165,7 @@ enum CgPhase : int {
                                 // correction equation down to the threshold CG_PHASE_FLEX_INIT derived from b
 };
 
-int slice_grid(const DeviceMatrix &m); // workgroups of the per-slice kernels (multiple of 8, at most 2560)
+int slice_grid(const DeviceMatrix &m); // workgroups of the per-slice kernels (8 * ceil(n_slices / 8), capped by FEMSHELL_SLICE_GRID through grid_cap of plan.hpp: a multiple of 8, at least 8, 65536 by default)
 
 // sections != nullptr: a context with shell sections (m.lds_* laid out for the sectioned records: assemble_lds_layout)
 // returns false, having launched nothing, when `sections` is given without its table or indices

@@ -5,6 +5,7 @@
 #include <sys/mman.h>
 
 #include <algorithm>
+#include <cerrno>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -255,6 +256,20 @@ bool default_symmetric_storage()
 {
     const char *e = getenv("FEMSHELL_SYMMETRIC");
     return !(e && atoi(e) == 0);
+}
+
+int grid_cap(const char *text, int fallback)
+{
+    long v = 0;
+    if (text) {
+        errno = 0;
+        char *end = nullptr;
+        v = strtol(text, &end, 10);
+        while (end != text && (*end == ' ' || *end == '\t' || *end == '\n')) end++;
+        if (end == text || *end != '\0' || errno != 0 || v > INT_MAX) v = 0;
+    }
+    if (v <= 0) v = fallback;
+    return v < 8 ? 8 : (int)(v & ~7L);
 }
 
 // Items of one slice (slot by slot, chunk 0 first: Plan::Item) into the lanes of the pipelined kernel's rounds: 192 lanes

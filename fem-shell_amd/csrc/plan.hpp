@@ -194,5 +194,11 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
 bool repack_assembly_items(Plan *plan, bool pipe, std::string *err);
 // the library's default storage: symmetric unless FEMSHELL_SYMMETRIC=0
 bool default_symmetric_storage();
+// Workgroup cap of a kernel that walks slices with SliceWalk (device_common.hpp), from the text of its tuning knob
+// (FEMSHELL_SLICE_GRID, FEMSHELL_ASM_GRID, FEMSHELL_ASM_PIPE_GRID).  The walk deals workgroups to 8 XCD groups and steps by
+// gridDim.x / 8: a grid that is no multiple of 8 visits slices twice and misses others, one below 8 steps by zero and never
+// ends.  So: the value rounded down to a multiple of 8, never less than 8; text that is no whole positive number (or absent)
+// gives fallback, held to the same rule.
+int grid_cap(const char *text, int fallback);
 
 } // namespace femshell

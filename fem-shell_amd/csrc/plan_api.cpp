@@ -37,6 +37,8 @@ int femshell_plan_create(int32_t n_nodes, const double *xyz, int32_t n_tri, cons
 
 void femshell_plan_destroy(femshell_plan *plan) { delete plan; }
 
+int32_t femshell_grid_cap(const char *text, int32_t fallback) { return grid_cap(text, fallback); }
+
 int femshell_plan_info(const femshell_plan *plan, int64_t *info)
 {
     if (!plan || !info) return set_err(FEMSHELL_ERR_INVALID, "femshell_plan_info: null argument");

@@ -128,6 +128,12 @@ int64_t femshell_amg_host_pack(int32_t n_rows, const int32_t *rowptr, const int3
 int femshell_reorder_host(int32_t kind, int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t *tri,
                           int32_t n_quad, const int32_t *quad, int32_t *perm_out);
 
+/* the workgroup cap the library takes from the text of FEMSHELL_SLICE_GRID, FEMSHELL_ASM_GRID or FEMSHELL_ASM_PIPE_GRID
+ * (text may be NULL: the variable is not set; fallback: the knob's default): rounded down to a multiple of 8 and never
+ * below 8 -- the slice walk of the kernels deals workgroups to 8 groups and steps by a eighth of the grid --; text that
+ * is no whole positive number gives the fallback (csrc/plan.hpp grid_cap) */
+int32_t femshell_grid_cap(const char *text, int32_t fallback);
+
 /* symmetric storage of a square operator (coarse multigrid levels): diagonal + upper blocks in the sliced ELL arrays and
  * the in-lists of the transposed products; returns the total slots, *in_total receives the in-list entries; arrays may
  * be NULL for a sizing call */

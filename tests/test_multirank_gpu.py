@@ -216,7 +216,12 @@ def test_multigrid_on_a_row_partitioned_context(world, kind, dist_min, tmp_path)
 
 @pytest.mark.parametrize("world,kind,dist_min", [(2, "panel", 100), (3, "cylinder", 60000), (4, "panel", 100)])
 def test_row_partitioned_hierarchy_follows_the_restatement(world, kind, dist_min, tmp_path):
-    """oracle/amg_oracle.py restates the rank-local aggregation (aggregate_by_rank); tentative prolongator, smoothing and
+    check_hierarchy_against_the_restatement(world, kind, dist_min, tmp_path)
+
+
+def check_hierarchy_against_the_restatement(world, kind, dist_min, tmp_path, extra_env=None):
+    """(extra_env: more environment for the ranks -- tests/test_gpu_slice_walk.py runs the same assertions under a small grid.)
+    oracle/amg_oracle.py restates the rank-local aggregation (aggregate_by_rank); tentative prolongator, smoothing and
     Galerkin product are the single-rank ones.  The ranks' rows of every level -- aggregates, P, the level operators -- put
     together equal the restatement's, level by level; so do the iteration count and the residual history; and the solution
     equals the oracle's refined direct solve of the oracle-assembled K up to the sensitivity of two FP64 assemblies."""
@@ -227,7 +232,7 @@ def test_row_partitioned_hierarchy_follows_the_restatement(world, kind, dist_min
     from tests.helpers import oracle
     from tests.helpers.multirank_worker import build_problem
 
-    env = {"FEMSHELL_AMG_DIST_MIN": str(dist_min), "FEMSHELL_TEST_AMG_EXPORT": "1", "FEMSHELL_TEST_EXPORT": "1"}
+    env = dict({"FEMSHELL_AMG_DIST_MIN": str(dist_min), "FEMSHELL_TEST_AMG_EXPORT": "1", "FEMSHELL_TEST_EXPORT": "1"}, **(extra_env or {}))
     ranks = sorted(run_ranks(world, kind, tmp_path, pc="amg", extra_env=env), key=lambda q: int(q["begin"]))
     m, mat = build_problem(kind)
     n = m.n_nodes

@@ -509,3 +509,76 @@ def test_node_normals_from_the_gather_lists_are_the_element_walks_bit_for_bit(me
     assert a.shape == b.shape and len(a) > 100
     np.testing.assert_array_equal(a, b)
     assert np.allclose(np.linalg.norm(a, axis=1), 1.0)
+
+
+# ---- the workgroup caps of the kernels that walk slices (csrc/plan.hpp grid_cap) --------------------------------------------------
+
+def slice_walk_visits(n_slices, grid):
+    """SliceWalk of csrc/device_common.hpp restated: how often the workgroups of a grid visit every slice.  A step of zero (a
+    workgroup that never leaves its loop) is reported as None."""
+    per, step = (n_slices + 7) >> 3, grid >> 3
+    seen = np.zeros(n_slices, dtype=np.int64)
+    for b in range(grid):
+        first = (b & 7) * per
+        last = min(first + per, n_slices)
+        s = first + (b >> 3)
+        if s < last and step == 0:
+            return None
+        while s < last:
+            seen[s] += 1
+            s += step
+    return seen
+
+
+def launched_grid(n_slices, cap):
+    return min(8 * ((n_slices + 7) // 8), cap)
+
+
+GRID_KNOB_TEXTS = ["-5", "0", "1", "7", "8", "9", "12", "20", "24", "65536", "garbage"]
+
+
+@pytest.mark.parametrize("fallback", [65536, 2048, 512])  # FEMSHELL_SLICE_GRID, FEMSHELL_ASM_GRID, FEMSHELL_ASM_PIPE_GRID (2 x 256 CUs)
+def test_grid_caps_are_multiples_of_eight_and_at_least_eight(fallback):
+    """FEMSHELL_SLICE_GRID, FEMSHELL_ASM_GRID and FEMSHELL_ASM_PIPE_GRID all pass through femshell_grid_cap: at least 8, a multiple
+    of 8, not above what was asked where that is 8 or more; no whole positive number: the default.  With every such cap the walk
+    visits every slice of 0 to 79 exactly once.
+
+    Before, the knobs went through as atoi(text), and min(8 * ceil(S / 8), atoi(text)) workgroups were launched.  That expression
+    evaluated here (never on a GPU) for S = 40: "1" and "7" give grids of 1 and 7 workgroups, step = grid >> 3 = 0 -- workgroup 0
+    has slice 0 in range and never leaves its loop; "12" gives 12 workgroups with step 1 -- workgroups 0 and 8 both walk slices
+    0..4 of group 0 (8 starts one further), groups 4 to 7 have one workgroup each: slices 1 to 4 are visited twice; "20" gives
+    step 2 with workgroups 0, 8, 16 on group 0 -- slices 2 and 4 twice.  Per-row results survive that, partial sums do not."""
+    for text in [None] + GRID_KNOB_TEXTS:
+        cap = pkg.grid_cap(text, fallback)
+        assert cap >= 8 and cap % 8 == 0, (text, cap)
+        try:
+            asked = int(text)
+        except (TypeError, ValueError):
+            asked = 0
+        if asked >= 8:
+            assert asked - 8 < cap <= asked, (text, cap)
+        elif asked >= 1:
+            assert cap == 8, (text, cap)
+        else:
+            assert cap == fallback, (text, cap)
+        for n_slices in range(80):
+            seen = slice_walk_visits(n_slices, launched_grid(n_slices, cap))
+            assert seen is not None and (seen == 1).all(), (text, cap, n_slices)
+    # text that only starts like a number is no number; blanks around one are
+    assert pkg.grid_cap("12abc", fallback) == fallback and pkg.grid_cap("", fallback) == fallback
+    assert pkg.grid_cap(" 16\n", fallback) == 16 and pkg.grid_cap("99999999999999999999", fallback) == fallback
+    # a default that is itself off the rule (an odd number of compute units) is held to it as well
+    assert pkg.grid_cap(None, 5) == 8 and pkg.grid_cap("junk", 2047) == 2040
+
+
+def test_the_unchecked_caps_of_before_broke_the_walk():
+    """The restated walk on the parent's arithmetic -- min(8 * ceil(S / 8), int(text)) workgroups -- for the caps the rule now
+    rounds: 1 and 7 never end, 12 and 20 visit slices twice (and 12 of 40 slices misses none but doubles four of group 0's)."""
+    for asked in (1, 7):
+        assert slice_walk_visits(40, launched_grid(40, asked)) is None
+    for asked in (12, 20):
+        seen = slice_walk_visits(40, launched_grid(40, asked))
+        assert seen.max() == 2, (asked, seen)
+    for asked in (8, 16, 24):
+        for n_slices in range(80):
+            assert (slice_walk_visits(n_slices, launched_grid(n_slices, asked)) == 1).all()
