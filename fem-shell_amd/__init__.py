@@ -16,6 +16,7 @@ from .binding import (  # noqa: F401
     KERNEL_CG_DIRECTION,
     KERNEL_CG_UPDATE,
     KERNEL_ELEMENT_PRODUCT,
+    KERNEL_ELEMENT_RESULTANTS,
     KERNEL_SPMV,
     REASSEMBLE_EACH_SOLVE,
     REF_DEFAULT,

@@ -19,6 +19,7 @@ KERNEL_ASSEMBLE, KERNEL_SPMV, KERNEL_CG_UPDATE, KERNEL_CG_DIRECTION = 0, 1, 2, 3
 KERNEL_LUMPED_MASS, KERNEL_MASS_SHIFT, KERNEL_NEWMARK_RHS, KERNEL_NEWMARK_UPDATE = 4, 5, 6, 7
 KERNEL_SPMM, KERNEL_GRAM, KERNEL_BLOCK_COMBINE = 8, 9, 10
 KERNEL_ELEMENT_PRODUCT = 11
+KERNEL_ELEMENT_RESULTANTS = 12
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -33,7 +34,7 @@ SYMBOLS = [
     "femshell_set_density", "femshell_lumped_mass", "femshell_dynamics_defaults", "femshell_dynamics_begin", "femshell_dynamics_step",
     "femshell_dynamics_accept", "femshell_dynamics_state", "femshell_dynamics_energy", "femshell_dynamics_end",
     "femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram",
-    "femshell_set_prescribed", "femshell_reactions", "femshell_element_product",
+    "femshell_set_prescribed", "femshell_reactions", "femshell_element_product", "femshell_element_resultants",
 ]
 
 
@@ -190,6 +191,7 @@ def load_library():
     L.femshell_set_prescribed.argtypes = [vp, C.c_int32, ip, dp]
     L.femshell_reactions.argtypes = [vp, dp, dp]
     L.femshell_element_product.argtypes = [vp, dp, dp]
+    L.femshell_element_resultants.argtypes = [vp, dp, dp]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -295,6 +297,15 @@ class FemShell:
         y = np.zeros_like(x)
         _check(self._L.femshell_element_product(self._h, _d(x), _d(y)))
         return y
+
+    def element_resultants(self, u=None):
+        """What the shell carries, (n_tri + n_quad, 14), the triangles of set_mesh in their order, then the quadrilaterals: membrane
+        force tensor N [0:6] and moment tensor M [6:12] in global axes (xx, yy, zz, xy, yz, zx), the von Mises stress at the top
+        [12] and the bottom [13] surface -- the element means by the element's own quadrature (femshell_element_resultants).
+        u None: the solution of the last solve, prescribed part included."""
+        out = np.zeros((self.n_tri + self.n_quad, 14))
+        _check(self._L.femshell_element_resultants(self._h, _d(self._node_vector(u, "u")), _d(out)))
+        return out
 
     def set_sections(self, sections, tri_section=None, quad_section=None):
         """Shell sections: `sections` is an (n, 3) array-like of (nu, E, thickness), tri_section / quad_section give every

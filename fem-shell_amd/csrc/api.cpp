@@ -1,5 +1,6 @@
 // api.cpp -- the C ABI of libfemshell (include/femshell.h): context, communication, mesh and the data on it, assembly, solve,
-// export and products.  Dynamics: api_dynamics.cpp; modal analysis: api_modal.cpp; measurement hooks: api_timing.cpp; node ids and
+// export and products.  Dynamics: api_dynamics.cpp; modal analysis: api_modal.cpp; element resultants: api_resultants.cpp;
+// measurement hooks: api_timing.cpp; node ids and
 // node vectors across the boundary: node_io.cpp.  The CG driver is cg_driver.cpp, the plan inspection entry points plan_api.cpp.
 // All arithmetic of the hot path runs in the kernels of the .hip files; there is no CPU fallback anywhere in this library.
 #include "api_internal.hpp"
@@ -270,7 +271,7 @@ int do_assemble(femshell_ctx *c, bool wait)
 
 // u_bar of the prescribed values and the Dirichlet set in force (femshell_set_prescribed): the entries at fixed dofs, zero
 // elsewhere, on the host and in HBM.  Single-rank contexts only: the owned rows are all rows.
-static int resolve_prescribed(femshell_ctx *c)
+int resolve_prescribed(femshell_ctx *c)
 {
     if (c->ubar_valid) return FEMSHELL_OK;
     const Plan &p = c->plan;

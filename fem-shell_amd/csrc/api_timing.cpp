@@ -175,6 +175,34 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
             *bytes_out = 24.0 * p.n_own + (16.0 + (c->have_sections ? 4.0 : 0.0)) * (double)p.slice_elem_nodes.size() / 4.0 + 96.0 * p.n_own;
         return FEMSHELL_OK;
     }
+    if (which == FEMSHELL_KERNEL_ELEMENT_RESULTANTS) {
+        // the element resultants of a hashed displacement vector, back to back between one event pair (rows in the local order: the
+        // host's part of femshell_element_resultants is not timed)
+        if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_time_kernel: the element resultants run on single-rank contexts");
+        hipStream_t st = c->stream;
+        const Plan &p = c->plan;
+        const int64_t ld = (int64_t)p.n_local_nodes() * 6;
+        DevBuf<double> S, R, thick;
+        FS_HIP(S.alloc((size_t)ld));
+        FS_HIP(S.zero(st));
+        FS_HIP(R.alloc(((size_t)p.n_ltri() + (size_t)p.n_lquad()) * 14));
+        const double *sec_t = nullptr;
+        rc = upload_section_thickness(c, &thick, &sec_t);
+        if (rc) return rc;
+        launch_modal_init(c->dm, nullptr, 1, S.p, ld, st);
+        FS_HIP(hipStreamSynchronize(st));
+        FS_HIP(hipEventRecord(c->ev0, st));
+        for (int32_t i = 0; i < reps; i++) launch_element_resultants(c->dm, c->mc, c->sections_or_null(), sec_t, S.p, nullptr, R.p, st);
+        FS_HIP(hipEventRecord(c->ev1, st));
+        FS_HIP(hipGetLastError());
+        rc = check_status(c, "femshell_time_kernel");
+        if (rc) return rc;
+        float ms = 0.f;
+        FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        *mean_ms_out = (double)ms / reps;
+        if (bytes_out) *bytes_out = bytes_element_resultants(c);
+        return FEMSHELL_OK;
+    }
     if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->matrix_valid) {
         rc = do_assemble(c);
         if (rc) return rc;

@@ -189,6 +189,15 @@ void launch_element_matrices(const DeviceMatrix &m, const MatConst &mc, int32_t 
 void launch_element_product(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const double *x, const double *xp,
                             const double *sub, double *y, bool rhs, hipStream_t st);
 
+// Element stress resultants and surface stresses (element_resultants.hip): out[(n_ltri + n_lquad)][14] in the LOCAL
+// element order (triangles, then quadrilaterals) -- membrane force tensor, moment tensor (global axes, xx yy zz xy yz zx) and the von
+// Mises stress at the top and the bottom surface, the element means by the element's own quadrature -- from u + up (each
+// (n_pad + n_ghost) x 6; up may be nullptr).  sec_t: the thickness of every section where `sections` is given (its table keeps
+// products only), nullptr otherwise.  One lane per element, no atomics: two launches give the same bits.  A degenerate element
+// writes zeros and reports kStatusDirect + its index through m.status.
+void launch_element_resultants(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const double *sec_t, const double *u,
+                               const double *up, double *out, hipStream_t st);
+
 // ---- sparse products (spmv_kernels.hip) ----
 // What a product does with its result besides storing it: what the callers fill and what k_spmv receives.
 struct SpmvEpilogue {

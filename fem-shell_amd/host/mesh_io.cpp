@@ -639,7 +639,8 @@ void write_meshgen_files(const MeshGenArgs &a, const std::string &name)
     }
 }
 
-void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::string &path, const std::vector<PointVectors> *point_vectors)
+void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::string &path, const std::vector<PointVectors> *point_vectors,
+               const std::vector<CellArray> *cell_arrays)
 {
     std::ofstream os(path);
     if (!os) throw std::runtime_error("cannot write " + path);
@@ -675,9 +676,38 @@ void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::stri
                 os << line;
             }
         }
+    const bool cells = cell_arrays && !cell_arrays->empty();
+    if (m.sections_in_use || cells) os << "CELL_DATA " << ne << "\n";
     if (m.sections_in_use) { // (runs with -sections / -section_ids only: everything above is the file of a run without)
-        os << "CELL_DATA " << ne << "\nSCALARS section int 1\nLOOKUP_TABLE default\n";
+        os << "SCALARS section int 1\nLOOKUP_TABLE default\n";
         for (long e = 0; e < ne; e++) os << m.tag_of((int32_t)e) << "\n";
+    }
+    if (cells) {
+        char word[40];
+        auto rows = [&](const CellArray &a) {
+            for (long e = 0; e < ne; e++)
+                for (int v = 0; v < a.components; v++) {
+                    snprintf(word, sizeof word, "%.17g%c", a.values[(size_t)e * (size_t)a.components + v], v + 1 < a.components ? ' ' : '\n');
+                    os << word;
+                }
+        };
+        int wide = 0;
+        for (const CellArray &a : *cell_arrays) {
+            if (a.components != 1) {
+                wide++;
+                continue;
+            }
+            os << "SCALARS " << a.name << " double 1\nLOOKUP_TABLE default\n";
+            rows(a);
+        }
+        if (wide) {
+            os << "FIELD cell_fields " << wide << "\n";
+            for (const CellArray &a : *cell_arrays) {
+                if (a.components == 1) continue;
+                os << a.name << " " << a.components << " " << ne << " double\n";
+                rows(a);
+            }
+        }
     }
 }
 

@@ -99,7 +99,15 @@ struct PointVectors {
     std::string name;
     std::vector<double> xyz; // n_nodes x 3
 };
-void write_vtk(const ShellMesh &m, const std::vector<double> &u6, const std::string &path, const std::vector<PointVectors> *point_vectors = nullptr);
+// cell_arrays: cell arrays of 1 or more components (the element resultants of FEM-shell -stress), one tuple per element in file order,
+// written with every digit: one component as SCALARS, more as arrays of a FIELD of the cell data
+struct CellArray {
+    std::string name;
+    int components = 1;
+    std::vector<double> values; // n_elements x components
+};
+void write_vtk(const ShellMesh &m, const std::vector<double> &u6, const std::string &path, const std::vector<PointVectors> *point_vectors = nullptr,
+               const std::vector<CellArray> *cell_arrays = nullptr);
 // <stem>.pvtu + <stem>_0.vtu: the VTK XML pair libMesh's VTKIO writes per time step of a serial coupled run
 // (fem-shell_precice.cpp:1552-1559); path must end in .pvtu
 void write_pvtu(const ShellMesh &m, const std::vector<double> &u6, const std::string &path);

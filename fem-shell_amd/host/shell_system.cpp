@@ -117,7 +117,10 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-modes_shift:\t shift S >= 0: solves with K + S M (with -modes; an unconstrained shell needs S > 0; default 0)\n"
             << "-prescribed:\t file of lines 'node u v w tx ty tz': prescribed displacements of the dofs the boundary ids fix (optional)\n"
             << "-reactions:\t writes <out>_reactions.txt, lines 'node rx ry rz mx my mz' of the nodes with a fixed dof and a line 'sum',\n"
-            << "\t and the point arrays reaction_f / reaction_m of <out>.vtk (optional)\n";
+            << "\t and the point arrays reaction_f / reaction_m of <out>.vtk (optional)\n"
+            << "-stress:\t writes <out>_stress.txt, a line per element with the membrane force tensor N, the moment tensor M (global axes,\n"
+            << "\t xx yy zz xy yz zx) and the von Mises stress at the top and the bottom surface (element means), and the cell arrays\n"
+            << "\t membrane_force, moment, von_mises_top, von_mises_bottom of <out>.vtk (optional)\n";
         return false;
     }
     bool failed = false;
@@ -302,6 +305,13 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             failed = true;
         }
     }
+    if (has_flag(argc, argv, "-stress")) {
+        p.stress = true;
+        if (has_flag(argc, argv, "-modes") || has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps")) {
+            err << "ERROR: -stress belongs to the static solve: not with -modes or the time stepping options -dt / -steps!\n";
+            failed = true;
+        }
+    }
 
     out << "Run program with parameters:"
         << " debug messages = " << (p.debug ? "true" : "false") << ", nu = " << p.nu << ", E = " << p.em
@@ -436,6 +446,7 @@ void ShellSystem::comm_init(const unsigned char id[128]) { check(femshell_comm_i
 void ShellSystem::set_mesh(const ShellMesh &m)
 {
     n_nodes_ = m.n_nodes();
+    n_elems_ = m.n_tri() + m.n_quad();
     solved_once_ = false;
     check(femshell_set_mesh(ctx_, m.n_nodes(), m.xyz.data(), m.n_tri(), m.tri.data(), m.n_quad(), m.quad.data()),
           "femshell_set_mesh");
@@ -464,6 +475,13 @@ std::vector<double> ShellSystem::reactions()
     std::vector<double> r((size_t)n_nodes_ * 6, 0.0);
     check(femshell_reactions(ctx_, nullptr, r.data()), "femshell_reactions");
     return r;
+}
+
+std::vector<double> ShellSystem::element_resultants()
+{
+    std::vector<double> s((size_t)n_elems_ * 14, 0.0);
+    check(femshell_element_resultants(ctx_, nullptr, s.data()), "femshell_element_resultants");
+    return s;
 }
 
 SectionTable read_sections(const Parameters &p, ShellMesh &mesh)
@@ -682,6 +700,7 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
             system.set_prescribed(p);
         }
         if (p.reactions && launch.world_size != 1) throw std::runtime_error("-reactions runs on one rank");
+        if (p.stress && launch.world_size != 1) throw std::runtime_error("-stress runs on one rank");
         clock.done("symbolic phase, boundary conditions, loads");
         if (p.modes_requested()) {
             // natural frequencies and mode shapes instead of a solve
@@ -827,9 +846,46 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
                 reaction_arrays.push_back(std::move(a));
             }
         }
+        std::vector<CellArray> stress_arrays;
+        if (p.stress) {
+            // what the shell carries: a line per element in the order of the mesh file (the cells of <out>.vtk); the library's rows
+            // are the triangles, then the quadrilaterals
+            const std::vector<double> s = system.element_resultants();
+            const std::string stem = p.isOutfileSet ? p.out_filename : std::string("out");
+            std::ofstream sf(stem + "_stress.txt");
+            if (!sf) throw std::runtime_error("cannot write " + stem + "_stress.txt");
+            sf << "# element Nxx Nyy Nzz Nxy Nyz Nzx Mxx Myy Mzz Mxy Myz Mzx von_mises_top von_mises_bottom\n"
+               << "# N: membrane force per length, M: moment per length (M = integral of sigma z dz), global axes; element means\n";
+            static const char *names[4] = {"membrane_force", "moment", "von_mises_top", "von_mises_bottom"};
+            static const int first[4] = {0, 6, 12, 13}, comps[4] = {6, 6, 1, 1};
+            const size_t ne = mesh.order.size();
+            for (int a = 0; a < 4; a++) {
+                CellArray c;
+                c.name = names[a];
+                c.components = comps[a];
+                c.values.resize(ne * (size_t)comps[a]);
+                stress_arrays.push_back(std::move(c));
+            }
+            double worst = 0.0;
+            char word[40];
+            for (size_t e = 0; e < ne; e++) {
+                const size_t row = mesh.order[e].first == 't' ? (size_t)mesh.order[e].second : (size_t)mesh.n_tri() + (size_t)mesh.order[e].second;
+                const double *q = &s[14 * row];
+                sf << e;
+                for (int v = 0; v < 14; v++) {
+                    snprintf(word, sizeof word, " %.15e", q[v]);
+                    sf << word;
+                }
+                sf << "\n";
+                for (int a = 0; a < 4; a++)
+                    for (int v = 0; v < comps[a]; v++) stress_arrays[(size_t)a].values[e * (size_t)comps[a] + v] = q[first[a] + v];
+                worst = std::max(worst, std::max(q[12], q[13]));
+            }
+            out << "Element resultants: largest surface von Mises stress = " << worst << ", in " << stem << "_stress.txt" << std::endl;
+        }
         if (p.isOutfileSet) {
             write_exodus(mesh, sols, p.out_filename + ".e"); // the reference's file (fem-shell.cpp:1249)
-            write_vtk(mesh, sols, p.out_filename + ".vtk", p.reactions ? &reaction_arrays : nullptr);
+            write_vtk(mesh, sols, p.out_filename + ".vtk", p.reactions ? &reaction_arrays : nullptr, p.stress ? &stress_arrays : nullptr);
             clock.done("output files");
         }
         out << "All done :)\n";

@@ -79,6 +79,12 @@ struct Parameters {
     std::vector<int> prescribed_lines;     // ... and its line number
     std::vector<double> prescribed_values; // ... and its six values
     bool reactions = false;
+    // element stress resultants and surface stresses (extension, stand-alone program only; the reference writes displacements, its
+    // thesis names the stresses as future work).  -stress: after the static solve writes <out>_stress.txt -- a '#' header, then a
+    // line "element Nxx Nyy Nzz Nxy Nyz Nzx Mxx Myy Mzz Mxy Myz Mzx vm_top vm_bottom" (%.15e) per element in the order of the mesh
+    // file -- and the cell arrays membrane_force, moment (6 components), von_mises_top, von_mises_bottom of <out>.vtk
+    // (femshell_element_resultants).
+    bool stress = false;
     bool prescribed_requested() const { return !prescribed_file.empty(); }
 };
 
@@ -149,6 +155,8 @@ class ShellSystem {
     void set_prescribed(const Parameters &p);
     // -reactions: r = K_unc u - loads of the last solve's solution, n_nodes x 6
     std::vector<double> reactions();
+    // -stress: the element resultants of the last solve's solution, (n_tri + n_quad) x 14, triangles then quadrilaterals
+    std::vector<double> element_resultants();
     // per node: the Dirichlet mask in force (what set_mesh derived from the boundary ids)
     const std::vector<uint8_t> &dirichlet_mask() const { return mask_; }
     // the assembly callback (SA:1160-1233); the name argument is checked like SA:1163
@@ -171,7 +179,7 @@ class ShellSystem {
   private:
     void choose_preconditioner(const Parameters &p);
     femshell_ctx *ctx_ = nullptr;
-    int n_nodes_ = 0, rank_ = 0;
+    int n_nodes_ = 0, n_elems_ = 0, rank_ = 0;
     bool solved_once_ = false; // later solves start from the solution before (libMesh's initial guess: ShellSystem::solve)
     std::vector<double> sols_;
     std::vector<uint8_t> mask_;

@@ -324,6 +324,25 @@ int femshell_get_solution(femshell_ctx *ctx, double *u_out);
  * Needs a mesh, not an assembled K.  Sums in a fixed order: two calls give the same bits, and the NULL form gives the bits of the
  * explicit one.  FEMSHELL_ERR_UNSUPPORTED on a row-partitioned context (world_size != 1). */
 int femshell_reactions(femshell_ctx *ctx, const double *u /* n_nodes x 6, or NULL */, double *r6_out /* n_nodes x 6 */);
+/* extends: the reference writes displacements only, and its thesis names the stresses as future work; this gives what the shell
+ * carries.  Per element 14 doubles, rows in the caller's order: its triangles, then its quadrilaterals (FEMSHELL_REORDER too):
+ *     [0..5]   membrane force tensor N (force per length), global axes, order xx, yy, zz, xy, yz, zx
+ *     [6..11]  moment tensor M (moment per length), global axes, same order
+ *     [12]     von Mises stress at the top surface (z = +t/2 along the element's local z axis), [13] at the bottom surface
+ * In the element frame (the one K is built with) N_loc = t Dm eps and M_loc = -Dp kappa, so that M = integral of sigma z dz, with
+ * eps = (u,x, v,y, u,y + v,x) and kappa = (w,xx, w,yy, 2 w,xy) the ELEMENT MEANS of the element's own strain operators by the
+ * quadrature its stiffness uses: TRI3 the constant CST strain and the mean of Specht's curvature over its three Gauss points (the
+ * same Y as the stiffness, FEMSHELL_REF_Y21 included), QUAD4 the det-J-weighted mean over the 2 x 2 Gauss points of the bilinear
+ * membrane strain and the DKQ curvature.  The tensors are R^T [[a_xx, a_xy, 0], [a_xy, a_yy, 0], [0, 0, 0]] R (rows of R: the
+ * local axes), which does not depend on the in-plane axes an element happens to choose.  sigma_top/bottom = N_loc / t +- 6 M_loc / t^2,
+ * von Mises in its plane-stress form; with sections t, Dm, Dp are the element's own.  The drilling rotation carries no resultant;
+ * Kirchhoff elements have no transverse shear.
+ * u: n_nodes x 6 in the caller's numbering, or NULL: the solution of the last solve, prescribed part included (taken where it
+ * lies in HBM).  Needs a mesh, not an assembled K.  No sums across elements: two calls give the same bits, and the NULL form gives
+ * the bits of the explicit one.  A degenerate element: FEMSHELL_ERR_MESH.  FEMSHELL_ERR_UNSUPPORTED on a row-partitioned context
+ * (world_size != 1); FEMSHELL_ERR_INVALID while dynamics is active, without a mesh, for the NULL form before any solve, for a
+ * non-finite u.  The context stays usable after every refusal. */
+int femshell_element_resultants(femshell_ctx *ctx, const double *u /* n_nodes x 6, or NULL */, double *out /* (n_tri + n_quad) x 14 */);
 /* The NEXT femshell_solve of this context starts from u0 (n_nodes x 6, the caller's numbering; every rank passes the whole vector
  * and keeps its own rows) instead of from zero; u0 == NULL: from the solution of the context's previous solve, where it lies in
  * HBM (no transfer).  Consumed by that solve; femshell_set_mesh forgets it.
@@ -511,7 +530,11 @@ typedef enum femshell_kernel {
     FEMSHELL_KERNEL_BLOCK_COMBINE = 10, /* 2c columns out of 3c */
     /* k_element_product (y = K_unc x, matrix-free) back to back on a hashed vector; needs a mesh only.  bytes_out: coordinates,
      * the node ids of the slices' element lists, x read, y written */
-    FEMSHELL_KERNEL_ELEMENT_PRODUCT = 11
+    FEMSHELL_KERNEL_ELEMENT_PRODUCT = 11,
+    /* k_element_resultants back to back on a hashed displacement vector; needs a mesh only.  bytes_out: 12 / 16 bytes of node ids
+     * and 112 bytes of output per element (4 more of a section index where the context has sections), coordinates and
+     * displacements (24 + 48 bytes) once per node */
+    FEMSHELL_KERNEL_ELEMENT_RESULTANTS = 12
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
