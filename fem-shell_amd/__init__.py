@@ -27,6 +27,8 @@ from .binding import (  # noqa: F401
     build_library,
     comm_unique_id,
     grid_cap,
+    knob_flag,
+    knob_long,
     library_path,
     load_library,
     build_plan,

@@ -873,3 +873,19 @@ def grid_cap(text, fallback):
     L.femshell_grid_cap.argtypes = [C.c_char_p, C.c_int32]
     L.femshell_grid_cap.restype = C.c_int32
     return int(L.femshell_grid_cap(None if text is None else str(text).encode(), int(fallback)))
+
+
+def knob_long(name, default):
+    """The number the library reads from the environment variable `name` (femshell_knob_long; unset: default).  CPU only."""
+    L = load_library()
+    L.femshell_knob_long.argtypes = [C.c_char_p, C.c_long]
+    L.femshell_knob_long.restype = C.c_long
+    return int(L.femshell_knob_long(str(name).encode(), int(default)))
+
+
+def knob_flag(name, default):
+    """The switch the library reads from the environment variable `name` (femshell_knob_flag; unset: default).  CPU only."""
+    L = load_library()
+    L.femshell_knob_flag.argtypes = [C.c_char_p, C.c_int]
+    L.femshell_knob_flag.restype = C.c_int
+    return bool(L.femshell_knob_flag(str(name).encode(), int(bool(default))))

@@ -31,9 +31,16 @@
 #include <vector>
 
 #include "amg_patch.hpp"
+#include "knobs.hpp"
 #include "plan.hpp"
 
 namespace femshell {
+
+// FEMSHELL_AMG_VERBOSE=1: the setup prints its laps, its allocator costs and why a dense inverse failed to stderr (read per
+// call: every site is in a setup path)
+inline bool amg_verbose() { return knob_flag("FEMSHELL_AMG_VERBOSE", false); }
+// FEMSHELL_AMG_PLAIN_RBM=1: the six plain rigid-body modes as the near-null space, no projection onto the node normals (A/B runs)
+inline bool amg_plain_rbm() { return knob_flag("FEMSHELL_AMG_PLAIN_RBM", false); }
 
 // arrays that stay uninitialised on resize (RawVec, plan.hpp): the gigabyte-sized value arrays and the large index arrays
 // of the setup are written in full by parallel loops; a serial zero fill first would cost as much as the loop itself

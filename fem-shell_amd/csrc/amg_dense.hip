@@ -55,23 +55,6 @@ __global__ __launch_bounds__(256) void k_dense_scatter(const int64_t *__restrict
     D[(6ll * lo + r) * ld + 6ll * col[q] + c] = val[e];
 }
 
-// lower triangle <- mean of the two triangles (the Galerkin products are symmetric up to rounding), unit diagonal on the
-// padding rows, copy of the diagonal for the pivot test
-__global__ __launch_bounds__(256) void k_dense_symmetrize(double *__restrict__ D, int64_t ld, int n, int n_pad, double *__restrict__ diag0)
-{
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int r = (int)(e / n_pad), c = (int)(e % n_pad);
-    if (r >= n_pad || c > r) return;
-    if (r >= n) {
-        D[(int64_t)r * ld + c] = r == c ? 1.0 : 0.0;
-        if (r == c) diag0[r] = 1.0;
-        return;
-    }
-    const double v = 0.5 * (D[(int64_t)r * ld + c] + D[(int64_t)c * ld + r]);
-    D[(int64_t)r * ld + c] = v;
-    if (r == c) diag0[r] = v;
-}
-
 // The sweeps read and write the lower triangle only, and the lower triangle of a Galerkin operator is as good a symmetric
 // matrix as the mean of its two triangles (they differ in the 16th digit): nothing to symmetrise, only the diagonal to copy
 // for the pivot test and a unit diagonal to put on the padding rows (0.31 ms of transposed reads less at 7386 dofs).
@@ -933,7 +916,7 @@ __global__ __launch_bounds__(256) void k_dense_gemv_big(const T *__restrict__ A,
 int amg_dense_probe_streams(femshell_ctx *c)
 {
     hipStream_t st = c->stream;
-    const bool verbose = getenv("FEMSHELL_AMG_VERBOSE") && atoi(getenv("FEMSHELL_AMG_VERBOSE")) != 0;
+    const bool verbose = amg_verbose();
     DevBuf<unsigned int> flag;
     DevBuf<int32_t> seen;
     FS_HIP(flag.alloc(1));
@@ -1011,13 +994,8 @@ int dense_inverse_once(femshell_ctx *c, const Bsr &A, bool single_precision, Dev
     FS_HIP(hipEventRecord(e0, st));
     const int64_t nent = (int64_t)A.val.size();
     hipLaunchKernelGGL(k_dense_scatter, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, st, dptr.p, dcol.p, dval.p, A.nr, D.p, ld);
-    // FEMSHELL_AMG_DENSE_SYMMETRIZE=1: the mean of the two triangles as before round 4 (A/B runs)
-    if (getenv("FEMSHELL_AMG_DENSE_SYMMETRIZE") && atoi(getenv("FEMSHELL_AMG_DENSE_SYMMETRIZE")) == 1) {
-        hipLaunchKernelGGL(k_dense_symmetrize, dim3((unsigned)(((int64_t)n_pad * n_pad + 255) / 256)), dim3(256), 0, st, D.p, ld, n, n_pad, diag0.p);
-    } else {
-        const int64_t work = std::max<int64_t>(n_pad, (int64_t)(n_pad - n) * n_pad);
-        hipLaunchKernelGGL(k_dense_prepare, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, D.p, ld, n, n_pad, diag0.p);
-    }
+    const int64_t prepare_work = std::max<int64_t>(n_pad, (int64_t)(n_pad - n) * n_pad);
+    hipLaunchKernelGGL(k_dense_prepare, dim3((unsigned)((prepare_work + 255) / 256)), dim3(256), 0, st, D.p, ld, n, n_pad, diag0.p);
     const int tiles = nt * (nt + 1) / 2;
     // super-blocks of the trailing update, dealt out to the eight XCDs by weight (DenseTileMap)
     DevBuf<int32_t> d_sb_list;
@@ -1053,7 +1031,7 @@ int dense_inverse_once(femshell_ctx *c, const Bsr &A, bool single_precision, Dev
         tmap.list = d_sb_list.p;
         tmap.per_xcd = (int)longest;
         tmap.nt = nt;
-        tmap.linear = (getenv("FEMSHELL_AMG_DENSE_XCD_MAP") && atoi(getenv("FEMSHELL_AMG_DENSE_XCD_MAP")) == 0) ? 1 : 0;
+        tmap.linear = knob_flag("FEMSHELL_AMG_DENSE_XCD_MAP", true) ? 0 : 1;
     }
     const unsigned update_grid = 8u * (unsigned)tmap.per_xcd * kSb * kSb;
     const size_t lds_upd_bytes = (size_t)kUpdLds * sizeof(double);
@@ -1066,13 +1044,13 @@ int dense_inverse_once(femshell_ctx *c, const Bsr &A, bool single_precision, Dev
     // were serialised, or on a card shared with other processes, a bound expires.  The waiting kernel then marks status 2 and
     // amg_dense_inverse_device runs the whole inverse again with the pivot as a launch in front of every sweep (slower, same
     // numbers).
-    const bool panel_split = !(getenv("FEMSHELL_AMG_DENSE_PANEL_SPLIT") && atoi(getenv("FEMSHELL_AMG_DENSE_PANEL_SPLIT")) == 0);
+    const bool panel_split = knob_flag("FEMSHELL_AMG_DENSE_PANEL_SPLIT", true);
     // FEMSHELL_AMG_DENSE_TILE=128: the trailing update on 128 x 128 tiles (k_dense_update128; default: 64 x 64, four workgroups
     // per CU).  MEASURED, round 5, 7776 dofs, alternating on one box, both with the look-ahead on the second stream: 15.0 ms
     // against 13.5 ms (before the loads of a chunk were kept together: stage_chunk) -- half the operand traffic and four times
     // the matrix instructions per LDS read buy nothing where the workgroups wait for memory latency, and the larger tile has 1891
     // workgroups for 512 slots (a fourth, nearly empty round).  The measured alternative stays, and stays under test.
-    const bool big_tiles = getenv("FEMSHELL_AMG_DENSE_TILE") && atoi(getenv("FEMSHELL_AMG_DENSE_TILE")) == 128;
+    const bool big_tiles = knob_long("FEMSHELL_AMG_DENSE_TILE", 0) == 128;
     const int stiles = ns * (ns + 1) / 2;
     const size_t lds_big_bytes = 2 * (size_t)kSW * kLdh * sizeof(double);
     if (big_tiles) {
@@ -1081,8 +1059,8 @@ int dense_inverse_once(femshell_ctx *c, const Bsr &A, bool single_precision, Dev
     }
     // the look-ahead's second stream: made once per context; it meets the first through the counters (and one event, here: the
     // counters are zero before anything polls them)
-    int spin_limit = 1 << 22; // polls before a waiting workgroup gives up (seconds) (FEMSHELL_AMG_DENSE_LOOKAHEAD_SPINS: tests)
-    if (const char *e = getenv("FEMSHELL_AMG_DENSE_LOOKAHEAD_SPINS")) spin_limit = atoi(e);
+    // polls before a waiting workgroup gives up (seconds) (FEMSHELL_AMG_DENSE_LOOKAHEAD_SPINS: tests)
+    const int spin_limit = (int)knob_long("FEMSHELL_AMG_DENSE_LOOKAHEAD_SPINS", 1l << 22);
     unsigned int *tiles_in_place = la_flags.p, *b_complete = la_flags.p + ns + 1;
     if (lookahead && c->aux_streams_side_by_side < 0) lookahead = false;
     if (lookahead && ns > 1) {
@@ -1162,12 +1140,12 @@ int amg_dense_inverse_device(femshell_ctx *c, const Bsr &A, bool single_precisio
                              int64_t *lda_out, AmgDenseStats *stats)
 {
     // FEMSHELL_AMG_DENSE_LOOKAHEAD=0: the pivot inverse as a launch of its own in front of every sweep (A/B runs)
-    const bool lookahead = !(getenv("FEMSHELL_AMG_DENSE_LOOKAHEAD") && atoi(getenv("FEMSHELL_AMG_DENSE_LOOKAHEAD")) == 0);
+    const bool lookahead = knob_flag("FEMSHELL_AMG_DENSE_LOOKAHEAD", true);
     bool timed_out = false;
     int rc = dense_inverse_once(c, A, single_precision, inv64, inv32, lda_out, stats, lookahead, &timed_out);
     if (rc && timed_out && lookahead) {
         // the look-ahead's workgroup was not scheduled beside the three it waits for (shared card, CU mask): once more, without it
-        if (getenv("FEMSHELL_AMG_VERBOSE") && atoi(getenv("FEMSHELL_AMG_VERBOSE")) != 0)
+        if (amg_verbose())
             fprintf(stderr, "[femshell amg setup] the look-ahead of the dense inverse timed out: running it again without\n");
         inv64->release();
         inv32->release();

@@ -197,6 +197,8 @@ int32_t amg_dist_min();
 // FEMSHELL_AMG_KEEP_HOST=1 (up to 2,000,000 blocks).  Until round 4 every problem of up to 2,000,000 blocks paid for them: a
 // quarter of the multigrid setup of the 250k-triangle roof went into downloads nobody read.
 bool amg_keep_host(int64_t nnz_blocks);
+// FEMSHELL_AMG_QR=memory: every aggregate takes the tentative QR's path of the large ones (rows in Q instead of registers; tests)
+inline bool amg_qr_in_memory() { return knob_is("FEMSHELL_AMG_QR", "memory"); }
 // does the hierarchy keep single-precision copies (level operators for the smoothers, coarsest inverse)?
 bool amg_uses_single_precision(const Amg &H);
 // the smoother's upper bound of the spectrum of D^-1 A: safety factor x the estimate of a power iteration of that many steps

@@ -399,11 +399,7 @@ static int32_t aggregate_on_pattern(const HostEllPattern &H, const std::vector<i
 
 // FEMSHELL_AMG_SYMBOLIC=host: the patterns of a coarsening step on the host threads as until round 6 (the path tests compare the
 // device's with, and the fallback of rows too long for the lane sets); default: amg_symbolic.hip
-static bool symbolic_on_device()
-{
-    const char *e = getenv("FEMSHELL_AMG_SYMBOLIC"); // (read per setup: the tests switch it inside one process)
-    return !(e && std::strcmp(e, "host") == 0);
-}
+static bool symbolic_on_device() { return !knob_is("FEMSHELL_AMG_SYMBOLIC", "host"); } // (read per setup: the tests switch it inside one process)
 
 // The integer work of a coarsening step on the host threads: the patterns as lists, their sliced ELL images (kept: eP, eAP, eR,
 // eAc), the uploads into S.  G: the level's graph, sorted rows.
@@ -740,8 +736,7 @@ int amg_device_coarsen(femshell_ctx *c, const DeviceMatrix &Adev, const HostEllP
     {
         FS_HIP(d_Q.alloc((size_t)n * 36));
         FS_HIP(Bc_dev->alloc((size_t)na * 36));
-        // FEMSHELL_AMG_QR=memory: every aggregate takes the path of the large ones (rows in Q instead of registers; tests)
-        const bool in_memory = getenv("FEMSHELL_AMG_QR") && std::string(getenv("FEMSHELL_AMG_QR")) == "memory";
+        const bool in_memory = amg_qr_in_memory();
         if (before_qr) {
             const int rcq = before_qr();
             if (rcq) return rcq;
@@ -771,7 +766,7 @@ int amg_device_coarsen(femshell_ctx *c, const DeviceMatrix &Adev, const HostEllP
     // on the matrix cores (6-row panels leave 10 of 16 tile rows idle and the operands arrive 8 bytes at a time) -- the
     // product is a gather of 288-byte blocks at 4 TFLOP/s, not a GEMM, so the vector-ALU kernel is the default and the
     // matrix-core kernel the measured alternative (tests run both; bench.py reports both).  Read per setup.
-    const bool use_mfma = getenv("FEMSHELL_AMG_GALERKIN") && std::string(getenv("FEMSHELL_AMG_GALERKIN")) == "mfma";
+    const bool use_mfma = knob_is("FEMSHELL_AMG_GALERKIN", "mfma");
     // the spectral bound of the level: its power iteration has been running beside the host work above
     double lam = 0.0;
     int rc = lam_of(&lam);

@@ -279,7 +279,7 @@ int dist_coarsen(femshell_ctx *c, const femshell_pc_options &opt, int level, con
             FS_HIP(d_Q.alloc((size_t)n_local * 36));
             FS_HIP(d_Q.zero(st));
             FS_HIP(res->Bc_dev.alloc((size_t)std::max(na, 1) * 36));
-            const bool in_memory = getenv("FEMSHELL_AMG_QR") && std::string(getenv("FEMSHELL_AMG_QR")) == "memory";
+            const bool in_memory = amg_qr_in_memory();
             launch_amg_tentative_qr(Bsrc, d_gptr.p, d_order.p, na, largest, d_Q.p, res->Bc_dev.p, in_memory, st);
             FS_HIP(hipGetLastError());
             FS_HIP(d_keyf.upload(keyf, st));
@@ -794,11 +794,7 @@ double operator_bytes(const AmgOperator &op)
 
 } // namespace
 
-int32_t amg_dist_min()
-{
-    const char *e = getenv("FEMSHELL_AMG_DIST_MIN"); // read per setup: the tests switch it inside one process
-    return e ? (int32_t)atol(e) : (int32_t)60000;
-}
+int32_t amg_dist_min() { return (int32_t)knob_long("FEMSHELL_AMG_DIST_MIN", 60000); } // (read per setup: the tests switch it inside one process)
 
 int level_halo_exchange(femshell_ctx *c, LevelHalo &H, double *vec, int width, hipStream_t st)
 {
@@ -831,7 +827,7 @@ int amg_setup_dist(femshell_ctx *c)
     Amg &H = *c->amg;
     H.opt = opt;
     H.dist.reset(new AmgDist());
-    static const bool verbose = getenv("FEMSHELL_AMG_VERBOSE") && atoi(getenv("FEMSHELL_AMG_VERBOSE")) != 0;
+    static const bool verbose = amg_verbose();
     double tl = now_s();
     int lap_level = 0;
     auto lap = [&](const char *what) {
@@ -841,7 +837,7 @@ int amg_setup_dist(femshell_ctx *c)
         CommWatch::heartbeat(); // (progress of the phase the watchdog times)
     };
     const bool keep_host = amg_keep_host(pl.nnz_blocks); // inspection exports (tests)
-    static const bool plain = getenv("FEMSHELL_AMG_PLAIN_RBM") && atoi(getenv("FEMSHELL_AMG_PLAIN_RBM")) != 0;
+    static const bool plain = amg_plain_rbm();
 
     // ---- level 0: the rank's rows of K
     H.levels.emplace_back(new AmgLevel());

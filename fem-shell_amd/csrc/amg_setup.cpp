@@ -216,6 +216,9 @@ void rigid_body_modes(int32_t n, const double *xyz, const uint8_t *dmask, std::v
     });
 }
 
+// FEMSHELL_AMG_AGG_ORDER=bfs|index forces one of the two visiting orders below (experiments); default: by the scatter of the numbering
+static const char *amg_agg_order() { return knob_text("FEMSHELL_AMG_AGG_ORDER"); }
+
 // Order in which the greedy aggregation visits the nodes.  The passes below sweep the nodes in sequence, which gives
 // compact aggregates when the numbering itself sweeps the mesh (structured grids, Morton / Cuthill-McKee numberings) and
 // ragged ones when it does not: on a 500k-triangle Delaunay mesh with shuffled numbering the solve took 287 iterations
@@ -237,8 +240,7 @@ void aggregation_order(const Bsr &A, std::vector<int32_t> *order)
     }, 1 << 16);
     const double dist = (double)dist_sum.load();
     const int64_t edges = A.ptr[n];
-    // FEMSHELL_AMG_AGG_ORDER=bfs|index forces one of the two (experiments); default: by the scatter of the numbering
-    const char *force = getenv("FEMSHELL_AMG_AGG_ORDER");
+    const char *force = amg_agg_order();
     if (force && std::strcmp(force, "index") == 0) return;
     const bool bfs = force && std::strcmp(force, "bfs") == 0;
     if (!bfs && (edges == 0 || dist / (double)edges <= 8.0 * std::sqrt((double)n))) return;
@@ -349,14 +351,14 @@ static const Bsr *graph_for_aggregation(const Bsr &A, int keep, Bsr *store)
 // meshes, 11.9 neighbours per node on their coarse levels, keep their aggregates bit for bit; 0: all of them, as in rounds 2-4)
 static int aggregation_keep()
 {
-    const char *e = getenv("FEMSHELL_AMG_AGG_KEEP"); // (read per setup: the tests switch it inside one process)
+    const char *e = knob_text("FEMSHELL_AMG_AGG_KEEP"); // (read per setup: the tests switch it inside one process)
     return e && *e ? atoi(e) : 12;
 }
 
 // FEMSHELL_AMG_AGG_CHUNK: rows per chunk of the chunked aggregation below (default 0: the whole graph in one piece)
 static int64_t aggregation_chunk()
 {
-    const char *e = getenv("FEMSHELL_AMG_AGG_CHUNK"); // (read per setup: the tests switch it inside one process)
+    const char *e = knob_text("FEMSHELL_AMG_AGG_CHUNK"); // (read per setup: the tests switch it inside one process)
     return e && *e ? atoll(e) : 0;
 }
 
@@ -372,7 +374,7 @@ bool aggregation_is_plain(int32_t n, int64_t widest_row, int64_t edges, double n
     const int keep = aggregation_keep();
     if (keep > 0 && widest_row > (int64_t)keep + 1) return false;
     if (have_visit || n < 64) return true;
-    const char *force = getenv("FEMSHELL_AMG_AGG_ORDER");
+    const char *force = amg_agg_order();
     if (force && std::strcmp(force, "index") == 0) return true;
     if (force && std::strcmp(force, "bfs") == 0) return false;
     return edges == 0 || neighbour_distance_sum / (double)edges <= 8.0 * std::sqrt((double)n);
@@ -935,7 +937,7 @@ bool dense_inverse(const Bsr &A, std::vector<double> *invout)
         double d = a_cc;
         for (int64_t k = 0; k < c; k++) d -= L[c * n + k] * L[c * n + k];
         if (d < -1e-4 * std::fabs(a_cc) || !(a_cc > 0.0)) {
-            if (getenv("FEMSHELL_AMG_VERBOSE"))
+            if (amg_verbose())
                 fprintf(stderr, "[femshell amg setup] dense inverse: pivot %lld of %lld: d = %.3e, diagonal %.3e (ratio %.2e)\n",
                         (long long)c, (long long)n, d, a_cc, d / a_cc);
             return false;

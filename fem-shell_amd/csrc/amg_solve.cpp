@@ -26,14 +26,13 @@ bool has_lowp_copy(const AmgLevel &L) { return L.A32.p != nullptr; }
 // Chebyshev direction; 1: the results only; 0: nothing.  Residuals and iterates stay FP64.  Read per setup.
 int smooth_vectors_f32()
 {
-    const char *e = getenv("FEMSHELL_AMG_VEC_F32");
-    const int v = e ? atoi(e) : 2;
+    const int v = (int)knob_long("FEMSHELL_AMG_VEC_F32", 2);
     return v < 0 ? 0 : (v > 2 ? 2 : v);
 }
 
-bool setup_verbose_flag()
+bool setup_verbose() // (once per process)
 {
-    static const bool verbose = getenv("FEMSHELL_AMG_VERBOSE") && atoi(getenv("FEMSHELL_AMG_VERBOSE")) != 0;
+    static const bool verbose = amg_verbose();
     return verbose;
 }
 
@@ -125,12 +124,12 @@ struct PowerIteration {
 // FEMSHELL_AMG_PATCH_TAU (default 0.8; 0: no patch smoother) and FEMSHELL_AMG_PATCH_MAX (nodes per cluster, default 8): amg_patch.hpp
 double patch_tau()
 {
-    const char *e = getenv("FEMSHELL_AMG_PATCH_TAU"); // (read per setup: the tests switch it inside one process)
+    const char *e = knob_text("FEMSHELL_AMG_PATCH_TAU"); // (read per setup: the tests switch it inside one process)
     return e && *e ? atof(e) : 0.8;
 }
 int patch_max_nodes()
 {
-    const char *e = getenv("FEMSHELL_AMG_PATCH_MAX");
+    const char *e = knob_text("FEMSHELL_AMG_PATCH_MAX");
     const int m = e && *e ? atoi(e) : 8;
     return m < 2 ? 2 : (m > kPatchMaxNodes ? kPatchMaxNodes : m);
 }
@@ -142,7 +141,7 @@ int patch_max_nodes()
 // clusters are built when more than FEMSHELL_AMG_PATCH_TRIGGER (default 0.01) of the pairs exceed 0.98; 0: whenever an edge exceeds tau.
 double patch_trigger()
 {
-    const char *e = getenv("FEMSHELL_AMG_PATCH_TRIGGER");
+    const char *e = knob_text("FEMSHELL_AMG_PATCH_TRIGGER");
     return e && *e ? atof(e) : 0.01;
 }
 constexpr double kPatchTriggerSigma = 0.98;
@@ -189,7 +188,7 @@ int amg_build_patches(femshell_ctx *c, const DeviceMatrix &A, AmgLevel &L, bool 
         high = all[0];
         pairs = all[1];
     }
-    if (setup_verbose_flag())
+    if (setup_verbose())
         fprintf(stderr, "[femshell amg setup] patch smoother: %u of %.0f pairs above sigma %.2f (%.0f above %.2f: %s)\n", found, pairs, tau, high,
                 kPatchTriggerSigma, high > patch_trigger() * pairs || (patch_trigger() <= 0.0 && found > 0) ? "a mesh of poor element quality" : "no clusters");
     if (patch_trigger() > 0.0 ? !(high > patch_trigger() * pairs) : found == 0) return FEMSHELL_OK;
@@ -244,7 +243,7 @@ int amg_build_patches(femshell_ctx *c, const DeviceMatrix &A, AmgLevel &L, bool 
     P->fell_back = patch_matrices(P->h_ptr, moff, hD.data(), hB.data());
     FS_HIP(hipMemcpyAsync(P->M.p, hB.data(), hB.size() * sizeof(double), hipMemcpyHostToDevice, st));
     FS_HIP(hipStreamSynchronize(st)); // (hB goes out of scope)
-    if (setup_verbose_flag())
+    if (setup_verbose())
         fprintf(stderr, "[femshell amg setup] patch smoother: %lld rigid edges (sigma > %.2f), %d clusters of %d nodes (at most %d each), %d not positive definite\n",
                 (long long)P->edges, tau, P->n_clusters, P->n_members, P->max_nodes, P->fell_back);
     L.patches = P;
@@ -352,15 +351,13 @@ int alloc_level_vectors(AmgLevel &L, bool top, bool kcycle, hipStream_t st)
 
 double amg_lambda_safety()
 {
-    const char *e = getenv("FEMSHELL_AMG_LAMBDA_SAFETY");
-    const double v = e ? atof(e) : 1.1;
+    const double v = knob_double("FEMSHELL_AMG_LAMBDA_SAFETY", 1.1);
     return v >= 1.0 && v <= 4.0 ? v : 1.1;
 }
 
 int amg_power_iterations()
 {
-    const char *e = getenv("FEMSHELL_AMG_POWER_ITS");
-    const int v = e ? atoi(e) : 30;
+    const int v = (int)knob_long("FEMSHELL_AMG_POWER_ITS", 30);
     return v >= 2 && v <= 10000 ? v : 30;
 }
 
@@ -370,8 +367,7 @@ bool coarse_symmetric_storage(int32_t n_nodes)
     // diagonal + upper blocks: their products are HBM-bound (4M-triangle panel, level 1 of 222k nodes: 1.63 s against
     // 1.71 s per solve); the smaller levels are launch- and latency-bound, where the two-phase product loses (all
     // levels symmetric: 1.80 s)
-    const char *e = getenv("FEMSHELL_AMG_COARSE_SYM"); // (read per call: the tests switch it inside one process)
-    const long min_nodes = e ? atol(e) : 100000l;
+    const long min_nodes = knob_long("FEMSHELL_AMG_COARSE_SYM", 100000l); // (read per call: the tests switch it inside one process)
     return min_nodes > 0 && n_nodes >= min_nodes && default_symmetric_storage();
 }
 
@@ -423,18 +419,11 @@ SetupRules setup_rules(const femshell_pc_options &opt)
     SetupRules r;
     r.opt = opt;
     // the first coarsening step runs its numerics on the device unless FEMSHELL_AMG_SETUP=host (amg_device_setup.cpp)
-    r.host_only = getenv("FEMSHELL_AMG_SETUP") && std::string(getenv("FEMSHELL_AMG_SETUP")) == "host";
-    const char *dmin_env = getenv("FEMSHELL_AMG_DEVICE_MIN"); // nodes; levels at or below it are coarsened on the host
-    // (5000 since round 4: the 18.6k-node level of the 4M-triangle meshes on the device as well, 46 -> 32 ms for the two
-    //  steps below level 0)
-    r.device_min = dmin_env ? (int32_t)atol(dmin_env) : (int32_t)5000;
+    r.host_only = knob_is("FEMSHELL_AMG_SETUP", "host");
+    // nodes; levels at or below it are coarsened on the host (5000 since round 4: the 18.6k-node level of the 4M-triangle
+    // meshes on the device as well, 46 -> 32 ms for the two steps below level 0)
+    r.device_min = (int32_t)knob_long("FEMSHELL_AMG_DEVICE_MIN", 5000);
     return r;
-}
-
-bool setup_verbose()
-{
-    static const bool verbose = getenv("FEMSHELL_AMG_VERBOSE") && atoi(getenv("FEMSHELL_AMG_VERBOSE")) != 0;
-    return verbose;
 }
 
 } // namespace
@@ -468,9 +457,7 @@ int dense_inverse_defect(femshell_ctx *c, AmgLevel &L, const DeviceMatrix &A, Am
 
 bool amg_keep_host(int64_t nnz_blocks)
 {
-    const char *e = getenv("FEMSHELL_AMG_KEEP_HOST"); // (read per setup)
-    if (e && atoi(e) != 0) return nnz_blocks <= (int64_t)2000000;
-    return nnz_blocks <= (int64_t)300000;
+    return nnz_blocks <= (knob_flag("FEMSHELL_AMG_KEEP_HOST", false) ? (int64_t)2000000 : (int64_t)300000); // (read per setup)
 }
 
 bool amg_uses_single_precision(const Amg &H)
@@ -493,7 +480,7 @@ int amg_setup(femshell_ctx *c)
     Amg &H = *c->amg;
     H.opt = opt;
     const Plan &pl = c->plan;
-    if (setup_verbose_flag()) {
+    if (setup_verbose()) {
         double ps[6];
         DevPool::get().stats(ps); // (clears the counters: what follows belongs to this setup)
     }
@@ -511,8 +498,7 @@ int amg_setup(femshell_ctx *c)
     Bsr A;
     std::vector<double> B;  // near-null space of the current level on the host (levels coarsened on the host) ...
     DevBuf<double> Bdev;    // ... and in HBM (levels coarsened on the device, from the second one on)
-    // FEMSHELL_AMG_PLAIN_RBM=1: the six plain rigid-body modes (A/B runs)
-    static const bool plain = getenv("FEMSHELL_AMG_PLAIN_RBM") && atoi(getenv("FEMSHELL_AMG_PLAIN_RBM")) != 0;
+    static const bool plain = amg_plain_rbm();
     // the node normals (48 MB to bring over at 4M triangles) on a thread of their own, beside the search for
     // clusters, the copy of the pattern and the greedy passes of the aggregation: the thread computes them and -- when a coarsening
     // step on the device will read them -- copies them into HBM on a stream of its own; whoever needs them first waits for the
@@ -638,7 +624,7 @@ int amg_setup(femshell_ctx *c)
                 FS_HIP(hipStreamSynchronize(st));
                 if (L0.patches->glue) L0.patches->glue = false;
                 else L0.patches.reset();
-                if (setup_verbose_flag()) fprintf(stderr, "[femshell amg setup] patch smoother: %s\n", L0.patches ? "once more without gluing the clusters" : "given up for this mesh");
+                if (setup_verbose()) fprintf(stderr, "[femshell amg setup] patch smoother: %s\n", L0.patches ? "once more without gluing the clusters" : "given up for this mesh");
                 continue;
             }
             break;
@@ -665,7 +651,7 @@ int amg_setup(femshell_ctx *c)
     rc = amg_finish_hierarchy(c, A, B, Bdev, first_level);
     if (rc) return rc;
     H.setup_seconds = now_s() - t0;
-    if (setup_verbose_flag()) {
+    if (setup_verbose()) {
         double ps[6];
         DevPool::get().stats(ps);
         fprintf(stderr, "[femshell amg setup] device allocator during this setup (and whatever ran since the last one): %.0f hipMalloc %.1f ms, %.0f hipFree %.1f ms, "
@@ -761,11 +747,11 @@ int amg_finish_hierarchy(femshell_ctx *c, Bsr &A, std::vector<double> &B, DevBuf
             // until the host's 0.19 s at 145 nodes and 0.35 s at 204 showed up as most of the setup of the small coupled
             // examples) the inverse is computed on the matrix cores (amg_dense.hip: n^3 flops, 0.4 TFLOP at 1231 nodes)
             // (read per setup: the tests switch them inside one process)
-            const long dense_device_min = getenv("FEMSHELL_AMG_DENSE_DEVICE_MIN") ? atol(getenv("FEMSHELL_AMG_DENSE_DEVICE_MIN")) : 64l;
+            const long dense_device_min = knob_long("FEMSHELL_AMG_DENSE_DEVICE_MIN", 64l);
             // (stored and applied in single precision unless FEMSHELL_AMG_DENSE_F32=0: the coarsest solve sits inside a K cycle
             //  inside a flexible Krylov method, 1e-7 there moves the iteration count by one or two and halves the 436 MB the
             //  four visits per iteration stream: panel 0.809 -> 0.785 s, cylinder 0.755 -> 0.744 s)
-            const bool dense_f32 = !c->amg_fp64_only && !(getenv("FEMSHELL_AMG_DENSE_F32") && atoi(getenv("FEMSHELL_AMG_DENSE_F32")) == 0);
+            const bool dense_f32 = !c->amg_fp64_only && knob_flag("FEMSHELL_AMG_DENSE_F32", true);
             H.coarse_lda = 0;
             H.dense = AmgDenseStats();
             H.coarse_inv32.release();
@@ -907,8 +893,7 @@ int amg_finish_hierarchy(femshell_ctx *c, Bsr &A, std::vector<double> &B, DevBuf
         // below ||K||: only the smoother -- a polynomial in D^-1 A whose job is the upper end of the spectrum -- tolerates
         // 1e-7, and the flexible Krylov method around the cycle does not care that the preconditioner moved a little.
         // 1 (default): levels of at least 4096 nodes; 2: level 0 only, 3: every level, whatever their size (A/B runs, tests); 0: off.
-        const char *e = getenv("FEMSHELL_AMG_SMOOTH_F32");
-        const int mode = c->amg_fp64_only ? 0 : (e ? atoi(e) : 1);
+        const int mode = c->amg_fp64_only ? 0 : (int)knob_long("FEMSHELL_AMG_SMOOTH_F32", 1);
         // (what the coarsening steps released -- A P, Q, the symbolic buffers -- joins the pool's kept blocks now: the copies below are
         //  carved from them instead of being fresh requests to the driver, context.hpp DevPool::alloc (3))
         if (mode != 0) (void)DevPool::get().flush_pending();
@@ -971,26 +956,11 @@ int amg_finish_hierarchy(femshell_ctx *c, Bsr &A, std::vector<double> &B, DevBuf
 namespace {
 
 // FEMSHELL_AMG_FUSED_CHEB=0: product and Chebyshev step of the full-storage levels as two launches (A/B runs)
-bool fused_cheb()
-{
-    const char *e = getenv("FEMSHELL_AMG_FUSED_CHEB");
-    return !(e && atoi(e) == 0);
-}
+bool fused_cheb() { return knob_flag("FEMSHELL_AMG_FUSED_CHEB", true); }
 
-// FEMSHELL_AMG_POST_INCREMENT=0: the residual the post-smoothing starts from as b - A x, an FP64 product with the iterate, instead
-// of (restricted residual) - A (P x_c) on the smoother's copy of the operator (A/B runs)
-bool post_increment()
-{
-    const char *e = getenv("FEMSHELL_AMG_POST_INCREMENT");
-    return !(e && atoi(e) == 0);
-}
-
-// FEMSHELL_AMG_RESIDUAL_INCREMENT=0: the residual in front of a restriction as b - A x, a product of its own in FP64 (A/B runs)
-bool residual_increment()
-{
-    const char *e = getenv("FEMSHELL_AMG_RESIDUAL_INCREMENT");
-    return !(e && atoi(e) == 0);
-}
+// FEMSHELL_AMG_RESIDUAL_INCREMENT=0: the residual in front of a restriction as b - A x, a product of its own in FP64, and the
+// post-smoothing from x += P x_c with a residual product of its own as well (A/B runs)
+bool residual_increment() { return knob_flag("FEMSHELL_AMG_RESIDUAL_INCREMENT", true); }
 
 // does the matrix view carry the single-precision copy of its values for the smoothing products?
 bool has_lowp(const DeviceMatrix &A) { return A.vals32 != nullptr; }
@@ -1003,21 +973,7 @@ bool has_lowp(const DeviceMatrix &A) { return A.vals32 != nullptr; }
 // panel, with the one-lane-per-node vector kernels the fused passes take as long as the passes they replace (147 against 65 + 81
 // us, 226 against 82 + 85 + 81 us: these kernels are bound by their load instructions, not by their bytes), so the gain is the
 // launches only; bit 2 changed the iteration count by rounding luck (104 -> 106) and stays off.
-int fuse_mask()
-{
-    const char *e = getenv("FEMSHELL_AMG_FUSE");
-    return e ? atoi(e) : 3;
-}
-
-// FEMSHELL_AMG_K_MASK (experiments; round 6): bit l set = the cycle of level l is wrapped into the K cycle's two Krylov steps; a
-// level whose bit is clear is visited once per visit of its parent, as in a V cycle.  Default: every level above the coarsest.
-// MEASURED (profiles/r06_kcycle_levels.txt): the Krylov steps cannot be taken off any level -- 4M-triangle panel 100 -> 196
-// iterations with the K cycle on level 1 only.
-int k_cycle_mask()
-{
-    const char *e = getenv("FEMSHELL_AMG_K_MASK");
-    return e && *e ? atoi(e) : ~0;
-}
+int fuse_mask() { return (int)knob_long("FEMSHELL_AMG_FUSE", 3); }
 
 struct Cycle {
     femshell_ctx *c;
@@ -1026,7 +982,6 @@ struct Cycle {
     hipStream_t st;
     int rc = FEMSHELL_OK;
     const int fuse = fuse_mask();
-    const int k_mask = k_cycle_mask();
     // level 0: the caller's kernel (k_pcg_update_start_node) has taken the first step of the pre-smoothing already -- d in L.d, x = d
     bool pre_started0 = false;
 
@@ -1092,7 +1047,6 @@ struct Cycle {
     }
     // y = K x on level 0 of a row-partitioned context: the halo exchange beside the interior slices (symmetric storage with
     // defer: the direct part only, the consumer collects the transposed products)
-    // (vals32: a smoothing product on the single-precision copy of K's values)
     // (lowp: a smoothing product on the single-precision copy of K's values that matrix view carries)
     void product0(double *x, double *y, bool defer, const DeviceMatrix *lowp = nullptr, int vec32 = 0)
     {
@@ -1289,12 +1243,15 @@ struct Cycle {
             launch_spmv(L.R.dm, rf, N.b.p, SpmvEpilogue(), gate, st);
         }
         const bool next_is_coarsest = (size_t)l + 2 == H.levels.size();
-        if (H.opt.cycle == FEMSHELL_CYCLE_K && !next_is_coarsest && ((k_mask >> (l + 1)) & 1)) kcycle(l + 1);
+        // (every level above the coarsest is wrapped into the K cycle's two Krylov steps: they cannot be taken off any level --
+        //  4M-triangle panel 100 -> 196 iterations with the K cycle on level 1 only, profiles/r06_kcycle_levels.txt)
+        if (H.opt.cycle == FEMSHELL_CYCLE_K && !next_is_coarsest) kcycle(l + 1);
         else cycle(l + 1, N.b.p, N.x.p);
         if (N.dist) halo(l + 1, N.x.p);
-        if (increments && post_increment()) {
+        if (increments) {
             // x += e, e = P x_c kept in the direction vector -- as floats where the smoothing products read theirs as floats --
-            // and the residual the post-smoothing starts from is the restricted one minus A e
+            // and the residual the post-smoothing starts from is the restricted one minus A e (with b - A x, an FP64 product with
+            // the iterate, in its place the CG broke down on the strip and Delaunay meshes: profiles/r04_breakdown_probe.txt)
             const DeviceMatrix &A = L.smooth_ready ? L.smooth_dm : amg_level_matrix(c, l);
             const bool e32 = A.symmetric && has_lowp(A) && A.vec32 == 2;
             SpmvEpilogue keep;
@@ -1473,7 +1430,7 @@ int cg_amg(femshell_ctx *c, const CgVectors &v0, double rtol, int32_t max_it, do
     const double rtol_first = loosened ? std::min(100.0 * rtol, 1e-2) : rtol;
     const int pass_limit = refine + (loosened ? 1 : 0);
     // FEMSHELL_REFINE_ADAPTIVE=0: every pass to a drop of 1e-4 of its own right-hand side, as before round 5 (A/B runs)
-    const bool adaptive_pass = !(getenv("FEMSHELL_REFINE_ADAPTIVE") && atoi(getenv("FEMSHELL_REFINE_ADAPTIVE")) == 0);
+    const bool adaptive_pass = knob_flag("FEMSHELL_REFINE_ADAPTIVE", true);
     CgVectors v = v0;
     CgScalars hs{};
     double pass_host[3] = {0.0, 0.0, 0.0}; // source of an asynchronous copy below: lives until the function's next synchronisation

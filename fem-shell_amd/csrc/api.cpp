@@ -685,11 +685,8 @@ int femshell_create(const femshell_config *cfg, femshell_ctx **out)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&c->ev0);
     if (e == hipSuccess) e = hipEventCreate(&c->ev1);
-    {
-        const char *sm = getenv("FEMSHELL_STATUS_MAPPED"), *ae = getenv("FEMSHELL_ASM_EVENTS");
-        c->status_mapped = !(sm && atoi(sm) == 0);
-        c->asm_events = !(ae && atoi(ae) == 0);
-    }
+    c->status_mapped = knob_flag("FEMSHELL_STATUS_MAPPED", true);
+    c->asm_events = knob_flag("FEMSHELL_ASM_EVENTS", true);
     if (e == hipSuccess) e = c->status.alloc(1);
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void **>(&c->status_host), sizeof(int32_t), c->status_mapped ? hipHostMallocMapped : hipHostMallocDefault);
     if (e == hipSuccess) {
@@ -749,7 +746,7 @@ int femshell_create(const femshell_config *cfg, femshell_ctx **out)
     c->mc.g = (1.0 - nu) / 2.0;
     c->mc.t = t;
     if (!(c->cfg.flags & (FEMSHELL_REORDER_MORTON | FEMSHELL_REORDER_RCM)))
-        if (const char *e = getenv("FEMSHELL_REORDER")) {
+        if (const char *e = knob_text("FEMSHELL_REORDER")) {
             if (std::strcmp(e, "morton") == 0) c->cfg.flags |= FEMSHELL_REORDER_MORTON;
             else if (std::strcmp(e, "rcm") == 0) c->cfg.flags |= FEMSHELL_REORDER_RCM;
         }
@@ -758,13 +755,11 @@ int femshell_create(const femshell_config *cfg, femshell_ctx **out)
     if (cfg->world_size > 1) {
         // one process per GPU on one node (BASELINE: "the 8 GPUs of one node"): the ranks share the host's cores for the
         // plan and the multigrid setup; LOCAL_WORLD_SIZE (torchrun) / FEMSHELL_LOCAL_WORLD_SIZE say how many share this host
-        const char *lw = getenv("FEMSHELL_LOCAL_WORLD_SIZE");
-        if (!lw) lw = getenv("LOCAL_WORLD_SIZE");
-        set_host_share(lw && atoi(lw) > 0 ? atoi(lw) : cfg->world_size);
+        const int lw = (int)knob_long(knob_text("FEMSHELL_LOCAL_WORLD_SIZE") ? "FEMSHELL_LOCAL_WORLD_SIZE" : "LOCAL_WORLD_SIZE", 0);
+        set_host_share(lw > 0 ? lw : cfg->world_size);
     }
     {
-        const char *e = getenv("FEMSHELL_PC");
-        const bool amg = e && (std::strcmp(e, "amg") == 0 || std::strcmp(e, "gamg") == 0);
+        const bool amg = knob_is("FEMSHELL_PC", "amg") || knob_is("FEMSHELL_PC", "gamg");
         (void)femshell_pc_defaults(amg ? FEMSHELL_PC_AMG : FEMSHELL_PC_BLOCK_JACOBI, &c->pc);
     }
     *out = c;
@@ -808,7 +803,7 @@ int femshell_comm_init(femshell_ctx *c, const uint8_t id[128])
     if (!c || !id) return set_err(FEMSHELL_ERR_INVALID, "femshell_comm_init: null argument");
     // one rank needs no communicator; FEMSHELL_FORCE_COMM=1 creates a 1-rank RCCL communicator anyway so
     // that the RCCL code path (all-reduce on the stream, row gather) can be exercised on a single GPU
-    if (c->cfg.world_size == 1 && !(getenv("FEMSHELL_FORCE_COMM") && atoi(getenv("FEMSHELL_FORCE_COMM")) == 1))
+    if (c->cfg.world_size == 1 && knob_long("FEMSHELL_FORCE_COMM", 0) != 1)
         return FEMSHELL_OK;
     int rc = select_device(c);
     if (rc) return rc;
@@ -879,7 +874,7 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     int rc = FEMSHELL_OK;
     TraceRange trace("femshell_set_mesh (plan + upload)");
     // FEMSHELL_PLAN_VERBOSE=1: wall time of the call's parts on stderr (the plan prints its own phases)
-    static const bool verbose = getenv("FEMSHELL_PLAN_VERBOSE") && atoi(getenv("FEMSHELL_PLAN_VERBOSE")) != 0;
+    static const bool verbose = plan_verbose();
     double t_part = wall_s();
     auto part_done = [&](const char *what) {
         const double t = wall_s();
@@ -1020,14 +1015,14 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     c->dm.vals = c->vals.p;
     c->dm.symmetric = p.symmetric ? 1 : 0;
     // the lower words of the diagonal blocks are not written (kernels.hpp); FEMSHELL_DIAG_UPPER=0: all 18 words (A/B runs)
-    c->dm.diag_upper = (p.symmetric && !(getenv("FEMSHELL_DIAG_UPPER") && atoi(getenv("FEMSHELL_DIAG_UPPER")) == 0)) ? 1 : 0;
+    c->dm.diag_upper = (p.symmetric && knob_flag("FEMSHELL_DIAG_UPPER", true)) ? 1 : 0;
     c->dm.max_in_width = p.max_in_width;
     c->dm.in_width = c->in_width.p;
     c->dm.in_base = c->in_base.p;
     c->dm.in_slots = c->in_slots.p;
     c->dm.in_rows = c->in_rows.p;
     // FEMSHELL_SPMV_LOCAL=0: every transposed product through HBM (A/B runs)
-    const bool local_products = p.symmetric && p.max_loc > 0 && !(getenv("FEMSHELL_SPMV_LOCAL") && atoi(getenv("FEMSHELL_SPMV_LOCAL")) == 0);
+    const bool local_products = p.symmetric && p.max_loc > 0 && knob_flag("FEMSHELL_SPMV_LOCAL", true);
     c->dm.gat_slots = local_products ? c->gat_slots.p : c->in_slots.p;
     c->dm.loc_index = local_products ? c->loc_index.p : nullptr;
     c->dm.loc_list = local_products ? c->loc_list.p : nullptr;
@@ -1048,7 +1043,7 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     // overlap of the halo exchange with the interior SpMV (FEMSHELL_HALO_OVERLAP=0 keeps everything on one stream)
     c->halo_overlap = false;
     if (c->comm.active() && !p.peers.empty() && p.n_interior_slices > 0 &&
-        !(getenv("FEMSHELL_HALO_OVERLAP") && atoi(getenv("FEMSHELL_HALO_OVERLAP")) == 0)) {
+        knob_flag("FEMSHELL_HALO_OVERLAP", true)) {
         if (!c->halo_stream) { // (femshell_comm_init creates it for its self-test)
             FS_HIP(hipStreamCreateWithFlags(&c->halo_stream, hipStreamNonBlocking));
             c->comm.second = c->halo_stream;
@@ -1354,10 +1349,10 @@ int femshell_pc_defaults(int32_t type, femshell_pc_options *out)
     amg_default_options(out);
     out->type = type;
     if (type == FEMSHELL_PC_AMG) {
-        const char *cy = getenv("FEMSHELL_AMG_CYCLE");
+        const char *cy = knob_text("FEMSHELL_AMG_CYCLE");
         if (cy && (cy[0] == 'V' || cy[0] == 'v')) out->cycle = FEMSHELL_CYCLE_V;
-        const char *rp = getenv("FEMSHELL_REFINE_PASSES");
-        if (rp && atoi(rp) >= 0 && atoi(rp) <= 4) out->refine_passes = atoi(rp);
+        const long rp = knob_long("FEMSHELL_REFINE_PASSES", -1);
+        if (rp >= 0 && rp <= 4) out->refine_passes = (int32_t)rp;
     }
     return FEMSHELL_OK;
 }

@@ -92,8 +92,7 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         // the block kernels of the modal analysis on scratch blocks of hashed vectors, back to back between one event pair
         if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_time_kernel: the block kernels run on single-rank contexts");
         if (which == FEMSHELL_KERNEL_GRAM && !c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no density set");
-        const char *e = getenv("FEMSHELL_TIME_KERNEL_COLS");
-        const int nc = e ? atoi(e) : 4;
+        const int nc = (int)knob_long("FEMSHELL_TIME_KERNEL_COLS", 4);
         if (nc < 1 || nc > kModalMaxBlock) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: FEMSHELL_TIME_KERNEL_COLS must be in 1 .. 32");
         if (which == FEMSHELL_KERNEL_GRAM && (rc = ensure_mass(c))) return rc;
         if (which == FEMSHELL_KERNEL_SPMM && !c->matrix_valid && (rc = do_assemble(c))) return rc;

@@ -153,8 +153,7 @@ int cg_single_reduction(femshell_ctx *c, const CgVectors &v, double rtol, int32_
     const int G = slice_grid(m);
     double *spmv_partials = v.partials + 2 * (size_t)G; // third partial array
     // FEMSHELL_CG_FOLD=0: the unfolded sequence (k_sym_gather_node pass, scalar step as a launch of its own) for A/B runs
-    const char *fold_env = getenv("FEMSHELL_CG_FOLD");
-    const bool fold = !(fold_env && atoi(fold_env) == 0);
+    const bool fold = knob_flag("FEMSHELL_CG_FOLD", true);
     const bool gather = fold && m.symmetric != 0; // the update kernel collects the transposed products of w = A z
     launch_cgcg_init(m, v, st);
     int len3 = 0;
@@ -193,9 +192,7 @@ int cg_single_reduction(femshell_ctx *c, const CgVectors &v, double rtol, int32_
 // multi-rank contexts use the single-reduction recurrence; FEMSHELL_CG_SINGLE_REDUCTION=0/1 overrides
 bool use_single_reduction(const femshell_ctx *c)
 {
-    const char *e = getenv("FEMSHELL_CG_SINGLE_REDUCTION");
-    if (e) return atoi(e) != 0;
-    return c->comm.active();
+    return knob_flag("FEMSHELL_CG_SINGLE_REDUCTION", c->comm.active());
 }
 
 } // namespace femshell

@@ -42,7 +42,7 @@ bool load_api(std::string *err)
     std::lock_guard<std::mutex> lock(g_api_mutex);
     if (g_api.lib) return true;
     // FEMSHELL_RCCL_LIB: tests point this at tests/helpers/fake_rccl (several ranks on one GPU)
-    const char *override_path = getenv("FEMSHELL_RCCL_LIB");
+    const char *override_path = knob_text("FEMSHELL_RCCL_LIB");
     void *lib = override_path ? dlopen(override_path, RTLD_NOW | RTLD_LOCAL) : dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
     if (!lib && override_path) {
         if (err) *err = std::string("cannot open FEMSHELL_RCCL_LIB=") + override_path + ": " + dlerror();
@@ -90,7 +90,7 @@ bool check(ncclResult_t r, const char *what, std::string *err)
 // ---- watchdog (comm.hpp) ---------------------------------------------------------------------------------------
 // Every live CommWatch is an entry of a registry the monitor thread walks: contexts on different threads have their own
 // phases and timers (distinct contexts are thread-safe, include/femshell.h).  The time limit is read once, by the thread that
-// opens the watch -- the monitor thread never calls getenv, which would race with a host that changes its environment.
+// opens the watch -- the monitor thread never reads the environment, which would race with a host that changes its environment.
 namespace {
 
 int64_t now_ms()
@@ -138,12 +138,11 @@ void watch_loop()
 CommWatch::CommWatch(int rank, int world, const char *phase) : entry_(nullptr)
 {
     if (world <= 1) return;
-    const char *e = getenv("FEMSHELL_COMM_TIMEOUT"); // once per watch, on the caller's thread (tests shorten it between calls)
     WatchEntry *w = new WatchEntry();
     w->phase = phase;
     w->rank = rank;
     w->world = world;
-    w->limit_s = e ? atof(e) : 120.0;
+    w->limit_s = knob_double("FEMSHELL_COMM_TIMEOUT", 120.0); // once per watch, on the caller's thread (tests shorten it between calls)
     w->since_ms.store(now_ms(), std::memory_order_release);
     w->parent = t_watch_top;
     t_watch_top = w;

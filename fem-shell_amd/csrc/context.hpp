@@ -45,6 +45,9 @@ inline const char *fs_basename(const char *path)
                                                  " (" + fs_basename(__FILE__) + ":" + std::to_string(__LINE__) + ")"); \
     } while (0)
 
+// FEMSHELL_POOL_VERBOSE=1: every hipMalloc of the pool below goes to stderr with its size and time (read per call)
+inline bool pool_verbose() { return knob_flag("FEMSHELL_POOL_VERBOSE", false); }
+
 // Device memory of the library's buffers.
 // (1) ARENAS (round 6).  A multigrid setup at 4M triangles makes about 150 allocations, and hipMalloc costs 0.5 - 2.5 ms a call on
 //     the boxes of this pool whatever the size: 60 to 370 ms of a 0.18 - 0.5 s setup were the driver's allocator
@@ -117,7 +120,7 @@ class DevPool {
                     const hipError_t e = hipMalloc(&base, ab);
                     stat_malloc_ns_ += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
                     stat_mallocs_++;
-                    if (getenv("FEMSHELL_POOL_VERBOSE")) fprintf(stderr, "[femshell pool] hipMalloc of an arena, %zu MB (for a request of %zu bytes)\n", ab >> 20, bytes);
+                    if (pool_verbose()) fprintf(stderr, "[femshell pool] hipMalloc of an arena, %zu MB (for a request of %zu bytes)\n", ab >> 20, bytes);
                     if (e == hipSuccess) {
                         arenas_.push_back(Arena{dev, static_cast<char *>(base), ab, 0, 0, false});
                         a = &arenas_.back();
@@ -167,7 +170,7 @@ class DevPool {
         hipError_t e = hipMalloc(out, bytes);
         stat_malloc_ns_ += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
         stat_mallocs_++;
-        if (getenv("FEMSHELL_POOL_VERBOSE"))
+        if (pool_verbose())
             fprintf(stderr, "[femshell pool] hipMalloc %.1f MB: %.2f ms\n", (double)bytes / 1048576.0,
                     1e-6 * (double)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count());
         if (e != hipSuccess) { // out of memory with blocks kept (or waiting for the end of a setup): give them back and try once more
@@ -376,13 +379,11 @@ class DevPool {
     static constexpr size_t kArenaMax = 96u << 20; // requests below this come out of an arena
     DevPool()
     {
-        const char *e = getenv("FEMSHELL_POOL_GB");
-        const double gb = e ? atof(e) : 24.0;
+        const double gb = knob_double("FEMSHELL_POOL_GB", 24.0);
         limit_ = gb > 0.0 ? (size_t)(gb * 1073741824.0) : 0;
-        poison_ = getenv("FEMSHELL_POOL_POISON") && atoi(getenv("FEMSHELL_POOL_POISON")) != 0;
-        carve_ = !(getenv("FEMSHELL_POOL_CARVE") && atoi(getenv("FEMSHELL_POOL_CARVE")) == 0); // (0: no carving of kept blocks, A/B runs)
-        const char *a = getenv("FEMSHELL_POOL_ARENA_MB"); // 0: no arenas (every request to the driver, as in round 5)
-        const double mb = a ? atof(a) : 512.0;
+        poison_ = knob_flag("FEMSHELL_POOL_POISON", false);
+        carve_ = knob_flag("FEMSHELL_POOL_CARVE", true); // (0: no carving of kept blocks, A/B runs)
+        const double mb = knob_double("FEMSHELL_POOL_ARENA_MB", 512.0); // 0: no arenas (every request to the driver, as in round 5)
         arena_bytes_ = mb > 0.0 ? std::max((size_t)(mb * 1048576.0), 2 * kArenaMax) : 0;
     }
     // (callers hold m_)

@@ -25,7 +25,7 @@ static_assert(kSliceNodes == 32 && kSliceRows == 192, "kernels assume 32-node sl
 
 static int assemble_grid(const DeviceMatrix &m)
 {
-    static const int cap = grid_cap(getenv("FEMSHELL_ASM_GRID"), 2048); // (plan.hpp: a multiple of 8, at least 8)
+    static const int cap = grid_cap(knob_text("FEMSHELL_ASM_GRID"), 2048); // (plan.hpp: a multiple of 8, at least 8)
     const int g = 8 * ((m.n_slices + 7) / 8);
     return g < cap ? g : cap;
 }
@@ -33,7 +33,7 @@ static int assemble_grid(const DeviceMatrix &m)
 int slice_grid(const DeviceMatrix &m)
 {
     // tuning knob; one slice per workgroup up to 2M node rows: best SpMV rate; more rows share workgroups
-    static const int cap = grid_cap(getenv("FEMSHELL_SLICE_GRID"), 65536);
+    static const int cap = grid_cap(knob_text("FEMSHELL_SLICE_GRID"), 65536);
     const int g = 8 * ((m.n_slices + 7) / 8);
     return g < cap ? g : cap;
 }
@@ -49,10 +49,6 @@ bool launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st, 
 {
     const size_t lds = (size_t)m.lds_bytes;
     const DeviceSections ds = sections ? *sections : DeviceSections();
-    static const int variant = [] {
-        const char *e = getenv("FEMSHELL_ASM_WAVES"); // tuning knob: waves per SIMD the kernel is compiled for
-        return e ? atoi(e) : 2;
-    }();
     const int g = assemble_grid(m);
     auto launch = [&](auto kernel) {
         if (lds > 64 * 1024) // beyond the default dynamic-LDS limit
@@ -65,7 +61,7 @@ bool launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st, 
             int dev = 0, cus = 0;
             if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
                 cus = 256;
-            return grid_cap(getenv("FEMSHELL_ASM_PIPE_GRID"), 8 * ((2 * cus + 7) / 8));
+            return grid_cap(knob_text("FEMSHELL_ASM_PIPE_GRID"), 8 * ((2 * cus + 7) / 8));
         }();
         const int gp = g < pipe_cap ? g : pipe_cap;
         auto launch_pipe = [&](auto kernel) {
@@ -88,16 +84,9 @@ bool launch_assemble(const DeviceMatrix &m, const MatConst &mc, hipStream_t st, 
         else launch(k_assemble<2, 0, false, true>);
         return true;
     }
-    if (m.n_lquad > 0) {
-        launch(k_assemble<2, 0, true>);
-        return true;
-    }
-    switch (variant) {
-    case 1: launch(k_assemble<1, 0, false>); break;
-    case 3: launch(k_assemble<3, 0, false>); break;
-    case 4: launch(k_assemble<4, 0, false>); break;
-    default: launch(k_assemble<2, 0, false>); break;
-    }
+    // (compiled for two waves per SIMD: one is the same code, three and four spill -- profiles/sections_kernel_resources.txt)
+    if (m.n_lquad > 0) launch(k_assemble<2, 0, true>);
+    else launch(k_assemble<2, 0, false>);
     return true;
 }
 

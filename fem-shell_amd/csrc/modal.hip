@@ -204,8 +204,7 @@ void block_product(const DeviceMatrix &m, const double *X, double *Y, int64_t ld
                    int *fused)
 {
     // (FEMSHELL_SPMM_FUSED=0: the column-by-column path with symmetric storage too -- the yardstick of A/B measurements)
-    const char *e = getenv("FEMSHELL_SPMM_FUSED");
-    if (!(e && atoi(e) == 0) && launch_spmm_sym(m, X, Y, ld, n_cols, tbuf, plane, st)) {
+    if (knob_flag("FEMSHELL_SPMM_FUSED", true) && launch_spmm_sym(m, X, Y, ld, n_cols, tbuf, plane, st)) {
         if (fused) *fused = 1;
         return;
     }

@@ -34,8 +34,7 @@ void *raw_allocate(std::size_t bytes)
     if (p == nullptr) throw std::bad_alloc();
     // FEMSHELL_HUGEPAGES=0: no advice (a host whose memory is so fragmented that the kernel compacts it inside the page faults)
     // (read per allocation -- these are at least 4 MiB each --: the tests switch it inside one process)
-    const char *env = getenv("FEMSHELL_HUGEPAGES");
-    const bool advise = !(env && atoi(env) == 0);
+    const bool advise = knob_flag("FEMSHELL_HUGEPAGES", true);
     if (advise) (void)madvise(p, rounded, MADV_HUGEPAGE); // (advice: refused or unavailable, the array is an ordinary one)
     return p;
 }
@@ -86,8 +85,7 @@ void set_host_share(int ranks_on_this_host) { g_host_share.store(ranks_on_this_h
 // the ranks on the host; at most 64
 int host_thread_count()
 {
-    const char *e = getenv("FEMSHELL_HOST_THREADS"); // (read per call: tests switch it inside one process)
-    const int from_env = e ? atoi(e) : 0;
+    const int from_env = (int)knob_long("FEMSHELL_HOST_THREADS", 0); // (read per call: tests switch it inside one process)
     int t = from_env > 0 ? from_env : available_cpus() / g_host_share.load();
     return t < 1 ? 1 : (t > 64 ? 64 : t);
 }
@@ -154,7 +152,7 @@ void run_on_host_threads(int nt, const std::function<void(int)> &task)
         task(0);
         return;
     }
-    static const bool pool_off = getenv("FEMSHELL_HOST_POOL") && atoi(getenv("FEMSHELL_HOST_POOL")) == 0;
+    static const bool pool_off = !knob_flag("FEMSHELL_HOST_POOL", true);
     if (t_pool_worker) { // a call from inside a task: the cores are taken, the tasks run one after the other
         for (int t = 0; t < nt; t++) task(t);
         return;
@@ -252,11 +250,7 @@ static int owner_of(int32_t node, const std::vector<int32_t> &bounds)
     return (int)(std::upper_bound(bounds.begin(), bounds.end(), node) - bounds.begin()) - 1;
 }
 
-bool default_symmetric_storage()
-{
-    const char *e = getenv("FEMSHELL_SYMMETRIC");
-    return !(e && atoi(e) == 0);
-}
+bool default_symmetric_storage() { return knob_flag("FEMSHELL_SYMMETRIC", true); }
 
 int grid_cap(const char *text, int fallback)
 {
@@ -402,7 +396,7 @@ static int plan_item_pairs()
     // items); with symmetric storage a structured slice has 32 diagonal slots of 6 and 96 off-diagonal slots of 2
     // contributions, and items of 2 (192 equal items, three full waves while the fourth builds records) were measured
     // against items of 3 (160 items): 0.904 vs 0.875 ms -- fewer items and partial-sum rows win, 3 stays
-    static const int item_pairs_env = getenv("FEMSHELL_ITEM_PAIRS") ? atoi(getenv("FEMSHELL_ITEM_PAIRS")) : 0;
+    static const int item_pairs_env = (int)knob_long("FEMSHELL_ITEM_PAIRS", 0);
     return (item_pairs_env >= 1 && item_pairs_env <= kItemPairs) ? item_pairs_env : kItemPairs;
 }
 
@@ -589,7 +583,7 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
 
     // FEMSHELL_PLAN_VERBOSE=1: wall time of the phases below on stderr.  lap(name) opens the phase `name` and prints the
     // time of the one it closes.
-    static const bool verbose = getenv("FEMSHELL_PLAN_VERBOSE") && atoi(getenv("FEMSHELL_PLAN_VERBOSE")) != 0;
+    static const bool verbose = plan_verbose();
     auto t_lap = std::chrono::steady_clock::now();
     const char *open_phase = "input checks";
     auto lap = [&](const char *what) {
@@ -786,7 +780,7 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
         // neighbours there whatever the numbering is (exactly three on the structured grids)
         // (the caller asks for it when the library renumbered the nodes itself; FEMSHELL_SYM_ORIENT=geom|index overrides.
         //  4M-triangle panel, Morton numbering: SpMV 0.466 -> 0.456 ms, Hilbert 0.546 -> 0.453 ms; row-major: same plan)
-        const char *oe = getenv("FEMSHELL_SYM_ORIENT");
+        const char *oe = knob_text("FEMSHELL_SYM_ORIENT");
         const bool geometric = oe ? std::strcmp(oe, "geom") == 0 : geometric_orientation;
         plan_parallel(n_own, 4096, [&](int, int64_t a0, int64_t a1) {
             for (int64_t a = a0; a < a1; a++)
@@ -1132,8 +1126,7 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
         plan_parallel(p.n_slices, 256, [&](int t, int64_t s0, int64_t s1) {
             // local element ids of a slice within this span: bitmap + rank table (FEMSHELL_PLAN_DENSE_SPAN: the tests set 0 to
             // drive the sort-and-search path on small meshes; read per plan)
-            const char *span_env = getenv("FEMSHELL_PLAN_DENSE_SPAN");
-            const int64_t kDenseSpan = span_env ? atoll(span_env) : (int64_t)1 << 18;
+            const int64_t kDenseSpan = knob_long("FEMSHELL_PLAN_DENSE_SPAN", 1l << 18);
             std::vector<int32_t> ids, placed;
             std::vector<uint64_t> bits;
             std::vector<uint16_t> pos_of;
@@ -1247,8 +1240,8 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
     // keeps the two-phase kernel (read per plan).
     p.pipe = false;
     {
-        const char *e = getenv("FEMSHELL_ASM_PIPE");
-        const bool wanted = !(e && atoi(e) == 0);
+        const long pipe_knob = knob_long("FEMSHELL_ASM_PIPE", 1);
+        const bool wanted = pipe_knob != 0;
         int32_t max_cnt = 0;
         for (size_t i = 0; i + 1 < p.pair_ptr.size(); i++) max_cnt = std::max(max_cnt, p.pair_ptr[i + 1] - p.pair_ptr[i]);
         p.pipe = wanted && !p.slice_elem_nodes.empty() && // (the kernel's idle lanes read a valid element: there must be one)
@@ -1261,7 +1254,7 @@ bool build_plan(int32_t n_nodes, const double *xyz, int32_t n_tri, const int32_t
         // against 4.5 G elements/s at 1M triangles.  A second round per slice (full storage: 192 off-diagonal slots per
         // structured slice) is left to the two-phase kernel.  FEMSHELL_ASM_PIPE=2 takes the layout wherever the kernel can
         // run.
-        if (p.pipe && !(e && atoi(e) == 2)) {
+        if (p.pipe && pipe_knob != 2) {
             std::vector<int64_t> part((size_t)plan_chunks(p.n_slices, 256), 0);
             plan_parallel(p.n_slices, 256, [&](int t, int64_t s0, int64_t s1) {
                 int64_t r = 0;

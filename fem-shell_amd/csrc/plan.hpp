@@ -28,6 +28,8 @@
 #include <functional>
 #include <vector>
 
+#include "knobs.hpp"
+
 namespace femshell {
 
 // called between the phases of build_plan when set: libfemshell points it at CommWatch::heartbeat (comm.hpp), so that a long
@@ -200,5 +202,7 @@ bool default_symmetric_storage();
 // ends.  So: the value rounded down to a multiple of 8, never less than 8; text that is no whole positive number (or absent)
 // gives fallback, held to the same rule.
 int grid_cap(const char *text, int fallback);
+// FEMSHELL_PLAN_VERBOSE=1: the symbolic phase and femshell_set_mesh print their laps to stderr
+inline bool plan_verbose() { return knob_flag("FEMSHELL_PLAN_VERBOSE", false); }
 
 } // namespace femshell

@@ -8,6 +8,7 @@
 
 #include "amg.hpp"
 #include "errors.hpp"
+#include "knobs.hpp"
 #include "plan.hpp"
 #include "reorder.hpp"
 
@@ -38,6 +39,9 @@ int femshell_plan_create(int32_t n_nodes, const double *xyz, int32_t n_tri, cons
 void femshell_plan_destroy(femshell_plan *plan) { delete plan; }
 
 int32_t femshell_grid_cap(const char *text, int32_t fallback) { return grid_cap(text, fallback); }
+
+long femshell_knob_long(const char *name, long dflt) { return knob_long(name, dflt); }
+int femshell_knob_flag(const char *name, int dflt) { return knob_flag(name, dflt != 0) ? 1 : 0; }
 
 int femshell_plan_info(const femshell_plan *plan, int64_t *info)
 {

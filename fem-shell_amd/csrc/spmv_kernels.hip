@@ -369,14 +369,8 @@ __global__ __launch_bounds__(64) void k_spmv_sym(DeviceMatrix m, const double *_
 // level 0 is 72 MB: 0.0603 -> 0.0614 s -- an operator that small is gone from the L2s anyway and costs the vectors their place.
 static bool operator_fits_the_caches(const DeviceMatrix &m)
 {
-    static const double max_mb = [] {
-        const char *e = getenv("FEMSHELL_SPMV_CACHED_MB");
-        return e ? atof(e) : 300.0;
-    }();
-    static const double min_mb = [] {
-        const char *e = getenv("FEMSHELL_SPMV_CACHED_MIN_MB");
-        return e ? atof(e) : 128.0;
-    }();
+    static const double max_mb = knob_double("FEMSHELL_SPMV_CACHED_MB", 300.0);
+    static const double min_mb = knob_double("FEMSHELL_SPMV_CACHED_MIN_MB", 128.0);
     const double bytes_per_value = m.vals32 != nullptr ? 4.0 : 8.0;
     const double mb = (double)m.n_slices * m.max_slice_width * kSliceNodes * 36.0 * bytes_per_value * 1e-6;
     return mb <= max_mb && mb >= min_mb;
@@ -633,10 +627,7 @@ __global__ __launch_bounds__(64) void k_spmv_node(DeviceMatrix m, const double *
 // rows narrower than this go through k_spmv_node (FEMSHELL_SPMV_NODE_WIDTH; 0 = never)
 static int spmv_node_width()
 {
-    static const int w = [] {
-        const char *e = getenv("FEMSHELL_SPMV_NODE_WIDTH");
-        return e ? atoi(e) : 8;
-    }();
+    static const int w = (int)knob_long("FEMSHELL_SPMV_NODE_WIDTH", 8);
     return w;
 }
 
@@ -646,10 +637,7 @@ constexpr int kSpmvPanel = 64; // block slots of x staged in LDS at a time by k_
 static void spmv_dispatch(const DeviceMatrix &m, const double *x, double *y, double *partials, const CgScalars *s,
                           const int32_t *order, int count, int grid, hipStream_t st, const SpmvEpilogue &e)
 {
-    static const int chunk = [] {
-        const char *c = getenv("FEMSHELL_SPMV_CHUNK"); // tuning knob: block slots loaded together
-        return c ? atoi(c) : 8;
-    }();
+    static const int chunk = (int)knob_long("FEMSHELL_SPMV_CHUNK", 8); // tuning knob: block slots loaded together
     const dim3 g(grid), b(192);
     // x of the block columns, at most kSpmvPanel slots at a time (96 KiB of the CU's 160)
     const int panel = m.max_slice_width < kSpmvPanel ? (m.max_slice_width > 0 ? m.max_slice_width : 1) : kSpmvPanel;

@@ -134,6 +134,11 @@ int femshell_reorder_host(int32_t kind, int32_t n_nodes, const double *xyz, int3
  * is no whole positive number gives the fallback (csrc/plan.hpp grid_cap) */
 int32_t femshell_grid_cap(const char *text, int32_t fallback);
 
+/* how the library reads the environment variable `name` as a number and as a switch (csrc/knobs.hpp): unset gives dflt; set
+ * gives atol of the text -- text that is no number gives 0 -- and, as a switch, whether that number is not 0 */
+long femshell_knob_long(const char *name, long dflt);
+int femshell_knob_flag(const char *name, int dflt);
+
 /* symmetric storage of a square operator (coarse multigrid levels): diagonal + upper blocks in the sliced ELL arrays and
  * the in-lists of the transposed products; returns the total slots, *in_total receives the in-list entries; arrays may
  * be NULL for a sizing call */
