@@ -34,4 +34,7 @@ from .binding import (  # noqa: F401
     build_plan,
     plan_node_normals,
     reorder_host,
+    DERIVED_PRODUCTS,
+    STATE_CHANGES,
+    stale_after,
 )

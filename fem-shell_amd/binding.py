@@ -889,3 +889,22 @@ def knob_flag(name, default):
     L.femshell_knob_flag.argtypes = [C.c_char_p, C.c_int]
     L.femshell_knob_flag.restype = C.c_int
     return bool(L.femshell_knob_flag(str(name).encode(), int(bool(default))))
+
+
+# the derived products of a context and the changes that make them stale, in the order of csrc/derived.hpp
+DERIVED_PRODUCTS = ["K", "F", "Jacobi", "Hierarchy", "Mass", "Ubar", "Solution", "WarmStart", "Fp64Only"]
+STATE_CHANGES = ["mesh", "dirichlet", "sections", "sections_cleared_none_set", "loads", "prescribed", "density", "pc_options",
+                 "assembled", "matrix_shifted", "dynamics_begin", "matrix_spoiled", "dynamics_end", "fp64_fallback"]
+
+
+def stale_after(change):
+    """The derived products of a context (names of DERIVED_PRODUCTS, a frozenset) that the change `change` (a name of
+    STATE_CHANGES, or its number) makes stale (femshell_stale_after).  CPU only."""
+    L = load_library()
+    L.femshell_stale_after.argtypes = [C.c_int32]
+    L.femshell_stale_after.restype = C.c_int32
+    mask = int(L.femshell_stale_after(STATE_CHANGES.index(change) if isinstance(change, str) else int(change)))
+    if mask < 0:
+        raise FemShellError(-1, "femshell_stale_after: no such change")
+    assert mask >> len(DERIVED_PRODUCTS) == 0
+    return frozenset(name for bit, name in enumerate(DERIVED_PRODUCTS) if mask >> bit & 1)

@@ -1,7 +1,7 @@
-// api.cpp -- the C ABI of libfemshell (include/femshell.h): context, communication, mesh and the data on it, assembly, solve,
-// export and products.  Dynamics: api_dynamics.cpp; modal analysis: api_modal.cpp; element resultants: api_resultants.cpp;
-// measurement hooks: api_timing.cpp; node ids and
-// node vectors across the boundary: node_io.cpp.  The CG driver is cg_driver.cpp, the plan inspection entry points plan_api.cpp.
+// api.cpp -- the C ABI of libfemshell (include/femshell.h): context, communication, mesh and the data on it, solve, export and
+// products.  What of a context's derived state is valid, and the assembly and setups that make it so: api_state.cpp; dynamics:
+// api_dynamics.cpp; modal analysis: api_modal.cpp; element resultants: api_resultants.cpp; measurement hooks: api_timing.cpp;
+// node ids and node vectors across the boundary: node_io.cpp.  The CG driver is cg_driver.cpp, the plan inspection entry points plan_api.cpp.
 // All arithmetic of the hot path runs in the kernels of the .hip files; there is no CPU fallback anywhere in this library.
 #include "api_internal.hpp"
 #include "reorder.hpp"
@@ -115,7 +115,7 @@ static int agreed_outcome(femshell_ctx *c, const char *what, bool neutral)
 // assembly and after the block-Jacobi setup); all of them leave with an error when any of them has one.
 // (neutral: the caller is neither the assembly nor the block-Jacobi setup -- the healthy ranks then report "failed on N
 //  other rank(s)" with FEMSHELL_ERR_COMM instead of guessing at a degenerate element or a non-SPD block over there)
-static int agree_status(femshell_ctx *c, int local_rc, const char *what, bool neutral = false)
+int agree_status(femshell_ctx *c, int local_rc, const char *what, bool neutral)
 {
     if (!c->comm.active()) return local_rc;
     const std::string local_msg = last_err();
@@ -135,7 +135,7 @@ static int agree_status(femshell_ctx *c, int local_rc, const char *what, bool ne
 // cross-rank agreement in ONE stream synchronisation -- a kernel turns the status word into the two agreement counters,
 // the all-reduce runs on the device, status and counters come back together.  (check_status followed by agree_status is
 // two synchronisations and three copies; on 8 ranks a 0.1 ms assembly step would spend as long agreeing as assembling.)
-static int check_and_agree(femshell_ctx *c, const char *what)
+int check_and_agree(femshell_ctx *c, const char *what)
 {
     if (!c->comm.active()) return check_status(c, what);
     FS_HIP(c->agree.alloc(2));
@@ -190,147 +190,6 @@ static int upload_node_data(femshell_ctx *c, int what)
     return FEMSHELL_OK;
 }
 
-// status and timing of an assembly that femshell_assemble_async enqueued (nothing where none is pending): every entry point that
-// reads results, changes inputs or synchronises calls this first
-int finish_pending_assembly(femshell_ctx *c)
-{
-    if (!c->assembly_pending) return FEMSHELL_OK;
-    c->assembly_pending = false;
-    int rc = select_device(c);
-    if (rc) return rc;
-    rc = check_and_agree(c, "femshell_assemble_async");
-    if (rc) {
-        c->matrix_valid = false;
-        c->rhs_valid = false;
-        return rc;
-    }
-    float ms = 0.f;
-    FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last_assemble_s = 1e-3 * ms;
-    return FEMSHELL_OK;
-}
-
-// femshell_set_mesh and femshell_set_sections forget the densities (and with them the mass matrix in HBM)
-static void forget_density(femshell_ctx *c)
-{
-    c->have_density = c->mass_valid = false;
-    c->rho = 0.0;
-    c->sec_rho.clear();
-}
-
-int do_assemble(femshell_ctx *c, bool wait)
-{
-    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: no mesh set");
-    TraceRange trace("femshell_assemble");
-    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_assemble (agreement of the ranks on the outcome)");
-    int rc = select_device(c);
-    if (rc) return rc;
-    if (c->assembly_pending && wait) { // (async after async: one status word collects both)
-        rc = finish_pending_assembly(c);
-        if (rc) return rc;
-    }
-    // (the event pair costs the synchronous call its two records: without it assemble_seconds is the host's clock around launch
-    //  and synchronisation; an enqueued assembly always carries the pair -- nobody else could time it)
-    // (MEASURED, round 6, profiles/r06_sync_step_ab_raw.txt: neither the status word in mapped host memory, nor dropping the event
-    //  pair, nor polling a word that a one-lane kernel writes behind the assembly instead of synchronising the stream, nor polled
-    //  completion signals move the 40-50 us a synchronous step costs beyond its kernel: it is launch latency on an idle queue)
-    const bool events = c->asm_events || !wait;
-    const auto t_host = std::chrono::steady_clock::now();
-    if (events) FS_HIP(hipEventRecord(c->ev0, c->stream));
-    c->dm.rhs_loads = c->loads.p;
-    c->dm.rhs_F = c->F.p;
-    if (!launch_assemble(c->dm, c->mc, c->stream, c->sections_or_null())) // K and F (k_rhs alone serves changes of the loads)
-        return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: the context's sections have no table in HBM");
-    // (dynamics is active: the matrix in HBM is K_eff = K + shift M, also when K is built again -- FEMSHELL_REASSEMBLE_EACH_SOLVE)
-    if (c->dyn.active) launch_mass_shift(c->dm, c->mass.p, c->dyn.k.shift, c->stream);
-    if (events) FS_HIP(hipEventRecord(c->ev1, c->stream));
-    FS_HIP(hipGetLastError());
-    if (c->have_prescribed) { // (the assembly kernel wrote the masked loads: F of the prescribed values behind it)
-        rc = do_rhs(c);
-        if (rc) return rc;
-    }
-    if (wait) {
-        rc = check_and_agree(c, "femshell_assemble");
-        if (rc) return rc;
-        if (events) {
-            float ms = 0.f;
-            FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            c->last_assemble_s = 1e-3 * ms;
-        } else {
-            c->last_assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_host).count();
-        }
-    } else {
-        c->assembly_pending = true; // (a failed element leaves its mark in the status word until someone looks)
-    }
-    c->matrix_valid = true;
-    c->rhs_valid = true;
-    c->jacobi_valid = false;
-    c->amg.reset(); // the multigrid hierarchy belongs to the previous K
-    return FEMSHELL_OK;
-}
-
-// u_bar of the prescribed values and the Dirichlet set in force (femshell_set_prescribed): the entries at fixed dofs, zero
-// elsewhere, on the host and in HBM.  Single-rank contexts only: the owned rows are all rows.
-int resolve_prescribed(femshell_ctx *c)
-{
-    if (c->ubar_valid) return FEMSHELL_OK;
-    const Plan &p = c->plan;
-    c->ubar_host.assign((size_t)p.n_nodes * 6, 0.0);
-    bool nonzero = false;
-    for (int32_t a = 0; a < p.n_nodes; a++) {
-        const uint32_t fixed = c->dmask_global[(size_t)a];
-        for (int v = 0; v < 6 && fixed; v++)
-            if ((fixed >> v) & 1u) {
-                const double val = c->prescribed_global[6ull * (size_t)a + v];
-                c->ubar_host[6ull * (size_t)a + v] = val;
-                nonzero = nonzero || val != 0.0;
-            }
-    }
-    FS_HIP(c->ubar.alloc((size_t)p.n_local_nodes() * 6));
-    FS_HIP(c->ubar.zero(c->stream));
-    FS_HIP(hipMemcpyAsync(c->ubar.p, c->ubar_host.data(), (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream));
-    c->ubar_nonzero = nonzero;
-    c->ubar_valid = true;
-    return FEMSHELL_OK;
-}
-
-int do_rhs(femshell_ctx *c)
-{
-    if (c->have_prescribed) {
-        // F = mask(loads - K_unc u_bar): one launch of the matrix-free product with the unconstrained element matrices, the
-        // masked combine in its epilogue.  (No fixed dof carries a non-zero value: the masked copy below, as without the call.)
-        const int rc = resolve_prescribed(c);
-        if (rc) return rc;
-        if (c->ubar_nonzero) {
-            launch_element_product(c->dm, c->mc, c->sections_or_null(), c->ubar.p, nullptr, c->loads.p, c->F.p, true, c->stream);
-            FS_HIP(hipGetLastError());
-            c->rhs_valid = true;
-            return FEMSHELL_OK;
-        }
-    }
-    launch_rhs(c->dm, c->loads.p, c->F.p, c->stream);
-    FS_HIP(hipGetLastError());
-    c->rhs_valid = true;
-    return FEMSHELL_OK;
-}
-
-int do_jacobi(femshell_ctx *c)
-{
-    TraceRange trace("femshell block-Jacobi setup");
-    FS_HIP(hipEventRecord(c->ev0, c->stream));
-    launch_block_jacobi(c->dm, c->stream);
-    FS_HIP(hipEventRecord(c->ev1, c->stream));
-    FS_HIP(hipGetLastError());
-    int rc = check_and_agree(c, "block-Jacobi setup");
-    if (rc) return rc;
-    float ms = 0.f;
-    FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-    c->last_setup_s = 1e-3 * ms;
-    c->jacobi_valid = true;
-    return FEMSHELL_OK;
-}
-
 double wall_s()
 {
     using namespace std::chrono;
@@ -347,54 +206,6 @@ bool all_finite(const double *x, int64_t n)
     return bad.load() == 0;
 }
 
-// What a solve needs in HBM before its Krylov loop: K and F assembled (again, with FEMSHELL_REASSEMBLE_EACH_SOLVE), the
-// block-Jacobi inverse.  *asm_s / *setup_s: seconds of the assembly and of the block-Jacobi setup done here (0: none needed).
-static int prepare_system(femshell_ctx *c, double *asm_s, double *setup_s)
-{
-    int rc = FEMSHELL_OK;
-    *asm_s = *setup_s = 0.0;
-    if (!c->matrix_valid || (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)) {
-        rc = do_assemble(c);
-        if (rc) return rc;
-        *asm_s = c->last_assemble_s;
-    } else if (!c->rhs_valid) {
-        rc = do_rhs(c);
-        if (rc) return rc;
-    }
-    if (!c->jacobi_valid) {
-        rc = do_jacobi(c);
-        if (rc) return rc;
-        *setup_s = c->last_setup_s;
-    }
-    return rc;
-}
-
-// The multigrid hierarchy of the K in HBM, built where there is none (first solve, K changed, the all-FP64 rebuild): on one rank,
-// or row-partitioned and collective when the context has a communicator.  *pc_setup_s += its seconds.
-int ensure_amg_hierarchy(femshell_ctx *c, double *pc_setup_s)
-{
-    if (c->amg && c->amg->valid) return FEMSHELL_OK;
-    int rc = FEMSHELL_OK;
-    if (c->comm.active()) {
-        const double t0 = wall_s();
-        // row-partitioned hierarchy (amg_dist.cpp); a failure only one rank sees must reach the others
-        rc = agree_status(c, amg_setup_dist(c), "multigrid setup", true);
-        if (rc) {
-            c->amg.reset();
-            return rc;
-        }
-        *pc_setup_s += wall_s() - t0;
-    } else {
-        rc = amg_setup(c);
-        if (rc) {
-            c->amg.reset();
-            return rc;
-        }
-        *pc_setup_s += c->amg->setup_seconds;
-    }
-    return rc;
-}
-
 // dynamic: the solve of a Newmark step -- the right-hand side is F_eff, built from the F of the loads in force and the
 // committed state by k_newmark_rhs behind the (re)assembly, instead of F itself
 int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic)
@@ -408,10 +219,9 @@ int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, fe
     CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_solve (halo exchanges and all-reduces of the solve)");
     int rc = select_device(c);
     if (rc) return rc;
-    double asm_s = 0.0, setup_s = 0.0;
-    rc = prepare_system(c, &asm_s, &setup_s);
+    Timings t;
+    rc = ensure(c, kK | kF | kJacobi, &t, /*solving=*/true);
     if (rc) return rc;
-    double pc_setup_s = 0.0;
     const bool use_amg = c->pc.type == FEMSHELL_PC_AMG;
     hipStream_t st = c->stream;
     TraceRange trace_cg(use_amg ? "femshell_solve: multigrid-preconditioned CG" : "femshell_solve: block-Jacobi CG");
@@ -432,10 +242,7 @@ int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, fe
     bool fp64_fallback = false;
     float ms_abandoned = 0.f; // device time of an attempt that ended in the breakdown below: part of solve_seconds
     for (int attempt = 0;; attempt++) {
-        if (use_amg) {
-            rc = ensure_amg_hierarchy(c, &pc_setup_s);
-            if (rc) return rc;
-        }
+        if (use_amg && (rc = ensure(c, kHierarchy, &t))) return rc; // (first solve, K changed, the all-FP64 rebuild below)
         // a previous solve leaves done = 1 behind; the reduction launch in front of an all-reduce carries no phase and
         // would skip its work on it (multi-rank re-solves, e.g. every coupling iteration)
         FS_HIP(hipEventRecord(c->ev0, st)); // (behind the multigrid setup: solve_seconds is the time of the Krylov loop)
@@ -458,8 +265,7 @@ int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, fe
             FS_HIP(hipEventRecord(c->ev1, st));
             FS_HIP(hipEventSynchronize(c->ev1));
             FS_HIP(hipEventElapsedTime(&ms_abandoned, c->ev0, c->ev1));
-            c->amg_fp64_only = true;
-            c->amg.reset();
+            invalidate(c, Change::fp64_fallback);
             fp64_fallback = true;
             continue;
         }
@@ -502,8 +308,8 @@ int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, fe
         info->converged = recurrence_converged ? 1 : 0;
         info->rel_residual = hs.bb > 0.0 ? std::sqrt(recurrence_rr / hs.bb) : 0.0;
         info->true_rel_residual = true_rel;
-        info->assemble_seconds = asm_s;
-        info->setup_seconds = setup_s;
+        info->assemble_seconds = t.assemble_s;
+        info->setup_seconds = t.setup_s;
         info->solve_seconds = 1e-3 * ms;
         // (multigrid: the Krylov product, the update with its start of the smoothing, the two dot products and the new direction
         //  around the cycle: x, p, r, q read, x, r, q, z written, D^-1; z, r, q; z, p read, p written)
@@ -512,7 +318,7 @@ int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, fe
                                                        : bytes_spmv(c) + bytes_update(c) + bytes_direction(c);
         info->pc_type = c->pc.type;
         info->amg_levels = use_amg ? (int32_t)c->amg->levels.size() : 0;
-        info->pc_setup_seconds = pc_setup_s;
+        info->pc_setup_seconds = t.pc_setup_s;
         info->operator_complexity = 0.0;
         info->refine_passes_done = use_amg ? c->refine.passes : 0;
         info->pc_fp64_fallback = fp64_fallback ? 1 : 0;
@@ -771,7 +577,7 @@ int femshell_destroy(femshell_ctx *c)
     if (!c) return FEMSHELL_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    c->amg.reset();
+    invalidate(c, Change::mesh); // (the hierarchy goes before the communicator and the streams)
     comm_destroy(c->comm);
     if (c->halo_stream) (void)hipStreamSynchronize(c->halo_stream);
     if (c->ev_p_ready) (void)hipEventDestroy(c->ev_p_ready);
@@ -883,13 +689,15 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     };
     if (!all_finite(xyz, 3ll * n_nodes)) return set_err(FEMSHELL_ERR_MESH, "femshell_set_mesh: non-finite coordinate");
     std::string e;
-    c->have_mesh = false;
+    // From here on the plan and the buffers of the previous mesh are replaced piece by piece, and the call can still be refused:
+    // nothing derived from that mesh is valid any more, whatever happens below.
+    invalidate(c, Change::mesh);
     c->have_sections = false; // (the element count may change)
     c->n_sections = 0;
     c->sec_thickness.clear();
     forget_density(c);
     c->dyn.reset(); // (a new mesh ends dynamics)
-    c->have_prescribed = c->ubar_valid = c->ubar_nonzero = false; // (... and forgets the prescribed displacements)
+    c->have_prescribed = c->ubar_nonzero = false; // (... and forgets the prescribed displacements)
     c->prescribed_global.clear();
     c->ubar_host.clear();
     c->ubar.release();
@@ -897,8 +705,6 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     c->sec_table.release();
     c->slice_elem_section.release();
     c->elem_section.release();
-    c->warm_next = false;
-    c->amg_fp64_only = false;
     c->perm.clear();
     c->iperm.clear();
     std::vector<double> xyz_r;
@@ -1067,7 +873,6 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     FS_HIP(hipStreamSynchronize(st));
     part_done("allocations, fills, node data");
     c->have_mesh = true;
-    c->matrix_valid = c->rhs_valid = c->jacobi_valid = c->have_solution = false;
     return FEMSHELL_OK;
 }
 
@@ -1115,8 +920,7 @@ int femshell_set_dirichlet(femshell_ctx *c, int32_t n, const int32_t *node_ids, 
     c->dmask_global.swap(m);
     rc = upload_node_data(c, kNodeMasks);
     if (rc) return rc;
-    c->matrix_valid = c->rhs_valid = c->jacobi_valid = false;
-    c->ubar_valid = false; // (which of the prescribed values count is decided by the new set)
+    invalidate(c, Change::dirichlet); // (u_bar too: which of the prescribed values count is decided by the new set)
     return FEMSHELL_OK;
 }
 
@@ -1132,10 +936,10 @@ int femshell_set_prescribed(femshell_ctx *c, int32_t n, const int32_t *node_ids,
     if (n < 0) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: n < 0");
     const int32_t nn = c->plan.n_nodes;
     if (n == 0) { // clears
-        c->have_prescribed = c->ubar_valid = c->ubar_nonzero = false;
+        c->have_prescribed = c->ubar_nonzero = false;
         c->prescribed_global.clear();
         c->ubar_host.clear();
-        c->rhs_valid = false;
+        invalidate(c, Change::prescribed);
         return FEMSHELL_OK;
     }
     if (!node_ids && n != nn) return set_err(FEMSHELL_ERR_INVALID, "femshell_set_prescribed: dense form needs n == n_nodes");
@@ -1150,8 +954,7 @@ int femshell_set_prescribed(femshell_ctx *c, int32_t n, const int32_t *node_ids,
     }
     c->prescribed_global.swap(l);
     c->have_prescribed = true;
-    c->ubar_valid = false;
-    c->rhs_valid = false; // (K, block-Jacobi and the multigrid hierarchy are kept)
+    invalidate(c, Change::prescribed); // (K, block-Jacobi and the multigrid hierarchy are kept)
     return FEMSHELL_OK;
 }
 
@@ -1220,6 +1023,7 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
     std::string err;
     if (n_sections == 0) {
         forget_density(c);
+        invalidate(c, Change::sections_cleared_none_set);
         if (!c->have_sections) return FEMSHELL_OK; // nothing was set: nothing else changes
         if (c->pipe_without_sections && !p.pipe) { // back to the layout femshell_set_mesh chose: K is again what it was, bit for bit
             if (!repack_assembly_items(&p, true, &err)) return set_err(FEMSHELL_ERR_MESH, "femshell_set_sections: " + err);
@@ -1236,7 +1040,7 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
         c->sec_table.release();
         c->slice_elem_section.release();
         c->elem_section.release();
-        c->matrix_valid = c->rhs_valid = c->jacobi_valid = false;
+        invalidate(c, Change::sections);
         return FEMSHELL_OK;
     }
     // ---- the table, and the index of every local element and of every entry of the slices' element lists (ghost elements of a
@@ -1287,7 +1091,7 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
     c->sec_thickness.resize((size_t)n_sections);
     for (int32_t s = 0; s < n_sections; s++) c->sec_thickness[(size_t)s] = sections[s].thickness;
     forget_density(c); // (paired with the sections that were replaced)
-    c->matrix_valid = c->rhs_valid = c->jacobi_valid = false; // as a change of the Dirichlet set
+    invalidate(c, Change::sections);
     return FEMSHELL_OK;
 }
 
@@ -1325,7 +1129,7 @@ int femshell_set_loads(femshell_ctx *c, int32_t n, const int32_t *node_ids, cons
     c->loads_global.swap(l);
     rc = upload_node_data(c, kNodeLoads);
     if (rc) return rc;
-    c->rhs_valid = false;
+    invalidate(c, Change::loads);
     return FEMSHELL_OK;
 }
 
@@ -1377,8 +1181,7 @@ int femshell_set_preconditioner(femshell_ctx *c, const femshell_pc_options *opt)
     if (same_hierarchy && c->amg && c->amg->valid) {
         c->amg->opt = *opt;
     } else {
-        c->amg.reset();
-        c->amg_fp64_only = false;
+        invalidate(c, Change::pc_options);
     }
     return FEMSHELL_OK;
 }
@@ -1632,15 +1435,13 @@ int femshell_export_bsr(femshell_ctx *c, int32_t *rowptr, int32_t *colidx, doubl
 {
     if (!c || !rowptr || !colidx || !vals) return set_err(FEMSHELL_ERR_INVALID, "femshell_export_bsr: null argument");
     if (const int prc = finish_pending_assembly(c)) return prc;
-    if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_export_bsr: call femshell_assemble first");
+    if (!have(c, kK)) return set_err(FEMSHELL_ERR_INVALID, "femshell_export_bsr: call femshell_assemble first");
     int rc = select_device(c);
     if (rc) return rc;
     const Plan &p = c->plan;
     if (F) {
-        if (!c->rhs_valid) {
-            rc = do_rhs(c);
-            if (rc) return rc;
-        }
+        rc = ensure(c, kF);
+        if (rc) return rc;
         FS_HIP(hipMemcpyAsync(F, c->F.p, (size_t)p.n_own * 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     Bsr A;
@@ -1691,7 +1492,7 @@ int femshell_spmv(femshell_ctx *c, const double *x, double *y)
 {
     if (!c || !x || !y) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmv: null argument");
     if (const int prc = finish_pending_assembly(c)) return prc;
-    if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmv: call femshell_assemble first");
+    if (!have(c, kK)) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmv: call femshell_assemble first");
     if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_spmv: single-rank contexts only");
     int rc = select_device(c);
     if (rc) return rc;
@@ -1756,14 +1557,12 @@ int femshell_residual(femshell_ctx *c, const double *x, double *r)
 {
     if (!c || !x || !r) return set_err(FEMSHELL_ERR_INVALID, "femshell_residual: null argument");
     if (const int prc = finish_pending_assembly(c)) return prc;
-    if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_residual: call femshell_assemble first");
+    if (!have(c, kK)) return set_err(FEMSHELL_ERR_INVALID, "femshell_residual: call femshell_assemble first");
     if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_residual: single-rank contexts only");
     int rc = select_device(c);
     if (rc) return rc;
-    if (!c->rhs_valid) {
-        rc = do_rhs(c);
-        if (rc) return rc;
-    }
+    rc = ensure(c, kF);
+    if (rc) return rc;
     ProductBuffers b;
     rc = b.upload(c, NodeOrder::caller, x);
     if (rc) return rc;
@@ -1783,9 +1582,7 @@ int femshell_pc_apply(femshell_ctx *c, const double *r, double *z)
     CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_pc_apply (halo exchanges and all-reduces of one cycle)");
     int rc = select_device(c);
     if (rc) return rc;
-    double asm_s = 0.0, setup_s = 0.0, pc_setup_s = 0.0;
-    rc = prepare_system(c, &asm_s, &setup_s);
-    if (!rc) rc = ensure_amg_hierarchy(c, &pc_setup_s);
+    rc = ensure(c, kK | kF | kJacobi | kHierarchy, nullptr, /*solving=*/true);
     if (rc) return rc;
     // one rank: r and z in the caller's numbering; a row partition: the rank's owned rows as they lie in HBM, in and out
     const NodeOrder order = c->comm.active() ? NodeOrder::internal : NodeOrder::caller;

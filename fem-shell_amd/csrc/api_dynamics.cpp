@@ -5,35 +5,6 @@
 
 using namespace femshell;
 
-namespace femshell {
-
-// the diagonal of the lumped mass matrix of the owned rows in HBM (c->mass), computed where it is not there yet
-int ensure_mass(femshell_ctx *c)
-{
-    if (c->mass_valid) return FEMSHELL_OK;
-    const Plan &p = c->plan;
-    hipStream_t st = c->stream;
-    FS_HIP(c->mass.alloc((size_t)p.n_pad * 6));
-    const double2 *sec = nullptr;
-    if (c->have_sections) {
-        std::vector<double2> table((size_t)c->n_sections);
-        for (int32_t s = 0; s < c->n_sections; s++) {
-            const double rho = c->sec_rho.empty() ? c->rho : c->sec_rho[(size_t)s], t = c->sec_thickness[(size_t)s];
-            table[(size_t)s] = make_double2(rho * t, rho * t * t * t / 12.0);
-        }
-        FS_HIP(c->sec_mass.upload(table, st));
-        FS_HIP(hipStreamSynchronize(st)); // the host table goes out of scope
-        sec = c->sec_mass.p;
-    }
-    const double t = c->cfg.thickness;
-    launch_lumped_mass(c->dm, make_double2(c->rho * t, c->rho * t * t * t / 12.0), sec, c->ds.slice_elem_section, c->mass.p, st);
-    FS_HIP(hipGetLastError());
-    c->mass_valid = true;
-    return FEMSHELL_OK;
-}
-
-} // namespace femshell
-
 extern "C" {
 
 int femshell_set_density(femshell_ctx *c, double rho, int32_t n_sections, const double *section_rho)
@@ -58,7 +29,7 @@ int femshell_set_density(femshell_ctx *c, double rho, int32_t n_sections, const 
         c->rho = 0.0;
     }
     c->have_density = true;
-    c->mass_valid = false;
+    invalidate(c, Change::density);
     return FEMSHELL_OK;
 }
 
@@ -69,7 +40,7 @@ int femshell_lumped_mass(femshell_ctx *c, double *m6_out)
     if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_lumped_mass: no density set (femshell_set_density)");
     int rc = select_device(c);
     if (rc) return rc;
-    rc = ensure_mass(c);
+    rc = ensure(c, kMass);
     if (rc) return rc;
     return gather_node_vector(c, c->mass.p, m6_out);
 }
@@ -106,10 +77,7 @@ int femshell_dynamics_begin(femshell_ctx *c, const femshell_dynamics_options *op
     CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_dynamics_begin (assembly, halo exchange of K u0)");
     int rc = select_device(c);
     if (rc) return rc;
-    rc = ensure_mass(c);
-    if (rc) return rc;
-    if (!c->matrix_valid) rc = do_assemble(c); // K itself: dynamics is not active yet
-    else if (!c->rhs_valid) rc = do_rhs(c);
+    rc = ensure(c, kMass | kK | kF); // K itself: dynamics is not active yet
     if (rc) return rc;
     hipStream_t st = c->stream;
     femshell_ctx::Dynamics &d = c->dyn;
@@ -154,9 +122,7 @@ int femshell_dynamics_begin(femshell_ctx *c, const femshell_dynamics_options *op
     d.cur = 0;
     d.have_candidate = false;
     d.active = true;
-    c->jacobi_valid = false; // block-Jacobi and the multigrid hierarchy: from K_eff, at the first step
-    c->amg.reset();
-    c->warm_next = false;
+    invalidate(c, Change::dynamics_begin); // block-Jacobi and the multigrid hierarchy: from K_eff, at the first step
     return FEMSHELL_OK;
 }
 
@@ -217,10 +183,8 @@ int femshell_dynamics_energy(femshell_ctx *c, int32_t which, double out[2])
     CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_dynamics_energy (halo exchange and all-reduce)");
     int rc = select_device(c);
     if (rc) return rc;
-    if (!c->matrix_valid) {
-        rc = do_assemble(c);
-        if (rc) return rc;
-    }
+    rc = ensure(c, kK);
+    if (rc) return rc;
     femshell_ctx::Dynamics &d = c->dyn;
     const int i = which == 0 ? d.cur : d.cur ^ 1;
     hipStream_t st = c->stream;
@@ -252,9 +216,7 @@ int femshell_dynamics_end(femshell_ctx *c)
     if (rc) return rc;
     FS_HIP(hipStreamSynchronize(c->stream));
     c->dyn.reset();
-    c->matrix_valid = c->rhs_valid = c->jacobi_valid = false; // K and F again at the next use
-    c->amg.reset();
-    c->warm_next = false;
+    invalidate(c, Change::dynamics_end); // K and F again at the next use
     return FEMSHELL_OK;
 }
 

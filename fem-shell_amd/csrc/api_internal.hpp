@@ -1,11 +1,13 @@
-// api_internal.hpp -- what the files of the C ABI share: api.cpp (context, mesh and its data, assembly, solve, export, products),
-// api_dynamics.cpp, api_modal.cpp, api_resultants.cpp, api_timing.cpp.  Not for the rest of the library.  Each function is described where it is
-// defined: api.cpp, but for ensure_mass (api_dynamics.cpp), the byte models of the hot-path kernels (api_timing.cpp) and what
-// api_resultants.cpp shares with the timing hook.
+// api_internal.hpp -- what the files of the C ABI share: api.cpp (context, mesh and its data, solve, export, products), api_state.cpp
+// (what of the context's derived state is valid, and the functions that make it so), api_dynamics.cpp, api_modal.cpp,
+// api_resultants.cpp, api_timing.cpp.  Not for the rest of the library.  Each function is described where it is defined: api.cpp, but
+// for the block from invalidate to timed_assembly_done (api_state.cpp), the byte models of the hot-path kernels (api_timing.cpp)
+// and what api_resultants.cpp shares with the timing hook.
 #pragma once
 
 #include "amg_device.hpp"
 #include "context.hpp"
+#include "derived.hpp"
 #include "node_io.hpp"
 #include "trace.hpp"
 
@@ -16,14 +18,25 @@ int select_device(femshell_ctx *c);
 double wall_s();
 bool all_finite(const double *x, int64_t n);
 int check_status(femshell_ctx *c, const char *what);
+int check_and_agree(femshell_ctx *c, const char *what);
+int agree_status(femshell_ctx *c, int local_rc, const char *what, bool neutral = false);
+int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic);
+
+// seconds of what ensure() had to do (0: the product was there)
+struct Timings {
+    double assemble_s = 0.0, setup_s = 0.0, pc_setup_s = 0.0;
+};
+void invalidate(femshell_ctx *c, Change what);
+// a mesh is set and every product (Derived bits) named is valid: for the entry points that refuse rather than rebuild
+bool have(const femshell_ctx *c, uint32_t products);
+// brings the products named in `need` up to date: the lumped mass, K (solving: again with FEMSHELL_REASSEMBLE_EACH_SOLVE), F,
+// block-Jacobi, the multigrid hierarchy, in that order; adds the seconds of what it did to *t
+int ensure(femshell_ctx *c, uint32_t need, Timings *t = nullptr, bool solving = false);
 int finish_pending_assembly(femshell_ctx *c);
 int do_assemble(femshell_ctx *c, bool wait = true);
-int do_rhs(femshell_ctx *c);
 int resolve_prescribed(femshell_ctx *c);
-int do_jacobi(femshell_ctx *c);
-int ensure_amg_hierarchy(femshell_ctx *c, double *pc_setup_s);
-int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic);
-int ensure_mass(femshell_ctx *c);
+void forget_density(femshell_ctx *c);
+int timed_assembly_done(femshell_ctx *c);
 
 double bytes_assemble(const femshell_ctx *c);
 double bytes_spmv(const femshell_ctx *c);

@@ -29,7 +29,7 @@ int femshell_modal_gram(femshell_ctx *c, int32_t qa, const double *A, int32_t qb
     if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_modal_gram: single-rank contexts only");
     int rc = select_device(c);
     if (rc) return rc;
-    if (weighted && (rc = ensure_mass(c))) return rc;
+    if (weighted && (rc = ensure(c, kMass))) return rc;
     const size_t ld = (size_t)c->plan.n_local_nodes() * 6;
     DevBuf<double> da, db, partials, dg;
     std::vector<double> stage_a, stage_b; // (synchronised below)
@@ -73,10 +73,7 @@ int femshell_modes(femshell_ctx *c, const femshell_modal_options *opt, double *l
     const double t_begin = wall_s();
     int rc = select_device(c);
     if (rc) return rc;
-    rc = ensure_mass(c);
-    if (rc) return rc;
-    if (!c->matrix_valid || (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)) rc = do_assemble(c); // K itself
-    else if (!c->rhs_valid) rc = do_rhs(c);
+    rc = ensure(c, kMass | kK | kF, nullptr, /*solving=*/true); // K itself
     if (rc) return rc;
     hipStream_t st = c->stream;
     const bool shifted = opt->shift > 0.0;
@@ -84,20 +81,17 @@ int femshell_modes(femshell_ctx *c, const femshell_modal_options *opt, double *l
     auto leave = [&](int code) {
         if (shifted) {
             (void)hipStreamSynchronize(st);
-            c->matrix_valid = c->rhs_valid = c->jacobi_valid = false;
-            c->amg.reset();
+            invalidate(c, Change::matrix_spoiled);
         }
         return code;
     };
     if (shifted) {
         launch_mass_shift(c->dm, c->mass.p, opt->shift, st);
-        c->jacobi_valid = false;
-        c->amg.reset();
+        invalidate(c, Change::matrix_shifted);
         if (hipGetLastError() != hipSuccess) return leave(set_err(FEMSHELL_ERR_HIP, "femshell_modes: the mass shift could not be launched"));
     }
-    double pc_setup_s = 0.0;
-    if (!c->jacobi_valid && (rc = do_jacobi(c))) return leave(rc);
-    if (c->pc.type == FEMSHELL_PC_AMG && (rc = ensure_amg_hierarchy(c, &pc_setup_s))) return leave(rc);
+    Timings t;
+    if ((rc = ensure(c, kJacobi | (c->pc.type == FEMSHELL_PC_AMG ? kHierarchy : 0u), &t))) return leave(rc);
 
     ModalProblem mp;
     mp.dm = c->dm;
@@ -151,7 +145,7 @@ int femshell_modes(femshell_ctx *c, const femshell_modal_options *opt, double *l
         info->seconds_precond = res.seconds_precond;
         info->seconds_gram = res.seconds_gram;
         info->seconds_update = res.seconds_update;
-        info->pc_setup_seconds = pc_setup_s;
+        info->pc_setup_seconds = t.pc_setup_s;
         info->seconds_total = wall_s() - t_begin;
     }
     return leave(FEMSHELL_OK);
@@ -162,7 +156,7 @@ int femshell_spmm(femshell_ctx *c, int32_t n_cols, const double *X, double *Y)
     if (!c || !X || !Y) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: null argument");
     if (n_cols < 1 || n_cols > kModalMaxCols) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: n_cols must be in 1 .. 96");
     if (const int prc = finish_pending_assembly(c)) return prc;
-    if (!c->matrix_valid) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: call femshell_assemble first");
+    if (!have(c, kK)) return set_err(FEMSHELL_ERR_INVALID, "femshell_spmm: call femshell_assemble first");
     if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_spmm: single-rank contexts only");
     int rc = select_device(c);
     if (rc) return rc;

@@ -1,0 +1,266 @@
+// api_state.cpp -- the derived state of a context (derived.hpp): the one place that says what is valid.
+// invalidate() applies the table of derived.hpp after a change, the functions below it make a product valid, ensure() brings
+// what an entry point needs up to date, have() answers for the entry points that refuse instead.  No other file assigns to
+// matrix_valid, rhs_valid, jacobi_valid, mass_valid, ubar_valid or amg_fp64_only or drops the hierarchy; have_solution and
+// warm_next are set where a solve and a hand-over produce them (api.cpp, api_dynamics.cpp) and cleared here only.
+#include "api_internal.hpp"
+
+#include <chrono>
+
+using namespace femshell;
+
+namespace femshell {
+
+void invalidate(femshell_ctx *c, Change what)
+{
+    const uint32_t stale = stale_after(what);
+    if (what == Change::mesh) c->have_mesh = false;
+    if (stale & kK) c->matrix_valid = false;
+    if (stale & kF) c->rhs_valid = false;
+    if (stale & kJacobi) c->jacobi_valid = false;
+    if (stale & kHierarchy) c->amg.reset(); // (its HBM goes back at once)
+    if (stale & kMass) c->mass_valid = false;
+    if (stale & kUbar) c->ubar_valid = false;
+    if (stale & kSolution) c->have_solution = false;
+    if (stale & kWarmStart) c->warm_next = false;
+    if (stale & kFp64Only) c->amg_fp64_only = false;
+    if (what == Change::fp64_fallback) c->amg_fp64_only = true;
+}
+
+bool have(const femshell_ctx *c, uint32_t products)
+{
+    if (!c->have_mesh) return false;
+    const uint32_t valid = (c->matrix_valid ? kK : 0) | (c->rhs_valid ? kF : 0) | (c->jacobi_valid ? kJacobi : 0) |
+                           ((c->amg && c->amg->valid) ? kHierarchy : 0) | (c->mass_valid ? kMass : 0) | (c->ubar_valid ? kUbar : 0) |
+                           (c->have_solution ? kSolution : 0);
+    return (products & ~valid) == 0;
+}
+
+// status and timing of an assembly that femshell_assemble_async enqueued (nothing where none is pending): every entry point that
+// reads results, changes inputs or synchronises calls this first
+int finish_pending_assembly(femshell_ctx *c)
+{
+    if (!c->assembly_pending) return FEMSHELL_OK;
+    c->assembly_pending = false;
+    int rc = select_device(c);
+    if (rc) return rc;
+    rc = check_and_agree(c, "femshell_assemble_async");
+    if (rc) {
+        invalidate(c, Change::matrix_spoiled);
+        return rc;
+    }
+    float ms = 0.f;
+    FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->last_assemble_s = 1e-3 * ms;
+    return FEMSHELL_OK;
+}
+
+// femshell_set_mesh and femshell_set_sections forget the densities (the mass matrix in HBM goes with their entry of the table)
+void forget_density(femshell_ctx *c)
+{
+    c->have_density = false;
+    c->rho = 0.0;
+    c->sec_rho.clear();
+}
+
+// u_bar of the prescribed values and the Dirichlet set in force (femshell_set_prescribed): the entries at fixed dofs, zero
+// elsewhere, on the host and in HBM.  Single-rank contexts only: the owned rows are all rows.
+int resolve_prescribed(femshell_ctx *c)
+{
+    if (c->ubar_valid) return FEMSHELL_OK;
+    const Plan &p = c->plan;
+    c->ubar_host.assign((size_t)p.n_nodes * 6, 0.0);
+    bool nonzero = false;
+    for (int32_t a = 0; a < p.n_nodes; a++) {
+        const uint32_t fixed = c->dmask_global[(size_t)a];
+        for (int v = 0; v < 6 && fixed; v++)
+            if ((fixed >> v) & 1u) {
+                const double val = c->prescribed_global[6ull * (size_t)a + v];
+                c->ubar_host[6ull * (size_t)a + v] = val;
+                nonzero = nonzero || val != 0.0;
+            }
+    }
+    FS_HIP(c->ubar.alloc((size_t)p.n_local_nodes() * 6));
+    FS_HIP(c->ubar.zero(c->stream));
+    FS_HIP(hipMemcpyAsync(c->ubar.p, c->ubar_host.data(), (size_t)p.n_own * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    FS_HIP(hipStreamSynchronize(c->stream));
+    c->ubar_nonzero = nonzero;
+    c->ubar_valid = true;
+    return FEMSHELL_OK;
+}
+
+static int do_rhs(femshell_ctx *c)
+{
+    if (c->have_prescribed) {
+        // F = mask(loads - K_unc u_bar): one launch of the matrix-free product with the unconstrained element matrices, the
+        // masked combine in its epilogue.  (No fixed dof carries a non-zero value: the masked copy below, as without the call.)
+        const int rc = resolve_prescribed(c);
+        if (rc) return rc;
+        if (c->ubar_nonzero) {
+            launch_element_product(c->dm, c->mc, c->sections_or_null(), c->ubar.p, nullptr, c->loads.p, c->F.p, true, c->stream);
+            FS_HIP(hipGetLastError());
+            c->rhs_valid = true;
+            return FEMSHELL_OK;
+        }
+    }
+    launch_rhs(c->dm, c->loads.p, c->F.p, c->stream);
+    FS_HIP(hipGetLastError());
+    c->rhs_valid = true;
+    return FEMSHELL_OK;
+}
+
+int do_assemble(femshell_ctx *c, bool wait)
+{
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: no mesh set");
+    TraceRange trace("femshell_assemble");
+    CommWatch watch(c->cfg.rank, c->comm.active() ? c->cfg.world_size : 1, "femshell_assemble (agreement of the ranks on the outcome)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    if (c->assembly_pending && wait) { // (async after async: one status word collects both)
+        rc = finish_pending_assembly(c);
+        if (rc) return rc;
+    }
+    // (the event pair costs the synchronous call its two records: without it assemble_seconds is the host's clock around launch
+    //  and synchronisation; an enqueued assembly always carries the pair -- nobody else could time it)
+    // (MEASURED, round 6, profiles/r06_sync_step_ab_raw.txt: neither the status word in mapped host memory, nor dropping the event
+    //  pair, nor polling a word that a one-lane kernel writes behind the assembly instead of synchronising the stream, nor polled
+    //  completion signals move the 40-50 us a synchronous step costs beyond its kernel: it is launch latency on an idle queue)
+    const bool events = c->asm_events || !wait;
+    const auto t_host = std::chrono::steady_clock::now();
+    if (events) FS_HIP(hipEventRecord(c->ev0, c->stream));
+    c->dm.rhs_loads = c->loads.p;
+    c->dm.rhs_F = c->F.p;
+    if (!launch_assemble(c->dm, c->mc, c->stream, c->sections_or_null())) // K and F (k_rhs alone serves changes of the loads)
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: the context's sections have no table in HBM");
+    // (dynamics is active: the matrix in HBM is K_eff = K + shift M, also when K is built again -- FEMSHELL_REASSEMBLE_EACH_SOLVE)
+    if (c->dyn.active) launch_mass_shift(c->dm, c->mass.p, c->dyn.k.shift, c->stream);
+    if (events) FS_HIP(hipEventRecord(c->ev1, c->stream));
+    FS_HIP(hipGetLastError());
+    if (c->have_prescribed) { // (the assembly kernel wrote the masked loads: F of the prescribed values behind it)
+        rc = do_rhs(c);
+        if (rc) return rc;
+    }
+    if (wait) {
+        rc = check_and_agree(c, "femshell_assemble");
+        if (rc) return rc;
+        if (events) {
+            float ms = 0.f;
+            FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+            c->last_assemble_s = 1e-3 * ms;
+        } else {
+            c->last_assemble_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_host).count();
+        }
+    } else {
+        c->assembly_pending = true; // (a failed element leaves its mark in the status word until someone looks)
+    }
+    invalidate(c, Change::assembled); // block-Jacobi and the multigrid hierarchy belong to the previous K
+    c->matrix_valid = true;
+    c->rhs_valid = true;
+    return FEMSHELL_OK;
+}
+
+// femshell_time_kernel launched the assembly kernel itself, between its event pair: the call ends in the transition of
+// do_assemble.  While dynamics is active the shift is added once, so that HBM holds K_eff as the next step expects.  F is what it
+// was (the kernel rewrites the masked loads) unless prescribed values are in force, which that overwrites.
+int timed_assembly_done(femshell_ctx *c)
+{
+    if (c->dyn.active) {
+        launch_mass_shift(c->dm, c->mass.p, c->dyn.k.shift, c->stream);
+        FS_HIP(hipGetLastError());
+    }
+    const int rc = check_status(c, "femshell_time_kernel");
+    if (rc) return rc;
+    invalidate(c, Change::assembled);
+    c->matrix_valid = true;
+    if (c->have_prescribed) c->rhs_valid = false;
+    return FEMSHELL_OK;
+}
+
+static int do_jacobi(femshell_ctx *c)
+{
+    TraceRange trace("femshell block-Jacobi setup");
+    FS_HIP(hipEventRecord(c->ev0, c->stream));
+    launch_block_jacobi(c->dm, c->stream);
+    FS_HIP(hipEventRecord(c->ev1, c->stream));
+    FS_HIP(hipGetLastError());
+    int rc = check_and_agree(c, "block-Jacobi setup");
+    if (rc) return rc;
+    float ms = 0.f;
+    FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    c->last_setup_s = 1e-3 * ms;
+    c->jacobi_valid = true;
+    return FEMSHELL_OK;
+}
+
+// the diagonal of the lumped mass matrix of the owned rows in HBM (c->mass), computed where it is not there yet
+static int ensure_mass(femshell_ctx *c)
+{
+    if (c->mass_valid) return FEMSHELL_OK;
+    const Plan &p = c->plan;
+    hipStream_t st = c->stream;
+    FS_HIP(c->mass.alloc((size_t)p.n_pad * 6));
+    const double2 *sec = nullptr;
+    if (c->have_sections) {
+        std::vector<double2> table((size_t)c->n_sections);
+        for (int32_t s = 0; s < c->n_sections; s++) {
+            const double rho = c->sec_rho.empty() ? c->rho : c->sec_rho[(size_t)s], t = c->sec_thickness[(size_t)s];
+            table[(size_t)s] = make_double2(rho * t, rho * t * t * t / 12.0);
+        }
+        FS_HIP(c->sec_mass.upload(table, st));
+        FS_HIP(hipStreamSynchronize(st)); // the host table goes out of scope
+        sec = c->sec_mass.p;
+    }
+    const double t = c->cfg.thickness;
+    launch_lumped_mass(c->dm, make_double2(c->rho * t, c->rho * t * t * t / 12.0), sec, c->ds.slice_elem_section, c->mass.p, st);
+    FS_HIP(hipGetLastError());
+    c->mass_valid = true;
+    return FEMSHELL_OK;
+}
+
+// The multigrid hierarchy of the K in HBM, built where there is none (first solve, K changed, the all-FP64 rebuild): on one rank,
+// or row-partitioned and collective when the context has a communicator.  *pc_setup_s += its seconds.
+static int ensure_amg_hierarchy(femshell_ctx *c, double *pc_setup_s)
+{
+    if (c->amg && c->amg->valid) return FEMSHELL_OK;
+    int rc = FEMSHELL_OK;
+    if (c->comm.active()) {
+        const double t0 = wall_s();
+        // row-partitioned hierarchy (amg_dist.cpp); a failure only one rank sees must reach the others
+        rc = agree_status(c, amg_setup_dist(c), "multigrid setup", true);
+        if (rc) {
+            c->amg.reset();
+            return rc;
+        }
+        *pc_setup_s += wall_s() - t0;
+    } else {
+        rc = amg_setup(c);
+        if (rc) {
+            c->amg.reset();
+            return rc;
+        }
+        *pc_setup_s += c->amg->setup_seconds;
+    }
+    return rc;
+}
+
+int ensure(femshell_ctx *c, uint32_t need, Timings *t, bool solving)
+{
+    Timings unused;
+    if (!t) t = &unused;
+    int rc = FEMSHELL_OK;
+    // (the mass first: it depends on nothing here, and K_eff of an active dynamics is built with it)
+    if ((need & kMass) && (rc = ensure_mass(c))) return rc;
+    if ((need & kK) && (!c->matrix_valid || (solving && (c->cfg.flags & FEMSHELL_REASSEMBLE_EACH_SOLVE)))) {
+        if ((rc = do_assemble(c))) return rc; // (F with it)
+        t->assemble_s += c->last_assemble_s;
+    }
+    if ((need & kF) && !c->rhs_valid && (rc = do_rhs(c))) return rc;
+    if ((need & kJacobi) && !c->jacobi_valid) {
+        if ((rc = do_jacobi(c))) return rc;
+        t->setup_s += c->last_setup_s;
+    }
+    if (need & kHierarchy) rc = ensure_amg_hierarchy(c, &t->pc_setup_s);
+    return rc;
+}
+
+} // namespace femshell

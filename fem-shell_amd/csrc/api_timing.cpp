@@ -49,7 +49,7 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         // k_mass_shift run once per mesh and per dt)
         if (!c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no density set");
         if (which != FEMSHELL_KERNEL_LUMPED_MASS && !c->dyn.active) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: dynamics is not active");
-        rc = ensure_mass(c);
+        rc = ensure(c, kMass);
         if (rc) return rc;
         hipStream_t st = c->stream;
         femshell_ctx::Dynamics &d = c->dyn;
@@ -71,10 +71,7 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         float ms = 0.f;
         FS_HIP(hipEventElapsedTime(&ms, c->ev0, c->ev1));
         *mean_ms_out = (double)ms / reps;
-        if (which == FEMSHELL_KERNEL_MASS_SHIFT) {
-            c->matrix_valid = c->jacobi_valid = false; // (the shift was added `reps` times)
-            c->amg.reset();
-        }
+        if (which == FEMSHELL_KERNEL_MASS_SHIFT) invalidate(c, Change::matrix_spoiled); // (the shift was added `reps` times)
         if (which == FEMSHELL_KERNEL_NEWMARK_UPDATE) d.have_candidate = false;
         if (bytes_out) {
             const double n = p.n_own, ne = p.n_ltri() + p.n_lquad();
@@ -94,8 +91,8 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         if (which == FEMSHELL_KERNEL_GRAM && !c->have_density) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: no density set");
         const int nc = (int)knob_long("FEMSHELL_TIME_KERNEL_COLS", 4);
         if (nc < 1 || nc > kModalMaxBlock) return set_err(FEMSHELL_ERR_INVALID, "femshell_time_kernel: FEMSHELL_TIME_KERNEL_COLS must be in 1 .. 32");
-        if (which == FEMSHELL_KERNEL_GRAM && (rc = ensure_mass(c))) return rc;
-        if (which == FEMSHELL_KERNEL_SPMM && !c->matrix_valid && (rc = do_assemble(c))) return rc;
+        if (which == FEMSHELL_KERNEL_GRAM && (rc = ensure(c, kMass))) return rc;
+        if (which == FEMSHELL_KERNEL_SPMM && (rc = ensure(c, kK))) return rc;
         hipStream_t st = c->stream;
         const Plan &p = c->plan;
         const int64_t ld = (int64_t)p.n_local_nodes() * 6;
@@ -202,18 +199,7 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         if (bytes_out) *bytes_out = bytes_element_resultants(c);
         return FEMSHELL_OK;
     }
-    if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->matrix_valid) {
-        rc = do_assemble(c);
-        if (rc) return rc;
-    }
-    if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->rhs_valid) {
-        rc = do_rhs(c);
-        if (rc) return rc;
-    }
-    if (which != FEMSHELL_KERNEL_ASSEMBLE && !c->jacobi_valid) {
-        rc = do_jacobi(c);
-        if (rc) return rc;
-    }
+    if (which != FEMSHELL_KERNEL_ASSEMBLE && (rc = ensure(c, kK | kF | kJacobi))) return rc;
     hipStream_t st = c->stream;
     const Plan &p = c->plan;
     const size_t nrow = (size_t)p.n_pad * 6, nrow_ext = (size_t)p.n_local_nodes() * 6;
@@ -281,14 +267,7 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         bytes = which == FEMSHELL_KERNEL_SPMV ? bytes_spmv(c) : which == FEMSHELL_KERNEL_CG_UPDATE ? bytes_update(c) : bytes_direction(c);
     }
     if (bytes_out) *bytes_out = bytes;
-    if (which == FEMSHELL_KERNEL_ASSEMBLE) {
-        rc = check_status(c, "femshell_time_kernel");
-        if (rc) return rc;
-        c->matrix_valid = true;
-        c->jacobi_valid = false;
-        if (c->have_prescribed) c->rhs_valid = false; // (the assembly kernel wrote the masked loads over F)
-    }
-    return FEMSHELL_OK;
+    return which == FEMSHELL_KERNEL_ASSEMBLE ? timed_assembly_done(c) : FEMSHELL_OK;
 }
 
 } // extern "C"

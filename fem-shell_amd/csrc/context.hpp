@@ -485,6 +485,7 @@ struct femshell_ctx {
     bool halo_overlap = false;
     femshell::MatConst mc{};
     femshell::Plan plan;
+    // (what is valid -- these, mass_valid, ubar_valid, amg, amg_fp64_only below -- is written by api_state.cpp only: derived.hpp)
     bool have_mesh = false, matrix_valid = false, rhs_valid = false, jacobi_valid = false, have_solution = false;
 
     // optional renumbering (reorder.cpp): internal node i is the caller's node perm[i]; iperm is the inverse; both empty
@@ -543,7 +544,7 @@ struct femshell_ctx {
     } dyn;
     // prescribed displacements (femshell_set_prescribed): the values as the caller gave them (n_nodes x 6, internal numbering; which
     // of them count is decided by the Dirichlet set when the right-hand side is built) and u_bar in HBM -- the entries at fixed dofs,
-    // zero elsewhere -- resolved by resolve_prescribed (api.cpp) after every change of either.  The solution vector in HBM stays the
+    // zero elsewhere -- resolved by resolve_prescribed (api_state.cpp) after every change of either.  The solution vector in HBM stays the
     // homogeneous part; u_bar is added where a solution leaves the library.
     bool have_prescribed = false, ubar_valid = false, ubar_nonzero = false;
     std::vector<double> prescribed_global, ubar_host;

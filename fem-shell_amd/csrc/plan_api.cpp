@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "amg.hpp"
+#include "derived.hpp"
 #include "errors.hpp"
 #include "knobs.hpp"
 #include "plan.hpp"
@@ -42,6 +43,12 @@ int32_t femshell_grid_cap(const char *text, int32_t fallback) { return grid_cap(
 
 long femshell_knob_long(const char *name, long dflt) { return knob_long(name, dflt); }
 int femshell_knob_flag(const char *name, int dflt) { return knob_flag(name, dflt != 0) ? 1 : 0; }
+
+int32_t femshell_stale_after(int32_t change)
+{
+    if (change < 0 || change >= (int32_t)Change::count) return -1;
+    return (int32_t)stale_after(static_cast<Change>(change));
+}
 
 int femshell_plan_info(const femshell_plan *plan, int64_t *info)
 {

@@ -83,7 +83,8 @@ const char *femshell_last_error(void);
  * repeated node, unattached node).  FEMSHELL_ERR_UNSUPPORTED: a valid mesh beyond a limit of
  * the layout (more than 765 elements at a node, more than 4095 elements or too many for the
  * assembly kernel's LDS on one 32-node slice, more than 63 neighbours of a node in full
- * storage); the context stays usable. */
+ * storage); the context stays usable, but has no mesh until one is accepted: nothing of the
+ * previous mesh (K, the solution, the multigrid hierarchy) is valid any more. */
 int femshell_set_mesh(femshell_ctx *ctx, int32_t n_nodes, const double *xyz, int32_t n_tri,
                       const int32_t *tri, int32_t n_quad, const int32_t *quad);
 
@@ -234,7 +235,9 @@ int femshell_pc_defaults(int32_t type, femshell_pc_options *out);
 int femshell_set_preconditioner(femshell_ctx *ctx, const femshell_pc_options *opt);
 
 /* inspection of the multigrid hierarchy of the last solve (tests; host copies are kept for
- * matrices of up to 2M blocks): level 0 is K itself */
+ * matrices of up to 2M blocks): level 0 is K itself.  There is none from the moment K is stale
+ * (a new mesh, Dirichlet set or sections, an assembly, the start or end of dynamics) until the
+ * next solve builds one. */
 typedef struct femshell_amg_level_info {
     int32_t n_nodes;        /* block rows of the level */
     int32_t n_coarse;       /* aggregates = block rows of the next level (0 on the coarsest) */

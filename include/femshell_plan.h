@@ -139,6 +139,11 @@ int32_t femshell_grid_cap(const char *text, int32_t fallback);
 long femshell_knob_long(const char *name, long dflt);
 int femshell_knob_flag(const char *name, int dflt);
 
+/* which derived products of a context a change makes stale (csrc/derived.hpp): `change` is a number of
+ * femshell::Change; the result has a bit per product -- 1 K, 2 F, 4 block-Jacobi, 8 multigrid hierarchy, 16 lumped mass,
+ * 32 u_bar, 64 last solution, 128 warm start, 256 the all-FP64 choice -- or is -1 where there is no such change */
+int32_t femshell_stale_after(int32_t change);
+
 /* symmetric storage of a square operator (coarse multigrid levels): diagonal + upper blocks in the sliced ELL arrays and
  * the in-lists of the transposed products; returns the total slots, *in_total receives the in-list entries; arrays may
  * be NULL for a sizing call */
