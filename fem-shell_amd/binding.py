@@ -20,6 +20,7 @@ KERNEL_LUMPED_MASS, KERNEL_MASS_SHIFT, KERNEL_NEWMARK_RHS, KERNEL_NEWMARK_UPDATE
 KERNEL_SPMM, KERNEL_GRAM, KERNEL_BLOCK_COMBINE = 8, 9, 10
 KERNEL_ELEMENT_PRODUCT = 11
 KERNEL_ELEMENT_RESULTANTS = 12
+KERNEL_ELEMENT_LOADS = 13
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -35,6 +36,7 @@ SYMBOLS = [
     "femshell_dynamics_accept", "femshell_dynamics_state", "femshell_dynamics_energy", "femshell_dynamics_end",
     "femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram",
     "femshell_set_prescribed", "femshell_reactions", "femshell_element_product", "femshell_element_resultants",
+    "femshell_set_element_loads", "femshell_element_load_vector",
 ]
 
 
@@ -192,6 +194,8 @@ def load_library():
     L.femshell_reactions.argtypes = [vp, dp, dp]
     L.femshell_element_product.argtypes = [vp, dp, dp]
     L.femshell_element_resultants.argtypes = [vp, dp, dp]
+    L.femshell_set_element_loads.argtypes = [vp, dp, dp]
+    L.femshell_element_load_vector.argtypes = [vp, dp]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -306,6 +310,26 @@ class FemShell:
         out = np.zeros((self.n_tri + self.n_quad, 14))
         _check(self._L.femshell_element_resultants(self._h, _d(self._node_vector(u, "u")), _d(out)))
         return out
+
+    def set_element_loads(self, tri_load=None, quad_load=None):
+        """Pressure and traction per element (femshell_set_element_loads): tri_load is (n_tri, 4), quad_load (n_quad, 4), rows
+        (p, qx, qy, qz) in the element order of set_mesh -- p along the element's own normal, q per area in global axes.  None for
+        one kind leaves it unloaded, both None clears.  The loads in force are the nodal loads of set_loads plus the lumped nodal
+        equivalents; only the right-hand side is rebuilt."""
+        tl = None if tri_load is None else np.ascontiguousarray(tri_load, dtype=np.float64).reshape(-1, 4)
+        ql = None if quad_load is None else np.ascontiguousarray(quad_load, dtype=np.float64).reshape(-1, 4)
+        if tl is not None and len(tl) != self.n_tri:
+            raise ValueError("tri_load needs one row per triangle (%d), got %d" % (self.n_tri, len(tl)))
+        if ql is not None and len(ql) != self.n_quad:
+            raise ValueError("quad_load needs one row per quadrilateral (%d), got %d" % (self.n_quad, len(ql)))
+        _check(self._L.femshell_set_element_loads(self._h, _d(tl), _d(ql)))
+
+    def element_load_vector(self):
+        """S, (n_nodes, 6): the nodal equivalents of the element loads in force alone, in the caller's numbering, not masked;
+        zeros when none are set (femshell_element_load_vector)."""
+        f = np.zeros((self.n_nodes, 6))
+        _check(self._L.femshell_element_load_vector(self._h, _d(f)))
+        return f
 
     def set_sections(self, sections, tri_section=None, quad_section=None):
         """Shell sections: `sections` is an (n, 3) array-like of (nu, E, thickness), tri_section / quad_section give every

@@ -173,12 +173,15 @@ static int upload_node_data(femshell_ctx *c, int what)
         }
         if (what & kNodeLoads) {
             // the owned rows are one contiguous piece of the global array: no staging copy (96 MB at 4M triangles)
-            FS_HIP(c->loads.alloc((size_t)p.n_pad * 6));
+            // (element loads in force: the nodal part has a buffer of its own, and c->loads = nodal + S is formed behind the copy)
+            double *nodal = nullptr;
+            if (const int rc = nodal_loads_buffer(c, &nodal)) return rc;
             if (p.n_own > 0)
-                FS_HIP(hipMemcpyAsync(c->loads.p, c->loads_global.data() + 6ull * (size_t)p.row_begin, (size_t)p.n_own * 6 * sizeof(double),
+                FS_HIP(hipMemcpyAsync(nodal, c->loads_global.data() + 6ull * (size_t)p.row_begin, (size_t)p.n_own * 6 * sizeof(double),
                                       hipMemcpyHostToDevice, st));
             if (p.n_pad > p.n_own)
-                FS_HIP(hipMemsetAsync(c->loads.p + 6ull * (size_t)p.n_own, 0, (size_t)(p.n_pad - p.n_own) * 6 * sizeof(double), st));
+                FS_HIP(hipMemsetAsync(nodal + 6ull * (size_t)p.n_own, 0, (size_t)(p.n_pad - p.n_own) * 6 * sizeof(double), st));
+            if (const int rc = combine_loads(c)) return rc;
             FS_HIP(hipStreamSynchronize(st)); // (loads_global may be replaced by the next femshell_set_loads)
         }
     }
@@ -696,6 +699,7 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     c->n_sections = 0;
     c->sec_thickness.clear();
     forget_density(c);
+    forget_element_loads(c); // (per element of the previous mesh; kNodeCleared below zeroes the loads)
     c->dyn.reset(); // (a new mesh ends dynamics)
     c->have_prescribed = c->ubar_nonzero = false; // (... and forgets the prescribed displacements)
     c->prescribed_global.clear();

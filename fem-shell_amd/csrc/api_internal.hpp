@@ -37,6 +37,13 @@ int do_assemble(femshell_ctx *c, bool wait = true);
 int resolve_prescribed(femshell_ctx *c);
 void forget_density(femshell_ctx *c);
 int timed_assembly_done(femshell_ctx *c);
+// element loads (api_state.cpp): c->loads holds nodal + S; uploads of the nodal part go to nodal_loads_buffer and end in combine_loads
+void forget_element_loads(femshell_ctx *c);
+int nodal_loads_buffer(femshell_ctx *c, double **buf);
+int ensure_slice_elem_local(femshell_ctx *c);
+int combine_loads(femshell_ctx *c);
+int element_loads_apply(femshell_ctx *c, const RawVec<double> &rows);
+int element_loads_clear(femshell_ctx *c);
 
 double bytes_assemble(const femshell_ctx *c);
 double bytes_spmv(const femshell_ctx *c);
@@ -44,6 +51,8 @@ double bytes_update(const femshell_ctx *c);
 double bytes_direction(const femshell_ctx *c);
 double bytes_update_single_reduction(const femshell_ctx *c);
 double bytes_element_resultants(const femshell_ctx *c);
+double bytes_element_loads(const femshell_ctx *c);
+int time_element_loads(femshell_ctx *c, int32_t reps, double *mean_ms_out);
 int upload_section_thickness(femshell_ctx *c, DevBuf<double> *buf, const double **sec_t);
 
 } // namespace femshell

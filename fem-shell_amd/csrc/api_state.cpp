@@ -1,7 +1,7 @@
 // api_state.cpp -- the derived state of a context (derived.hpp): the one place that says what is valid.
 // invalidate() applies the table of derived.hpp after a change, the functions below it make a product valid, ensure() brings
 // what an entry point needs up to date, have() answers for the entry points that refuse instead.  No other file assigns to
-// matrix_valid, rhs_valid, jacobi_valid, mass_valid, ubar_valid or amg_fp64_only or drops the hierarchy; have_solution and
+// matrix_valid, rhs_valid, jacobi_valid, mass_valid, ubar_valid, have_element_loads or amg_fp64_only or drops the hierarchy; have_solution and
 // warm_next are set where a solve and a hand-over produce them (api.cpp, api_dynamics.cpp) and cleared here only.
 #include "api_internal.hpp"
 
@@ -61,6 +61,82 @@ void forget_density(femshell_ctx *c)
     c->have_density = false;
     c->rho = 0.0;
     c->sec_rho.clear();
+}
+
+// ---- element loads (femshell_set_element_loads, api_element_loads.cpp).  The invariant every consumer of the loads stands on:
+// c->loads in HBM holds nodal + S, S the nodal equivalents of the element loads in force (zero without), so do_rhs, the assembly's
+// rhs_loads, femshell_reactions and the Newmark right-hand side read one buffer as before.  While element loads are in force
+// the nodal part lies beside it in c->loads_nodal, and whoever rewrites the nodal loads writes there (nodal_loads_buffer) and
+// calls combine_loads.
+
+// femshell_set_mesh forgets the element loads: the flag, their buffers and the map of the previous mesh's lists
+void forget_element_loads(femshell_ctx *c)
+{
+    c->have_element_loads = false;
+    c->loads_nodal.release();
+    c->elem_load.release();
+    c->slice_elem_local.release();
+}
+
+// where an upload of the nodal loads goes (n_pad x 6, allocated here)
+int nodal_loads_buffer(femshell_ctx *c, double **buf)
+{
+    DevBuf<double> &b = c->have_element_loads ? c->loads_nodal : c->loads;
+    FS_HIP(b.alloc((size_t)c->plan.n_pad * 6));
+    *buf = b.p;
+    return FEMSHELL_OK;
+}
+
+// the slices' element lists as local element indices in HBM (Plan::slice_elems): once per mesh, at the first use
+int ensure_slice_elem_local(femshell_ctx *c)
+{
+    if (c->slice_elem_local.p) return FEMSHELL_OK;
+    FS_HIP(c->slice_elem_local.upload(c->plan.slice_elems, c->stream)); // (the plan outlives the stream's work)
+    return FEMSHELL_OK;
+}
+
+// c->loads = nodal + S, one launch; nothing without element loads (c->loads is the nodal part itself then)
+int combine_loads(femshell_ctx *c)
+{
+    if (!c->have_element_loads) return FEMSHELL_OK;
+    launch_element_loads(c->dm, c->slice_elem_local.p, c->elem_load.p, c->loads_nodal.p, c->loads.p, c->stream);
+    FS_HIP(hipGetLastError());
+    return FEMSHELL_OK;
+}
+
+// rows: four doubles per local element, which take force in place of the previous set.  The first set moves the nodal part
+// aside inside HBM; no set uploads it again.  Returns after the upload of `rows` has completed.
+int element_loads_apply(femshell_ctx *c, const RawVec<double> &rows)
+{
+    const size_t n6 = (size_t)c->plan.n_pad * 6;
+    hipStream_t st = c->stream;
+    int rc = ensure_slice_elem_local(c);
+    if (rc) return rc;
+    if (!c->have_element_loads) {
+        FS_HIP(c->loads_nodal.alloc(n6));
+        if (n6) FS_HIP(hipMemcpyAsync(c->loads_nodal.p, c->loads.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    }
+    FS_HIP(c->elem_load.upload(rows, st));
+    c->have_element_loads = true;
+    rc = combine_loads(c);
+    if (rc) return rc;
+    FS_HIP(hipStreamSynchronize(st));
+    invalidate(c, Change::loads);
+    return FEMSHELL_OK;
+}
+
+// no element loads any more: the nodal part goes back into c->loads
+int element_loads_clear(femshell_ctx *c)
+{
+    if (!c->have_element_loads) return FEMSHELL_OK;
+    const size_t n6 = (size_t)c->plan.n_pad * 6;
+    if (n6) FS_HIP(hipMemcpyAsync(c->loads.p, c->loads_nodal.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    FS_HIP(hipStreamSynchronize(c->stream));
+    c->have_element_loads = false;
+    c->loads_nodal.release();
+    c->elem_load.release();
+    invalidate(c, Change::loads);
+    return FEMSHELL_OK;
 }
 
 // u_bar of the prescribed values and the Dirichlet set in force (femshell_set_prescribed): the entries at fixed dofs, zero

@@ -199,6 +199,13 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         if (bytes_out) *bytes_out = bytes_element_resultants(c);
         return FEMSHELL_OK;
     }
+    if (which == FEMSHELL_KERNEL_ELEMENT_LOADS) {
+        // hashed element values from the loads in force into a scratch vector (api_element_loads.cpp): every rank times its own rows
+        rc = time_element_loads(c, reps, mean_ms_out);
+        if (rc) return rc;
+        if (bytes_out) *bytes_out = bytes_element_loads(c);
+        return FEMSHELL_OK;
+    }
     if (which != FEMSHELL_KERNEL_ASSEMBLE && (rc = ensure(c, kK | kF | kJacobi))) return rc;
     hipStream_t st = c->stream;
     const Plan &p = c->plan;

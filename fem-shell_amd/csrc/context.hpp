@@ -549,6 +549,13 @@ struct femshell_ctx {
     bool have_prescribed = false, ubar_valid = false, ubar_nonzero = false;
     std::vector<double> prescribed_global, ubar_host;
     femshell::DevBuf<double> ubar;
+    // element loads (femshell_set_element_loads): while they are in force `loads` holds nodal + S -- what every consumer of the
+    // loads reads --, loads_nodal the nodal part alone (HBM, allocated only then) and elem_load the caller's rows in the local
+    // element order.  slice_elem_local: Plan::slice_elems in HBM, uploaded at the first use per mesh.  (have_element_loads is
+    // written by api_state.cpp only.)
+    bool have_element_loads = false;
+    femshell::DevBuf<double> loads_nodal, elem_load;
+    femshell::DevBuf<int32_t> slice_elem_local;
     // CG state
     femshell::DevBuf<double> x, r, z, p, q, sv, partials, hist, sendbuf, ufull;
     femshell::DevBuf<double> xacc, rres; // iterative refinement of the multigrid-preconditioned solve: accumulated solution, residual

@@ -198,6 +198,14 @@ void launch_element_product(const DeviceMatrix &m, const MatConst &mc, const Dev
 void launch_element_resultants(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const double *sec_t, const double *u,
                                const double *up, double *out, hipStream_t st);
 
+// Nodal equivalents of per-element pressure and traction (element_loads.hip): out[n_pad][6] = base + S on the
+// translations of the owned rows, base on their rotations, zero on padding rows; base == nullptr: zero.  elem_load: four doubles
+// (p, qx, qy, qz) per LOCAL element (triangles, then quadrilaterals), 16-byte aligned; slice_elem_local: the local element of
+// every entry of the slices' element lists (Plan::slice_elems).  S_a: the shares of the elements that contain row a, added in
+// the order of the slice's list from zero, no atomics: two launches give the same bits at every grid size.  base may not be out.
+void launch_element_loads(const DeviceMatrix &m, const int32_t *slice_elem_local, const double *elem_load, const double *base, double *out,
+                          hipStream_t st);
+
 // ---- sparse products (spmv_kernels.hip) ----
 // What a product does with its result besides storing it: what the callers fill and what k_spmv receives.
 struct SpmvEpilogue {

@@ -88,6 +88,67 @@ static void check_prescribed_nodes(const Parameters &p, int32_t n_nodes)
                                      std::to_string(p.prescribed_nodes[i]) + " is out of range (the mesh has " + std::to_string(n_nodes) + " nodes)");
 }
 
+// -element_loads FILE into p.element_load_*: the conventions of the -prescribed reader
+static void read_element_loads(Parameters &p)
+{
+    std::ifstream in(p.element_loads_file);
+    if (!in) throw std::runtime_error("cannot open " + p.element_loads_file);
+    p.element_load_elems.clear();
+    p.element_load_lines.clear();
+    p.element_load_values.clear();
+    std::string line;
+    for (int no = 1; std::getline(in, line); no++) {
+        const size_t h = line.find('#');
+        if (h != std::string::npos) line.erase(h);
+        std::istringstream is(line);
+        std::string first;
+        if (!(is >> first)) continue; // blank or comment
+        const std::string where = p.element_loads_file + ": line " + std::to_string(no) + ": ";
+        char *end = nullptr;
+        const long elem = std::strtol(first.c_str(), &end, 10);
+        double v[4];
+        std::string rest;
+        if (*end != '\0' || !(is >> v[0] >> v[1] >> v[2] >> v[3]) || (is >> rest)) throw std::runtime_error(where + "expected 'elem p qx qy qz'");
+        for (double x : v)
+            if (!std::isfinite(x)) throw std::runtime_error(where + "a value is not finite");
+        if (elem < 0 || elem > 2147483647L) throw std::runtime_error(where + "element index " + first + " is out of range");
+        p.element_load_elems.push_back((int32_t)elem);
+        p.element_load_lines.push_back(no);
+        p.element_load_values.insert(p.element_load_values.end(), v, v + 4);
+    }
+}
+
+ElementLoads build_element_loads(const Parameters &p, const ShellMesh &mesh, const SectionTable *sections)
+{
+    const size_t ne = mesh.order.size();
+    std::vector<double> rows(4 * ne, 0.0); // mesh-file order
+    std::vector<uint8_t> listed(ne, 0);
+    for (size_t i = 0; i < p.element_load_elems.size(); i++) {
+        const std::string where = p.element_loads_file + ": line " + std::to_string(p.element_load_lines[i]) + ": ";
+        const size_t e = (size_t)p.element_load_elems[i];
+        if (e >= ne)
+            throw std::runtime_error(where + "element index " + std::to_string(e) + " is out of range (the mesh has " + std::to_string(ne) + " elements)");
+        if (listed[e]) throw std::runtime_error(where + "element " + std::to_string(e) + " is listed twice");
+        listed[e] = 1;
+        for (int v = 0; v < 4; v++) rows[4 * e + v] = p.element_load_values[4 * i + v];
+    }
+    ElementLoads l;
+    l.tri_load.assign(4 * (size_t)mesh.n_tri(), 0.0);
+    l.quad_load.assign(4 * (size_t)mesh.n_quad(), 0.0);
+    for (size_t e = 0; e < ne; e++) {
+        const bool tri = mesh.order[e].first == 't';
+        const size_t k = (size_t)mesh.order[e].second;
+        double *dst = tri ? &l.tri_load[4 * k] : &l.quad_load[4 * k];
+        for (int v = 0; v < 4; v++) dst[v] = rows[4 * e + v];
+        if (p.pressure_set) dst[0] += p.pressure;
+        if (p.gravity_set) {
+            const double t = sections ? sections->sections[(size_t)(tri ? sections->tri_section : sections->quad_section)[k]].thickness : p.thickness;
+            for (int d = 0; d < 3; d++) dst[1 + d] += p.rho * t * p.gravity[d];
+        }
+    }
+    return l;
+}
+
 bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, std::ostream &err)
 {
     if (argc < 5) {
@@ -120,7 +181,13 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "\t and the point arrays reaction_f / reaction_m of <out>.vtk (optional)\n"
             << "-stress:\t writes <out>_stress.txt, a line per element with the membrane force tensor N, the moment tensor M (global axes,\n"
             << "\t xx yy zz xy yz zx) and the von Mises stress at the top and the bottom surface (element means), and the cell arrays\n"
-            << "\t membrane_force, moment, von_mises_top, von_mises_bottom of <out>.vtk (optional)\n";
+            << "\t membrane_force, moment, von_mises_top, von_mises_bottom of <out>.vtk (optional)\n"
+            << "-pressure:\t uniform pressure P on every element, along the element's own normal (optional; dead load, lumped to the nodes)\n"
+            << "-element_loads:\t file of lines 'elem p qx qy qz': pressure and traction per area (global axes) of the element with that index\n"
+            << "\t in mesh-file order, the index of <out>_stress.txt; elements not listed get zero (optional)\n"
+            << "-gravity:\t gx gy gz: self-weight rho t g per area of every element, t the element's own under -sections (needs -rho; without\n"
+            << "\t -dt / -steps the solve stays static)\n"
+            << "\t -pressure, -element_loads and -gravity add up and come on top of the force file's nodal loads; not with -modes\n";
         return false;
     }
     bool failed = false;
@@ -312,6 +379,54 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             failed = true;
         }
     }
+    // element loads: refused here like the options above (the element indices are held against the mesh as soon as it is read)
+    auto number = [](const char *text, double *value) {
+        if (!text) return false;
+        char *end = nullptr;
+        *value = std::strtod(text, &end);
+        return end != text && *end == '\0' && std::isfinite(*value);
+    };
+    if (has_flag(argc, argv, "-pressure")) {
+        p.pressure_set = true;
+        if (!number(arg_after(argc, argv, "-pressure"), &p.pressure)) {
+            err << "ERROR: -pressure needs a finite number!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-element_loads")) {
+        const char *v = arg_after(argc, argv, "-element_loads");
+        p.element_loads_file = v ? v : "";
+        if (!v) {
+            err << "ERROR: -element_loads needs a file!\n";
+            failed = true;
+        } else {
+            try {
+                read_element_loads(p);
+            } catch (const std::exception &e) {
+                err << "ERROR: " << e.what() << "\n";
+                failed = true;
+            }
+        }
+    }
+    if (has_flag(argc, argv, "-gravity")) {
+        p.gravity_set = true;
+        bool ok = false;
+        for (int i = 1; i + 3 < argc; i++)
+            if (std::strcmp(argv[i], "-gravity") == 0)
+                ok = number(argv[i + 1], &p.gravity[0]) && number(argv[i + 2], &p.gravity[1]) && number(argv[i + 3], &p.gravity[2]);
+        if (!ok) {
+            err << "ERROR: -gravity needs three finite numbers gx gy gz!\n";
+            failed = true;
+        }
+        if (!has_flag(argc, argv, "-rho")) {
+            err << "ERROR: -gravity needs a density, -rho!\n";
+            failed = true;
+        }
+    }
+    if (p.element_loads_requested() && has_flag(argc, argv, "-modes")) {
+        err << "ERROR: -pressure / -element_loads / -gravity do not go together with -modes (a modal analysis has no loads)!\n";
+        failed = true;
+    }
 
     out << "Run program with parameters:"
         << " debug messages = " << (p.debug ? "true" : "false") << ", nu = " << p.nu << ", E = " << p.em
@@ -468,6 +583,12 @@ void ShellSystem::set_prescribed(const Parameters &p)
     check_prescribed_nodes(p, n_nodes_);
     check(femshell_set_prescribed(ctx_, (int32_t)p.prescribed_nodes.size(), p.prescribed_nodes.data(), p.prescribed_values.data()),
           "femshell_set_prescribed");
+}
+
+void ShellSystem::set_element_loads(const ElementLoads &l)
+{
+    check(femshell_set_element_loads(ctx_, l.tri_load.empty() ? nullptr : l.tri_load.data(), l.quad_load.empty() ? nullptr : l.quad_load.data()),
+          "femshell_set_element_loads");
 }
 
 std::vector<double> ShellSystem::reactions()
@@ -689,6 +810,8 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         SectionTable section_table;
         if (p.sections_requested()) section_table = read_sections(p, mesh);
         if (p.prescribed_requested()) check_prescribed_nodes(p, mesh.n_nodes()); // (before any device is touched)
+        ElementLoads element_loads;
+        if (p.element_loads_requested()) element_loads = build_element_loads(p, mesh, p.sections_requested() ? &section_table : nullptr); // (likewise)
         clock.done("read mesh and loads");
         const Launch launch = Launch::from_environment();
         ShellSystem system(p, launch);
@@ -699,6 +822,7 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
             if (launch.world_size != 1) throw std::runtime_error("-prescribed runs on one rank");
             system.set_prescribed(p);
         }
+        if (p.element_loads_requested()) system.set_element_loads(element_loads); // (on top of the force file's nodal loads)
         if (p.reactions && launch.world_size != 1) throw std::runtime_error("-reactions runs on one rank");
         if (p.stress && launch.world_size != 1) throw std::runtime_error("-stress runs on one rank");
         clock.done("symbolic phase, boundary conditions, loads");

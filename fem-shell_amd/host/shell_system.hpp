@@ -61,7 +61,8 @@ struct Parameters {
     double dt = 0.0;
     int steps = 0, probe = -1;
     double newmark_beta = 0.25, newmark_gamma = 0.5, damping = 0.0;
-    bool dynamics_requested() const { return rho > 0.0 && modes == 0; }
+    // (-rho with -gravity and neither -dt nor -steps: the density of the self-weight of a static solve)
+    bool dynamics_requested() const { return rho > 0.0 && modes == 0 && !(gravity_set && dt <= 0.0 && steps <= 0); }
     // modal analysis (extension, stand-alone program only): -rho R -modes N [-modes_tol T] [-modes_shift S] computes the N lowest
     // pairs of K x = lambda M x (femshell_modes) instead of a static solve; writes <out>_modes.txt and the mode shapes as point
     // arrays of <out>.vtk.  N in 1 .. 28 (the library's block of N + 4 vectors holds at most 32).
@@ -86,7 +87,29 @@ struct Parameters {
     // (femshell_element_resultants).
     bool stress = false;
     bool prescribed_requested() const { return !prescribed_file.empty(); }
+    // element loads (extension, stand-alone program only; the reference's loads are the nodal forces of the `_f` file): pressure and
+    // traction per element (femshell_set_element_loads).  -pressure P: p = P on every element, along the element's own normal.
+    // -element_loads FILE: lines "elem p qx qy qz" ('#' starts a comment), elem the element's index in mesh-file order (the index of
+    // <out>_stress.txt); elements not listed get zero.  -gravity gx gy gz (needs -rho): q += rho t g, t the element's own thickness
+    // under -sections.  The three add up, and the nodal forces of the `_f` file come on top.  The file is read with the command
+    // line; the indices are held against the mesh before any device is touched.  Constant in time under -dt / -steps.
+    bool pressure_set = false, gravity_set = false;
+    double pressure = 0.0, gravity[3] = {0.0, 0.0, 0.0};
+    std::string element_loads_file;
+    std::vector<int32_t> element_load_elems; // element of every line of the file
+    std::vector<int> element_load_lines;     // ... and its line number
+    std::vector<double> element_load_values; // ... and its four values
+    bool element_loads_requested() const { return pressure_set || gravity_set || !element_loads_file.empty(); }
 };
+
+// what femshell_set_element_loads takes: rows (p, qx, qy, qz) of the triangles and of the quadrilaterals
+struct ElementLoads {
+    std::vector<double> tri_load, quad_load;
+};
+struct SectionTable;
+// -pressure, -element_loads and -gravity added up per element (sections: the table -gravity takes the thicknesses from, or nullptr);
+// throws std::runtime_error with file name and line number on an element the mesh does not have or one listed twice
+ElementLoads build_element_loads(const Parameters &p, const ShellMesh &mesh, const SectionTable *sections);
 
 // what femshell_set_sections takes, from the files above: section 0 is the command line's material, the listed ones follow
 struct SectionTable {
@@ -153,6 +176,8 @@ class ShellSystem {
     void set_sections(const SectionTable &t);       // after set_mesh (femshell_set_mesh forgets the sections)
     // -prescribed: the file's values (after set_mesh; throws on a node the mesh does not have, with file and line)
     void set_prescribed(const Parameters &p);
+    // -pressure / -element_loads / -gravity: the rows of build_element_loads (after set_mesh)
+    void set_element_loads(const ElementLoads &l);
     // -reactions: r = K_unc u - loads of the last solve's solution, n_nodes x 6
     std::vector<double> reactions();
     // -stress: the element resultants of the last solve's solution, (n_tri + n_quad) x 14, triangles then quadrilaterals

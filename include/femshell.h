@@ -138,6 +138,40 @@ int femshell_set_prescribed(femshell_ctx *ctx, int32_t n, const int32_t *node_id
  * Nodes not listed get zero load.  Only the right-hand side is rebuilt. */
 int femshell_set_loads(femshell_ctx *ctx, int32_t n, const int32_t *node_ids, const double *f6);
 
+/* extends: the reference knows nodal forces only (its `_f` file; its mesh generator lumps a pressure to nodes by an h^2 rule)
+ * to DISTRIBUTED loads per element: pressure on the surface, weight or snow per area.  Per element four doubles (p, qx, qy, qz):
+ *   p   pressure, force per area, along the element's own +ez: the normal K is built with and the "top surface" of
+ *       femshell_element_resultants.  TRI3: ez || (b-a) x (c-a); QUAD4: ez || d1 x d2 with the diagonals d1 = c-a, d2 = d-b
+ *       (the direction of the element frame's ez: (mid1-mid3) x (mid2-mid0) = d1 x d2 / 2).  The load is DEAD: it follows the
+ *       undeformed geometry, it is not a follower load.
+ *   q   traction, force per area of the element's true area, in global axes (self-weight rho t g, snow).
+ * The nodal equivalents are LUMPED, with the shares of femshell_lumped_mass:
+ *     TRI3   every node gets  p (b-a) x (c-a) / 6 + q A / 3,   A = |(b-a) x (c-a)| / 2
+ *     QUAD4  every node gets  p (d1 x d2) / 8     + q A / 4,   A = |d1 x d2| / 2
+ * on u, v, w; the rotational rows receive nothing.  The pressure part is the exact resultant of p on the element (the vector area
+ * of a skew quadrilateral is d1 x d2 / 2); the traction part with q = rho t g is g times the element's translational lumped
+ * mass.  This is the work-equivalent load of the linear / bilinear membrane interpolation: the consistent nodal MOMENTS of
+ * Specht's and the DKQ bending fields are left out on purpose.  The deflection converges with h^2.
+ * S_a = the sum over the elements that contain node a, taken in the order of the element list of the node's slice, starting from
+ * zero, without atomics: bitwise reproducible, independent of grid and tile size.  The loads in force are
+ *     loads_a = nodal_a + S_a   (one rounding),
+ * nodal the loads of femshell_set_loads: F, the right-hand side with prescribed values, femshell_reactions (K_unc u - (nodal + S):
+ * its force columns balance the total load) and the Newmark right-hand side all see the sum.  A degenerate element contributes
+ * what the formula gives: a zero vector area, no status.
+ * tri_load[n_tri][4] / quad_load[n_quad][4]: rows in the caller's element order; every rank passes the full arrays (as for
+ * femshell_set_sections).  NULL for one kind leaves that kind unloaded; both NULL clears the element loads.  The call replaces the
+ * previous set; only the right-hand side is rebuilt, and the nodal loads are not uploaded again (32 bytes per local element are).
+ * Allowed wherever femshell_set_loads is: while dynamics is active (F of the next step), with prescribed values in force, on
+ * row-partitioned contexts.  FEMSHELL_ERR_INVALID (a non-finite value, no mesh) leaves what was in force untouched.
+ * femshell_set_mesh forgets the element loads; femshell_set_sections and femshell_set_density do not touch them (the values are
+ * the caller's per-area numbers).  Kernel: csrc/element_loads.hip. */
+int femshell_set_element_loads(femshell_ctx *ctx, const double *tri_load /* n_tri x 4, or NULL */,
+                               const double *quad_load /* n_quad x 4, or NULL */);
+/* f6_out[n_nodes][6]: S alone, the nodal equivalents of the element loads in force, in the caller's numbering, NOT masked by the
+ * Dirichlet set; on a row-partitioned context every rank receives all rows (gathered like femshell_lumped_mass).  Zeros when no
+ * element loads are set.  Two calls give the same bits. */
+int femshell_element_load_vector(femshell_ctx *ctx, double *f6_out /* n_nodes x 6 */);
+
 /* replaces: assemble_elasticity (SA:1160-1233): element stiffness (initElement, calcPlane,
  * calcPlate, constructStiffnessMatrix, localToGlobalTrafo), constraint handling, add_matrix /
  * add_vector.  K and F stay in HBM. */
@@ -537,7 +571,11 @@ typedef enum femshell_kernel {
     /* k_element_resultants back to back on a hashed displacement vector; needs a mesh only.  bytes_out: 12 / 16 bytes of node ids
      * and 112 bytes of output per element (4 more of a section index where the context has sections), coordinates and
      * displacements (24 + 48 bytes) once per node */
-    FEMSHELL_KERNEL_ELEMENT_RESULTANTS = 12
+    FEMSHELL_KERNEL_ELEMENT_RESULTANTS = 12,
+    /* k_element_loads back to back on hashed element values, from the loads in force into a scratch vector; needs a mesh only, the
+     * loads in force are not disturbed.  bytes_out: 16 bytes of node ids, 4 of element index and 32 of load words per entry of the
+     * slices' element lists, 24 bytes of coordinates per node, 48 bytes of base read and 48 written per owned row */
+    FEMSHELL_KERNEL_ELEMENT_LOADS = 13
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
