@@ -21,6 +21,7 @@ KERNEL_SPMM, KERNEL_GRAM, KERNEL_BLOCK_COMBINE = 8, 9, 10
 KERNEL_ELEMENT_PRODUCT = 11
 KERNEL_ELEMENT_RESULTANTS = 12
 KERNEL_ELEMENT_LOADS = 13
+KERNEL_GEOMETRIC_PRODUCT = 14
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -37,6 +38,7 @@ SYMBOLS = [
     "femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram",
     "femshell_set_prescribed", "femshell_reactions", "femshell_element_product", "femshell_element_resultants",
     "femshell_set_element_loads", "femshell_element_load_vector",
+    "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
 ]
 
 
@@ -85,6 +87,18 @@ class ModalInfo(C.Structure):
                 ("fused_product", C.c_int32), ("pc_type", C.c_int32), ("residual_max", C.c_double),
                 ("seconds_total", C.c_double), ("seconds_product", C.c_double), ("seconds_precond", C.c_double),
                 ("seconds_gram", C.c_double), ("seconds_update", C.c_double), ("pc_setup_seconds", C.c_double)]
+
+
+class BucklingOptions(C.Structure):
+    _fields_ = [("n_modes", C.c_int32), ("guard", C.c_int32), ("max_it", C.c_int32), ("reserved", C.c_int32),
+                ("tol", C.c_double), ("inner_rtol", C.c_double)]
+
+
+class BucklingInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("block", C.c_int32), ("pc_type", C.c_int32),
+                ("inner_iterations", C.c_int64), ("rho_max", C.c_double),
+                ("seconds_total", C.c_double), ("seconds_solves", C.c_double), ("seconds_products", C.c_double),
+                ("seconds_gram", C.c_double), ("seconds_update", C.c_double)]
 
 
 PC_BLOCK_JACOBI, PC_AMG = 0, 1
@@ -196,6 +210,9 @@ def load_library():
     L.femshell_element_resultants.argtypes = [vp, dp, dp]
     L.femshell_set_element_loads.argtypes = [vp, dp, dp]
     L.femshell_element_load_vector.argtypes = [vp, dp]
+    L.femshell_geometric_product.argtypes = [vp, dp, C.c_int32, dp, dp]
+    L.femshell_buckling_defaults.argtypes = [C.POINTER(BucklingOptions)]
+    L.femshell_buckling.argtypes = [vp, C.POINTER(BucklingOptions), dp, dp, dp, dp, C.POINTER(BucklingInfo)]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -422,6 +439,34 @@ class FemShell:
         Y = np.zeros_like(X)
         _check(self._L.femshell_spmm(self._h, X.shape[0], _d(X), _d(Y)))
         return Y.reshape(shape)
+
+    def geometric_product(self, u, X):
+        """Y = K_G(u) X, unconstrained: the geometric (initial-stress) stiffness of the membrane forces of u (u None: of the last
+        solution, prescribed part included) times a block X of shape (n_cols, n_nodes * 6) or (n_cols, n_nodes, 6), or one vector
+        of n_nodes x 6 entries: femshell_geometric_product"""
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        shape = X.shape
+        X = X.reshape(1, -1) if X.size == 6 * self.n_nodes else X.reshape(shape[0], -1)
+        if X.shape[1] != 6 * self.n_nodes:
+            raise ValueError("X needs n_nodes x 6 entries per column")
+        Y = np.zeros_like(X)
+        _check(self._L.femshell_geometric_product(self._h, _d(self._node_vector(u, "u")), X.shape[0], _d(X), _d(Y)))
+        return Y.reshape(shape)
+
+    def buckling(self, n_modes=4, guard=4, tol=1e-8, max_it=100, u=None, inner_rtol=0.0, want_modes=True):
+        """The n_modes load factors of smallest magnitude of (K + lambda K_G(u)) x = 0 on the free dofs, signed and ordered by
+        |lambda| (femshell_buckling): returns (lam[n_modes], modes (n_modes, n_nodes, 6) each with its largest translational entry
+        +1, or None, info dict with the convergence measures under "rho").  u None: the prestress of the last solution."""
+        o = BucklingOptions(int(n_modes), int(guard), int(max_it), 0, float(tol), float(inner_rtol))
+        nm = max(int(n_modes), 0)
+        lam = np.zeros(nm)
+        rho = np.zeros(nm)
+        modes = np.zeros((nm, self.n_nodes, 6)) if want_modes else None
+        info = BucklingInfo()
+        _check(self._L.femshell_buckling(self._h, C.byref(o), _d(self._node_vector(u, "u")), _d(lam), _d(modes), _d(rho), C.byref(info)))
+        d = {f[0]: getattr(info, f[0]) for f in BucklingInfo._fields_}
+        d["rho"] = rho
+        return lam, modes, d
 
     def modal_gram(self, A, B, weighted):
         """A^T diag(w) B by the Gram kernel of modes(): A (qa, n_nodes * 6), B (qb, n_nodes * 6), columns as rows of the arrays;

@@ -340,6 +340,54 @@ int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, fe
     return FEMSHELL_OK;
 }
 
+// x = K^-1 b from zero by the context's CG and preconditioner, for a right-hand side and a target that are not the context's
+// (femshell_buckling; b: n_pad x 6, x: (n_pad + n_ghost) x 6, both in HBM and zero on the constrained dofs).  The caller has made
+// K, block-Jacobi and, under AMG, the hierarchy valid.  Of the context only work vectors change: F, the last solution, its
+// history, the warm-start flag and the refinement statistics of the last femshell_solve stay.  A breakdown of the
+// multigrid-preconditioned recurrence under single-precision copies rebuilds the hierarchy in FP64 once, as femshell_solve does.
+// *iters: the iterations of the solve; *converged: 1 when the recurrence met rtol.
+int solve_vector(femshell_ctx *c, const double *b, double *x, double rtol, int32_t max_it, int32_t *iters, int32_t *converged)
+{
+    const bool use_amg = c->pc.type == FEMSHELL_PC_AMG;
+    hipStream_t st = c->stream;
+    CgVectors v = cg_vectors(c);
+    v.b = b;
+    v.x = x;
+    v.hist = nullptr; // (the history of the last femshell_solve stays)
+    v.hist_cap = 0;
+    const bool single_reduction = !use_amg && use_single_reduction(c);
+    const femshell_ctx::RefineStats kept = c->refine;
+    CgScalars hs{};
+    int rc = FEMSHELL_OK;
+    for (int attempt = 0;; attempt++) {
+        if (use_amg && (rc = ensure(c, kHierarchy))) break;
+        if (hipSuccess != c->scal.zero(st)) {
+            rc = set_err(FEMSHELL_ERR_HIP, "solve_vector: clearing the scalars of the recurrence failed");
+            break;
+        }
+        double true_rr = -1.0, rec_rr = -1.0;
+        rc = use_amg ? cg_amg(c, v, rtol, max_it, &true_rr, &rec_rr, nullptr)
+                     : single_reduction ? cg_single_reduction(c, v, rtol, max_it) : cg_classic(c, v, rtol, max_it, nullptr);
+        if (rc) break;
+        if (hipSuccess != hipMemcpyAsync(&hs, v.s, sizeof hs, hipMemcpyDeviceToHost, st) || hipSuccess != hipStreamSynchronize(st)) {
+            rc = set_err(FEMSHELL_ERR_HIP, "solve_vector: reading the scalars of the recurrence failed");
+            break;
+        }
+        const bool had_copies = use_amg && amg_uses_single_precision(*c->amg);
+        if (use_amg && hs.done < 0 && attempt == 0 && !c->amg_fp64_only && had_copies) {
+            invalidate(c, Change::fp64_fallback);
+            continue;
+        }
+        break;
+    }
+    c->refine = kept;
+    if (rc) return rc;
+    if (iters) *iters = hs.iters;
+    if (converged) *converged = hs.done == 1 ? 1 : 0;
+    if (hs.done < 0) return set_err(FEMSHELL_ERR_BREAKDOWN, "CG breakdown in an inner solve, p.Ap <= 0 (K is not positive definite on the free dofs)");
+    return FEMSHELL_OK;
+}
+
 } // namespace femshell
 
 int clear_status_word(femshell_ctx *c, hipStream_t st)

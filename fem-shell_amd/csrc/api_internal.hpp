@@ -21,6 +21,7 @@ int check_status(femshell_ctx *c, const char *what);
 int check_and_agree(femshell_ctx *c, const char *what);
 int agree_status(femshell_ctx *c, int local_rc, const char *what, bool neutral = false);
 int solve_system(femshell_ctx *c, double rtol, int32_t max_it, double *u_out, femshell_solve_info *info, bool dynamic);
+int solve_vector(femshell_ctx *c, const double *b, double *x, double rtol, int32_t max_it, int32_t *iters, int32_t *converged);
 
 // seconds of what ensure() had to do (0: the product was there)
 struct Timings {
@@ -53,6 +54,9 @@ double bytes_update_single_reduction(const femshell_ctx *c);
 double bytes_element_resultants(const femshell_ctx *c);
 double bytes_element_loads(const femshell_ctx *c);
 int time_element_loads(femshell_ctx *c, int32_t reps, double *mean_ms_out);
+double bytes_geometric_product(const femshell_ctx *c, int cols);
+int time_geometric_product(femshell_ctx *c, int32_t reps, double *mean_ms_out);
+int geometric_coefficients(femshell_ctx *c, const double *u, DevBuf<double> *coeff, const char *what);
 int upload_section_thickness(femshell_ctx *c, DevBuf<double> *buf, const double **sec_t);
 
 } // namespace femshell

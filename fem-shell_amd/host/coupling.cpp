@@ -306,6 +306,11 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
         out << "Read command-line arguments.......FAILED" << std::endl;
         return -1;
     }
+    if (p.buckling_requested()) {
+        err << "ERROR: -buckling is an option of the stand-alone program FEM-shell!\n";
+        out << "Read command-line arguments.......FAILED" << std::endl;
+        return -1;
+    }
     if (p.prescribed_requested() || p.reactions || p.stress) {
         err << "ERROR: -prescribed / -reactions / -stress are options of the stand-alone program FEM-shell!\n";
         out << "Read command-line arguments.......FAILED" << std::endl;

@@ -187,7 +187,11 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "\t in mesh-file order, the index of <out>_stress.txt; elements not listed get zero (optional)\n"
             << "-gravity:\t gx gy gz: self-weight rho t g per area of every element, t the element's own under -sections (needs -rho; without\n"
             << "\t -dt / -steps the solve stays static)\n"
-            << "\t -pressure, -element_loads and -gravity add up and come on top of the force file's nodal loads; not with -modes\n";
+            << "\t -pressure, -element_loads and -gravity add up and come on top of the force file's nodal loads; not with -modes\n"
+            << "-buckling:\t after the static solve: the N load factors of smallest magnitude (signed) at which the solved load case\n"
+            << "\t buckles, N in 1 .. 28; writes <out>_buckling.txt, lines 'index lambda rho', and the shapes as point arrays\n"
+            << "\t buckling_<k>_u / buckling_<k>_r of <out>.vtk (optional; not with -modes or -dt / -steps)\n"
+            << "-buckling_tol:\t tolerance of the pairs' convergence measure rho (with -buckling, default 1e-8)\n";
         return false;
     }
     bool failed = false;
@@ -341,6 +345,35 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
         p.modes_shift = v ? std::atof(v) : -1.0;
         if (!(std::isfinite(p.modes_shift) && p.modes_shift >= 0.0)) {
             err << "ERROR: -modes_shift must be a shift >= 0!\n";
+            failed = true;
+        }
+    }
+    // linear buckling: refused here like the options above
+    if (has_flag(argc, argv, "-buckling")) {
+        const char *v = arg_after(argc, argv, "-buckling");
+        p.buckling = v ? std::atoi(v) : 0;
+        if (p.buckling < 1 || p.buckling > 28) {
+            err << "ERROR: -buckling must be a number of load factors in 1 .. 28!\n";
+            p.buckling = 0;
+            failed = true;
+        }
+        if (has_flag(argc, argv, "-modes")) {
+            err << "ERROR: -buckling follows the static solve: it does not go together with -modes!\n";
+            failed = true;
+        }
+        if (has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps")) {
+            err << "ERROR: -buckling follows the static solve: it does not go together with the time stepping options -dt / -steps!\n";
+            failed = true;
+        }
+    } else if (has_flag(argc, argv, "-buckling_tol")) {
+        err << "ERROR: -buckling_tol needs a number of load factors, -buckling!\n";
+        failed = true;
+    }
+    if (has_flag(argc, argv, "-buckling_tol")) {
+        const char *v = arg_after(argc, argv, "-buckling_tol");
+        p.buckling_tol = v ? std::atof(v) : 0.0;
+        if (!(std::isfinite(p.buckling_tol) && p.buckling_tol > 0.0)) {
+            err << "ERROR: -buckling_tol must be a tolerance > 0!\n";
             failed = true;
         }
     }
@@ -742,6 +775,20 @@ femshell_modal_info ShellSystem::modes(const Parameters &p, std::vector<double> 
     return info;
 }
 
+femshell_buckling_info ShellSystem::buckling(const Parameters &p, std::vector<double> &lambda, std::vector<double> &shapes, std::vector<double> &rho)
+{
+    femshell_buckling_options o;
+    check(femshell_buckling_defaults(&o), "femshell_buckling_defaults");
+    o.n_modes = p.buckling;
+    o.tol = p.buckling_tol;
+    lambda.assign((size_t)p.buckling, 0.0);
+    rho.assign((size_t)p.buckling, 0.0);
+    shapes.assign((size_t)p.buckling * (size_t)n_nodes_ * 6, 0.0);
+    femshell_buckling_info info{};
+    check(femshell_buckling(ctx_, &o, nullptr, lambda.data(), shapes.data(), rho.data(), &info), "femshell_buckling");
+    return info;
+}
+
 namespace {
 double wall_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 } // namespace
@@ -825,6 +872,7 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         if (p.element_loads_requested()) system.set_element_loads(element_loads); // (on top of the force file's nodal loads)
         if (p.reactions && launch.world_size != 1) throw std::runtime_error("-reactions runs on one rank");
         if (p.stress && launch.world_size != 1) throw std::runtime_error("-stress runs on one rank");
+        if (p.buckling_requested() && launch.world_size != 1) throw std::runtime_error("-buckling runs on one rank");
         clock.done("symbolic phase, boundary conditions, loads");
         if (p.modes_requested()) {
             // natural frequencies and mode shapes instead of a solve
@@ -1007,14 +1055,47 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
             }
             out << "Element resultants: largest surface von Mises stress = " << worst << ", in " << stem << "_stress.txt" << std::endl;
         }
+        bool buckling_converged = true;
+        if (p.buckling_requested()) {
+            // at what multiple of the solved load case the shell buckles, and in which shapes: the prestress is the solution's
+            std::vector<double> lambda, shapes, rho;
+            const femshell_buckling_info bi = system.buckling(p, lambda, shapes, rho);
+            clock.done("buckling analysis");
+            buckling_converged = bi.converged == p.buckling;
+            const std::string stem = p.isOutfileSet ? p.out_filename : std::string("out");
+            std::ofstream bf(stem + "_buckling.txt");
+            if (!bf) throw std::runtime_error("cannot write " + stem + "_buckling.txt");
+            bf << "# mode lambda rho\n"
+               << "# lambda: load factor of (K + lambda K_G) x = 0, signed, by magnitude; rho: ||A x - mu K x||_{K^-1} / (|mu| ||x||_K), mu = 1 / lambda\n";
+            for (int k = 0; k < p.buckling; k++) {
+                char line[120];
+                snprintf(line, sizeof line, "%d %.15e %.15e\n", k + 1, lambda[(size_t)k], rho[(size_t)k]);
+                bf << line;
+            }
+            out << "Linear buckling: " << bi.converged << " of " << p.buckling << " pairs converged in " << bi.iterations << " iterations of a block of "
+                << bi.block << " (" << bi.inner_iterations << " CG iterations of the "
+                << (bi.pc_type == FEMSHELL_PC_AMG ? "multigrid-preconditioned" : "6x6 block-Jacobi") << " inner solves, tolerance " << p.buckling_tol
+                << "), worst rho " << bi.rho_max << "; load factors in " << stem << "_buckling.txt" << std::endl;
+            for (int k = 0; k < p.buckling; k++) out << " buckling mode " << k + 1 << ": lambda = " << lambda[(size_t)k] << std::endl;
+            const size_t n6 = (size_t)mesh.n_nodes() * 6;
+            for (int k = 0; k < p.buckling; k++)
+                for (int part = 0; part < 2; part++) {
+                    PointVectors a;
+                    a.name = "buckling_" + std::to_string(k + 1) + (part == 0 ? "_u" : "_r");
+                    a.xyz.resize((size_t)mesh.n_nodes() * 3);
+                    for (int32_t n = 0; n < mesh.n_nodes(); n++)
+                        for (int d = 0; d < 3; d++) a.xyz[3 * (size_t)n + d] = shapes[(size_t)k * n6 + 6 * (size_t)n + 3 * part + d];
+                    reaction_arrays.push_back(std::move(a)); // (the point arrays of <out>.vtk: reactions, then buckling shapes)
+                }
+        }
         if (p.isOutfileSet) {
             write_exodus(mesh, sols, p.out_filename + ".e"); // the reference's file (fem-shell.cpp:1249)
-            write_vtk(mesh, sols, p.out_filename + ".vtk", p.reactions ? &reaction_arrays : nullptr, p.stress ? &stress_arrays : nullptr);
+            write_vtk(mesh, sols, p.out_filename + ".vtk", reaction_arrays.empty() ? nullptr : &reaction_arrays, p.stress ? &stress_arrays : nullptr);
             clock.done("output files");
         }
         out << "All done :)\n";
         clock.report(err);
-        return res.converged ? 0 : 2;
+        return res.converged && buckling_converged ? 0 : 2;
     } catch (const std::exception &e) {
         err << "ERROR: " << e.what() << std::endl;
         return 1;

@@ -100,6 +100,14 @@ struct Parameters {
     std::vector<int> element_load_lines;     // ... and its line number
     std::vector<double> element_load_values; // ... and its four values
     bool element_loads_requested() const { return pressure_set || gravity_set || !element_loads_file.empty(); }
+    // linear buckling (extension, stand-alone program only; the reference has no stability analysis): -buckling N [-buckling_tol T],
+    // after the static solve, computes the N load factors of smallest magnitude of (K + lambda K_G(u)) x = 0 with the prestress of
+    // the solution (femshell_buckling); writes <out>_buckling.txt -- a '#' header, then a line "index lambda rho" (%.15e) per mode
+    // -- and the shapes as point arrays buckling_<k>_u / buckling_<k>_r of <out>.vtk.  N in 1 .. 28 (the library's block of N + 4
+    // vectors holds at most 32).  Not with -modes or -dt / -steps.
+    int buckling = 0;
+    double buckling_tol = 1e-8;
+    bool buckling_requested() const { return buckling > 0; }
 };
 
 // what femshell_set_element_loads takes: rows (p, qx, qy, qz) of the triangles and of the quadrilaterals
@@ -199,6 +207,9 @@ class ShellSystem {
     // modal analysis: density -rho, then femshell_modes with the library's defaults for guard and iteration limit; lambda[n],
     // modes[n][n_nodes][6], residual[n]
     femshell_modal_info modes(const Parameters &p, std::vector<double> &lambda, std::vector<double> &modes, std::vector<double> &residual);
+    // linear buckling under the prestress of the last solve: femshell_buckling with the library's defaults for guard and iteration
+    // limit; lambda[n], shapes[n][n_nodes][6], rho[n]
+    femshell_buckling_info buckling(const Parameters &p, std::vector<double> &lambda, std::vector<double> &shapes, std::vector<double> &rho);
     femshell_ctx *handle() { return ctx_; }
 
   private:

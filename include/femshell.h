@@ -477,6 +477,70 @@ int femshell_modal_defaults(femshell_modal_options *out);   /* n_modes 6, guard 
 int femshell_modes(femshell_ctx *ctx, const femshell_modal_options *opt, double *lambda_out /* n_modes */,
                    double *modes_out /* n_modes x n_nodes x 6, or NULL */, double *residual_out /* n_modes, or NULL */,
                    femshell_modal_info *info);
+/* ---- geometric (initial-stress) stiffness ------------------------------------------------------------------------------------
+ * extends: the reference has no stability analysis; this is the operator linear buckling adds to K, (K + lambda K_G) x = 0.
+ *
+ * Prestress.  The prestress of an element is its element-mean membrane force N_loc = (Nxx, Nyy, Nxy) of
+ * femshell_element_resultants, from the displacement vector u (n_nodes x 6, the caller's numbering), or u == NULL: from the solution
+ * of the last solve, prescribed part included.  The element's own section applies.
+ * Element matrix.  With phi_a the membrane shape functions in the element frame's in-plane coordinates -- TRI3: linear, one point
+ * of weight A; QUAD4: bilinear, at the stiffness's 2 x 2 Gauss points with weight det J --
+ *     g_ab = sum_gp w_gp grad phi_a(gp)^T [[Nxx, Nxy], [Nxy, Nyy]] grad phi_b(gp)      (symmetric; rows sum to 0)
+ *     K_G,e[a, b] = g_ab I3 on the translations (u, v, w), zero on the three rotations:
+ * the full Green-Lagrange term on all three translations, which needs no local-to-global rotation and gives a rigid translation
+ * zero geometric energy.  K_G is never stored: the unique g_ab of every element (6 or 10 doubles) are, and the product walks the
+ * slices' element lists (csrc/geometric_stiffness.hip).
+ *
+ * femshell_geometric_product: Y = K_G(u) X, UNCONSTRAINED (whatever femshell_set_dirichlet holds), for n_cols (1 .. 96) columns of
+ * n_nodes x 6 in the caller's numbering, column j at X + j * n_nodes * 6.  The rotational rows are exactly zero.  Needs a mesh
+ * only.  The additions of a row run in the order of its slice's element list, without atomics: two calls give the same bits,
+ * column j of a block is bitwise the single-column product, and the NULL form gives the bits of the explicit one.  A degenerate
+ * element: FEMSHELL_ERR_MESH.  FEMSHELL_ERR_UNSUPPORTED on a row-partitioned context (world_size != 1); FEMSHELL_ERR_INVALID
+ * while dynamics is active, without a mesh, for the NULL form before any solve, for a non-finite u, for n_cols out of range.  The
+ * context stays usable after every refusal. */
+int femshell_geometric_product(femshell_ctx *ctx, const double *u /* n_nodes x 6, or NULL */, int32_t n_cols /* 1 .. 96 */,
+                               const double *X, double *Y);
+
+/* ---- linear buckling: load factors and buckling shapes ------------------------------------------------------------------
+ * extends: the reference has no stability analysis; with the geometric stiffness above this solves the pencil
+ *     (K + lambda K_G(u)) x = 0
+ * on the free dofs of the Dirichlet set: at lambda times the load that produced u the shell buckles in the shape x.  Returned are
+ * the n_modes factors of SMALLEST MAGNITUDE, SIGNED, ordered by |lambda|, a positive one before a negative one of equal magnitude.
+ * A negative factor means the shell buckles under the reversed load; shear gives +- pairs.  (Magnitudes that agree to `tol` count
+ * as equal: the two members of such a pair differ by rounding only.)
+ *
+ * Method (csrc/buckling.cpp): block inverse iteration with Rayleigh-Ritz on A x = mu K x, A = -K_G, mu = 1 / lambda, with a block
+ * of mb = n_modes + guard columns: mb solves with K per iteration by the context's CG and preconditioner (femshell_set_preconditioner),
+ * the block product of femshell_modes, k_geometric_product, the Gram kernel, Cholesky and Jacobi on the host.  Pair j has converged
+ * when
+ *     rho_j = ||A x_j - mu_j K x_j||_{K^-1} / (|mu_j| ||x_j||_K) <= tol
+ * (some eigenvalue mu lies within rho_j |mu_j| of mu_j); the pairs returned have passed the test with a solve and products of their
+ * own.  The inner solves run to the relative residual inner_rtol (0: tol / 100).  Reaching max_it returns FEMSHELL_OK with
+ * info->converged < n_modes and the best pairs the call has.
+ *
+ * u: the displacements whose membrane forces are the prestress (n_nodes x 6), or NULL: the solution of the last solve, prescribed
+ * part included.  lambda_out[n_modes]; modes_out (n_modes x n_nodes x 6, the caller's numbering, or NULL): each scaled so that its
+ * translational entry of largest magnitude is +1 (lowest index on ties); rho_out[n_modes] (or NULL).  Two calls give the same bits.
+ * After the call the context is as it was: F, the last solution, a pending initial guess, K, block-Jacobi and the hierarchy (which
+ * the call builds where they were not there; a breakdown of the multigrid-preconditioned solve under single-precision copies
+ * rebuilds the hierarchy in FP64 as femshell_solve does).
+ * FEMSHELL_ERR_BREAKDOWN: no prestress at all (K_G = 0), Gram matrices that are not finite, a Y^T K Y that is not positive
+ * definite (K_G has too low a rank for the block: reduce n_modes + guard).  FEMSHELL_ERR_INVALID, the context left as it was: no
+ * mesh, the NULL form before any solve, a non-finite u, n_modes < 1, guard < 0, n_modes + guard > 32, fewer than
+ * 2 (n_modes + guard) free translational dofs, tol <= 0, inner_rtol < 0, max_it < 1, dynamics active.  FEMSHELL_ERR_UNSUPPORTED: a
+ * row-partitioned context (world_size != 1). */
+typedef struct femshell_buckling_options { int32_t n_modes, guard, max_it, reserved; double tol, inner_rtol; } femshell_buckling_options;
+typedef struct femshell_buckling_info {
+    int32_t iterations, converged /* pairs */, block /* mb */, pc_type;
+    int64_t inner_iterations;   /* CG iterations of all inner solves */
+    double rho_max;             /* worst rho of the returned pairs */
+    double seconds_total, seconds_solves, seconds_products, seconds_gram, seconds_update;
+} femshell_buckling_info;
+int femshell_buckling_defaults(femshell_buckling_options *out);   /* n_modes 4, guard 4, max_it 100, tol 1e-8, inner_rtol 0 (tol / 100) */
+int femshell_buckling(femshell_ctx *ctx, const femshell_buckling_options *opt, const double *u /* n_nodes x 6, or NULL */,
+                      double *lambda_out /* n_modes */, double *modes_out /* n_modes x n_nodes x 6, or NULL */,
+                      double *rho_out /* n_modes, or NULL */, femshell_buckling_info *info);
+
 /* test entry: G = A^T diag(w) B (qa x qb, row-major) by the solver's Gram kernel; A, B: qa / qb columns of n_nodes x 6 in the
  * caller's numbering, 1 <= qa, qb <= 96; weighted != 0: w = the lumped mass (a density must be set), else w = 1.  Partial sums
  * are added in a fixed order: two calls give the same bits. */
@@ -575,7 +639,11 @@ typedef enum femshell_kernel {
     /* k_element_loads back to back on hashed element values, from the loads in force into a scratch vector; needs a mesh only, the
      * loads in force are not disturbed.  bytes_out: 16 bytes of node ids, 4 of element index and 32 of load words per entry of the
      * slices' element lists, 24 bytes of coordinates per node, 48 bytes of base read and 48 written per owned row */
-    FEMSHELL_KERNEL_ELEMENT_LOADS = 13
+    FEMSHELL_KERNEL_ELEMENT_LOADS = 13,
+    /* k_geometric_product, one pass of four columns back to back on hashed coefficients and hashed vectors; needs a mesh only.
+     * bytes_out: 16 bytes of node ids, 4 of element index and 48 (80 on a mesh with quadrilaterals) of coefficients per entry of
+     * the slices' element lists, 24 bytes read and 48 written per owned row and column */
+    FEMSHELL_KERNEL_GEOMETRIC_PRODUCT = 14
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
