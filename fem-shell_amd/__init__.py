@@ -28,6 +28,7 @@ from .binding import (  # noqa: F401
     REORDER_RCM,
     build_library,
     comm_unique_id,
+    pool_stats,
     grid_cap,
     knob_flag,
     knob_long,

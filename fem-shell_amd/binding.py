@@ -39,6 +39,7 @@ SYMBOLS = [
     "femshell_set_prescribed", "femshell_reactions", "femshell_element_product", "femshell_element_resultants",
     "femshell_set_element_loads", "femshell_element_load_vector",
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
+    "femshell_pool_stats",
 ]
 
 
@@ -213,6 +214,7 @@ def load_library():
     L.femshell_geometric_product.argtypes = [vp, dp, C.c_int32, dp, dp]
     L.femshell_buckling_defaults.argtypes = [C.POINTER(BucklingOptions)]
     L.femshell_buckling.argtypes = [vp, C.POINTER(BucklingOptions), dp, dp, dp, dp, C.POINTER(BucklingInfo)]
+    L.femshell_pool_stats.argtypes = [dp]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -237,6 +239,15 @@ def _b(a):
 def _check(rc):
     if rc != 0:
         raise FemShellError(rc, load_library().femshell_last_error().decode())
+
+
+def pool_stats():
+    """The device pool of this process as it stands (csrc/dev_pool.hpp; no context needed): bytes the driver has handed out through
+    the pool, bytes in use, bytes kept for reuse, arenas and the bytes in them, blocks waiting for the end of a multigrid setup."""
+    out = np.zeros(6)
+    _check(load_library().femshell_pool_stats(_d(out)))
+    return {"outstanding": int(out[0]), "live": int(out[1]), "cached": int(out[2]), "arenas": int(out[3]),
+            "arena_bytes": int(out[4]), "pending": int(out[5])}
 
 
 def comm_unique_id():

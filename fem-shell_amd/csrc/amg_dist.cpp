@@ -815,7 +815,7 @@ int amg_setup_dist(femshell_ctx *c)
 {
     TraceRange trace("femshell multigrid setup (row-partitioned)");
     const double t0 = now_s();
-    DevPool::Defer no_sync_per_free; // (buffers released during the setup join the pool at its end: context.hpp)
+    DevPool::Defer no_sync_per_free; // (buffers released during the setup join the pool at its end: dev_pool.hpp)
     hipStream_t st = c->stream;
     const femshell_pc_options opt = c->pc;
     const bool kcycle = opt.cycle == FEMSHELL_CYCLE_K;

@@ -472,7 +472,7 @@ int amg_setup(femshell_ctx *c)
 {
     TraceRange trace("femshell multigrid setup");
     const double t0 = now_s();
-    DevPool::Defer no_sync_per_free; // (buffers released during the setup join the pool at its end: context.hpp)
+    DevPool::Defer no_sync_per_free; // (buffers released during the setup join the pool at its end: dev_pool.hpp)
     hipStream_t st = c->stream;
     const femshell_pc_options opt = c->pc;
     const bool kcycle = opt.cycle == FEMSHELL_CYCLE_K;
@@ -895,7 +895,7 @@ int amg_finish_hierarchy(femshell_ctx *c, Bsr &A, std::vector<double> &B, DevBuf
         // 1 (default): levels of at least 4096 nodes; 2: level 0 only, 3: every level, whatever their size (A/B runs, tests); 0: off.
         const int mode = c->amg_fp64_only ? 0 : (int)knob_long("FEMSHELL_AMG_SMOOTH_F32", 1);
         // (what the coarsening steps released -- A P, Q, the symbolic buffers -- joins the pool's kept blocks now: the copies below are
-        //  carved from them instead of being fresh requests to the driver, context.hpp DevPool::alloc (3))
+        //  carved from them instead of being fresh requests to the driver, dev_pool.hpp DevPool::alloc (3))
         if (mode != 0) (void)DevPool::get().flush_pending();
         for (size_t l = 0; l + 1 < H.levels.size(); l++) {
             AmgLevel &L = *H.levels[l];

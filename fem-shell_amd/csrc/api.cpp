@@ -1299,6 +1299,13 @@ int femshell_amg_symbolic_info(femshell_ctx *c, int32_t out[3])
     return FEMSHELL_OK;
 }
 
+int femshell_pool_stats(double out[6])
+{
+    if (!out) return set_err(FEMSHELL_ERR_INVALID, "femshell_pool_stats: null argument");
+    DevPool::get().counters(out);
+    return FEMSHELL_OK;
+}
+
 int femshell_amg_partition_info(femshell_ctx *c, double out[6])
 {
     if (!c || !out) return set_err(FEMSHELL_ERR_INVALID, "femshell_amg_partition_info: null argument");

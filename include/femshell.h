@@ -320,6 +320,12 @@ int femshell_amg_symbolic_info(femshell_ctx *ctx, int32_t out[3]);
  * out[2] = flops issued on the matrix cores, out[3] = n^3 (the flops of a symmetric inversion), out[4] = dropped
  * (semi-definite) directions, out[5] = bytes of the lower triangle read and written over all steps */
 int femshell_amg_dense_stats(femshell_ctx *ctx, double out[6]);
+/* The device-memory pool of this process as it stands (csrc/dev_pool.hpp; every buffer of every context comes out of it, so the
+ * call takes no context and also answers after the last one was destroyed): out[0] = bytes the driver has handed out through
+ * the pool and not got back, out[1] = bytes in use by buffers, out[2] = bytes kept for reuse (what FEMSHELL_POOL_GB bounds),
+ * out[3] = arenas (blocks that requests are carved from), out[4] = the bytes in them, out[5] = blocks that wait for the end of
+ * a multigrid setup.  The counters are the pool's own; all six are zero once the last context is gone. */
+int femshell_pool_stats(double out[6]);
 /* Multigrid hierarchy of a row-partitioned context (the reference's PETSc preconditioner lives on the distributed matrix,
  * doc/implementation.tex:463-472): out[0] = levels whose rows are split over the ranks (0: single-rank context), out[1] =
  * bytes of this rank's operators on those levels (they shrink with the rank count), out[2] = bytes of the levels below,

@@ -1,6 +1,6 @@
 """Does the device pool settle when a hierarchy is rebuilt again and again?  4M-triangle panel, the multigrid setup repeated after a
 change of the constraint set; HBM in use (torch.cuda.mem_get_info) and the setup's seconds after each.  (round 6: carved blocks,
-deferred releases -- csrc/context.hpp DevPool)"""
+deferred releases -- csrc/dev_pool.hpp DevPool)"""
 import importlib
 import sys
 
