@@ -152,7 +152,7 @@ __device__ __forceinline__ bool quad4_means(const double X[12], const double U[4
     o.ey[0] = o.ez[1] * o.ex[2] - o.ez[2] * o.ex[1];
     o.ey[1] = o.ez[2] * o.ex[0] - o.ez[0] * o.ex[2];
     o.ey[2] = o.ez[0] * o.ex[1] - o.ez[1] * o.ex[0];
-    double x[4], y[4], um[4][2], dp[4][3]; // local coordinates (no translation), local (u, v) and (w, tx, ty) of the nodes
+    double x[4], y[4], um[4][2], dp[4][3]; // local coordinates (of X as given: the caller translates), local (u, v) and (w, tx, ty) of the nodes
 #pragma unroll
     for (int n = 0; n < 4; n++) {
         x[n] = o.ex[0] * X[3 * n] + o.ex[1] * X[3 * n + 1] + o.ex[2] * X[3 * n + 2];
@@ -311,6 +311,12 @@ __global__ __launch_bounds__(kErThreads) void k_element_resultants(DeviceMatrix 
                 X[3 * i + 2] = pt[2];
                 gather_u(u, up, nid[i], U[i]);
             }
+            // coordinates relative to the first node, each difference rounded once: quad4_means projects the coordinates it is
+            // given onto the frame and differences the projections, which at a distance D from the origin costs D / size digits
+#pragma unroll
+            for (int i = 3; i >= 0; i--)
+#pragma unroll
+                for (int d = 0; d < 3; d++) X[3 * i + d] -= X[d];
             ok = quad4_means(X, U, f);
         }
         double tcm = mc.t * mc.cm, cp = mc.cp, nu = mc.nu, g = mc.g, t = mc.t;

@@ -199,6 +199,11 @@ __global__ __launch_bounds__(kGcThreads) void k_geometric_coeff(DeviceMatrix m, 
             X[3 * i + 1] = pt[1];
             X[3 * i + 2] = pt[2];
         }
+        // relative to the first node, as k_element_resultants hands them to quad4_means (quad4_coeff differences projections)
+#pragma unroll
+        for (int i = 3; i >= 0; i--)
+#pragma unroll
+            for (int d = 0; d < 3; d++) X[3 * i + d] -= X[d];
         ok = quad4_coeff(X, N, g);
     }
     if (!ok) report_status(m.status, kStatusDirect + e);

@@ -25,12 +25,12 @@ CLUSTER_GAP = 1e-2
 
 # ------------------------------------------------------------------ element level
 
-def element_prestress(xyz, u, nu, E, t, flags=oracle.REF_DEFAULT, dtype=np.float64):
+def element_prestress(xyz, u, nu, E, t, flags=oracle.REF_DEFAULT, dtype=np.float64, restated=False):
     """(N_loc (3,), S_N (3,), ops): the element-mean membrane force in the element frame, its absolute-sum scale and the
-    operators of resultants.py, all in `dtype`"""
+    operators of resultants.py, all in `dtype`; restated: as rs.element_resultants has it"""
     xyz = np.asarray(xyz, dtype=np.float64)
     nn = len(xyz)
-    ops = rs.tri3_operators(xyz, flags, dtype) if nn == 3 else rs.quad4_operators(xyz, dtype)
+    ops = rs.tri3_operators(xyz, flags, dtype, restated=restated) if nn == 3 else rs.quad4_operators(xyz, dtype, relative=bool(restated))
     T = ops["trafo"]
     ul = np.asarray(u, dtype=dtype).reshape(nn, 6)[:, :3] @ T.T
     dm = ul[:, :2].reshape(-1)
@@ -63,7 +63,8 @@ def _elements(xyz, tri, quad, nu, E, t, sec):
             yield c, m
 
 
-def element_coefficients(xyz, tri, quad, u, nu, E, t, sec=None, flags=oracle.REF_DEFAULT, dtype=np.float64, N_uniform=None):
+def element_coefficients(xyz, tri, quad, u, nu, E, t, sec=None, flags=oracle.REF_DEFAULT, dtype=np.float64, N_uniform=None,
+                         restated=False):
     """list of (conn, g (nn, nn), |g| scale (nn, nn)) per element, triangles then quadrilaterals.  N_uniform = (Nxx, Nyy, Nxy)
     in the global x-y axes: that membrane force in every element, taken into its frame, instead of the one recovered from u (the
     plate checks)."""
@@ -71,7 +72,8 @@ def element_coefficients(xyz, tri, quad, u, nu, E, t, sec=None, flags=oracle.REF
     u = None if u is None else np.asarray(u, dtype=np.float64).reshape(len(xyz), 6)
     out = []
     for c, m in _elements(xyz, tri, quad, nu, E, t, sec):
-        N, SN, ops = element_prestress(xyz[c], np.zeros((len(c), 6)) if u is None else u[c], *m, flags=flags, dtype=dtype)
+        N, SN, ops = element_prestress(xyz[c], np.zeros((len(c), 6)) if u is None else u[c], *m, flags=flags, dtype=dtype,
+                                       restated=restated)
         if N_uniform is not None:
             A = np.zeros((3, 3), dtype=dtype)
             A[0, 0], A[1, 1], A[0, 1], A[1, 0] = N_uniform[0], N_uniform[1], N_uniform[2], N_uniform[2]

@@ -12,26 +12,32 @@ import scipy.sparse.linalg as spla
 from tests.helpers import oracle
 
 
-def element_areas(xyz, tri=None, quad=None):
-    """(areas of the triangles |(b-a) x (c-a)| / 2, areas of the quadrilaterals |d1 x d2| / 2 with the diagonals d1, d2)"""
-    xyz = np.asarray(xyz, dtype=np.float64)
-    at = np.zeros(0)
-    aq = np.zeros(0)
+def _norm(v, dtype):
+    """row-wise 2-norm: np.linalg.norm where it keeps the type (FP64, bit for bit what it always was), else spelt out"""
+    return np.linalg.norm(v, axis=1) if dtype is np.float64 else np.sqrt((v * v).sum(axis=1))
+
+
+def element_areas(xyz, tri=None, quad=None, dtype=np.float64):
+    """(areas of the triangles |(b-a) x (c-a)| / 2, areas of the quadrilaterals |d1 x d2| / 2 with the diagonals d1, d2), in `dtype`"""
+    xyz = np.asarray(xyz, dtype=np.float64).astype(dtype)
+    at = np.zeros(0, dtype)
+    aq = np.zeros(0, dtype)
     if tri is not None and len(tri):
         a, b, c = (xyz[np.asarray(tri)[:, i]] for i in range(3))
-        at = 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
+        at = 0.5 * _norm(np.cross(b - a, c - a), dtype)
     if quad is not None and len(quad):
         a, b, c, d = (xyz[np.asarray(quad)[:, i]] for i in range(4))
-        aq = 0.5 * np.linalg.norm(np.cross(c - a, d - b), axis=1)
+        aq = 0.5 * _norm(np.cross(c - a, d - b), dtype)
     return at, aq
 
 
-def lumped_mass(xyz, tri, quad, rho, thickness, tri_section=None, quad_section=None):
+def lumped_mass(xyz, tri, quad, rho, thickness, tri_section=None, quad_section=None, dtype=np.float64):
     """m[n_nodes, 6]: rho t A / nn on u, v, w and rho t^3/12 A / nn on tx, ty, tz from every element to each of its nn nodes.
-    rho, thickness: scalars, or one entry per section with tri_section / quad_section naming every element's."""
+    rho, thickness: scalars, or one entry per section with tri_section / quad_section naming every element's.  Computed and
+    returned in `dtype`."""
     xyz = np.asarray(xyz, dtype=np.float64)
-    m = np.zeros((len(xyz), 6))
-    at, aq = element_areas(xyz, tri, quad)
+    m = np.zeros((len(xyz), 6), dtype)
+    at, aq = element_areas(xyz, tri, quad, dtype)
     for conn, area, sec in ((tri, at, tri_section), (quad, aq, quad_section)):
         if conn is None or len(conn) == 0:
             continue
@@ -40,6 +46,7 @@ def lumped_mass(xyz, tri, quad, rho, thickness, tri_section=None, quad_section=N
         r = np.broadcast_to(np.asarray(rho, dtype=np.float64), (len(conn),)) if np.ndim(rho) == 0 else np.asarray(rho, dtype=np.float64)[np.asarray(sec)]
         t = (np.broadcast_to(np.asarray(thickness, dtype=np.float64), (len(conn),)) if np.ndim(thickness) == 0
              else np.asarray(thickness, dtype=np.float64)[np.asarray(sec)])
+        r, t = r.astype(dtype), t.astype(dtype)
         for i in range(nn):
             np.add.at(m[:, :3], conn[:, i], (r * t * area / nn)[:, None])
             np.add.at(m[:, 3:], conn[:, i], (r * t ** 3 / 12.0 * area / nn)[:, None])

@@ -1,5 +1,6 @@
 """Element loads (femshell_set_element_loads): the reference of the tests, numpy in longdouble, written from the definition of
-include/femshell.h and not from the kernel.
+include/femshell.h and not from the kernel.  Every function computes in `work` (longdouble unless a caller asks for the same
+formulas in FP64: the reference's own error, tests/helpers/derived_truth.py).
 
 Per element (p, qx, qy, qz).  With the two vectors of the element's cross product -- TRI3: the edges d1 = b - a, d2 = c - a,
 QUAD4: the diagonals d1 = c - a, d2 = d - b -- the vector area is d1 x d2 / 2, the area A its length, and every node of the
@@ -13,9 +14,9 @@ import numpy as np
 LD = np.longdouble
 
 
-def cross_vectors(xyz, conn):
-    """(d1, d2) of every element of conn ((n, 3) triangles or (n, 4) quadrilaterals), longdouble"""
-    x = np.asarray(xyz, dtype=np.float64).astype(LD)
+def cross_vectors(xyz, conn, work=LD):
+    """(d1, d2) of every element of conn ((n, 3) triangles or (n, 4) quadrilaterals), in `work`"""
+    x = np.asarray(xyz, dtype=np.float64).astype(work)
     conn = np.asarray(conn)
     if conn.shape[1] == 3:
         a, b, c = (x[conn[:, i]] for i in range(3))
@@ -24,38 +25,47 @@ def cross_vectors(xyz, conn):
     return c - a, d - b
 
 
-def _kinds(tri, quad, tri_load, quad_load):
+def _kinds(tri, quad, tri_load, quad_load, work=LD):
     for conn, load, nn in ((tri, tri_load, 3), (quad, quad_load, 4)):
         if conn is None or len(conn) == 0:
             continue
         conn = np.asarray(conn).reshape(-1, nn)
         load = np.zeros((len(conn), 4)) if load is None else np.asarray(load, dtype=np.float64).reshape(len(conn), 4)
-        yield conn, load.astype(LD), nn
+        yield conn, load.astype(work), nn
 
 
-def element_terms(xyz, tri=None, quad=None, tri_load=None, quad_load=None):
-    """per element, triangles then quadrilaterals: (pressure resultant p vecarea (n, 3), traction resultant q A (n, 3)), longdouble"""
-    fp, fq = [np.zeros((0, 3), LD)], [np.zeros((0, 3), LD)]
-    for conn, load, nn in _kinds(tri, quad, tri_load, quad_load):
-        d1, d2 = cross_vectors(xyz, conn)
-        va = np.cross(d1, d2) / LD(2)
+def element_terms(xyz, tri=None, quad=None, tri_load=None, quad_load=None, work=LD):
+    """per element, triangles then quadrilaterals: (pressure resultant p vecarea (n, 3), traction resultant q A (n, 3)), in `work`"""
+    fp, fq = [np.zeros((0, 3), work)], [np.zeros((0, 3), work)]
+    for conn, load, nn in _kinds(tri, quad, tri_load, quad_load, work):
+        d1, d2 = cross_vectors(xyz, conn, work)
+        va = np.cross(d1, d2) / work(2)
         area = np.sqrt((va * va).sum(axis=1))
         fp.append(load[:, :1] * va)
         fq.append(load[:, 1:] * area[:, None])
     return np.concatenate(fp), np.concatenate(fq)
 
 
-def load_vector(xyz, tri=None, quad=None, tri_load=None, quad_load=None, dtype=np.float64):
-    """(S, T): S (n_nodes, 6) the lumped nodal equivalents (summed in longdouble, returned as dtype), T (n_nodes,) the row scale"""
+def element_shares(xyz, conn, load, work=LD):
+    """(n, 3): what every node of each element of conn gets on u, v, w from the load rows (p, qx, qy, qz), in `work`"""
+    conn = np.asarray(conn)
+    nn = conn.shape[1]
+    d1, d2 = cross_vectors(xyz, conn, work)
+    cr = np.cross(d1, d2)
+    area = np.sqrt((cr * cr).sum(axis=1)) / work(2)
+    load = np.asarray(load, dtype=np.float64).reshape(len(conn), 4).astype(work)
+    return load[:, :1] * cr / work(2 * nn) + load[:, 1:] * (area / work(nn))[:, None]
+
+
+def load_vector(xyz, tri=None, quad=None, tri_load=None, quad_load=None, dtype=np.float64, work=LD):
+    """(S, T): S (n_nodes, 6) the lumped nodal equivalents (summed in `work`, returned as dtype), T (n_nodes,) the row scale"""
     n = len(xyz)
-    S = np.zeros((n, 6), LD)
-    T = np.zeros(n, LD)
-    for conn, load, nn in _kinds(tri, quad, tri_load, quad_load):
-        d1, d2 = cross_vectors(xyz, conn)
-        cr = np.cross(d1, d2)
-        area = np.sqrt((cr * cr).sum(axis=1)) / LD(2)
-        share = load[:, :1] * cr / LD(2 * nn) + load[:, 1:] * (area / LD(nn))[:, None]
-        scale = np.abs(load).sum(axis=1) * np.sqrt((d1 * d1).sum(axis=1)) * np.sqrt((d2 * d2).sum(axis=1))
+    S = np.zeros((n, 6), work)
+    T = np.zeros(n, work)
+    for conn, load, nn in _kinds(tri, quad, tri_load, quad_load, work):
+        d1, d2 = cross_vectors(xyz, conn, work)
+        share = element_shares(xyz, conn, load, work)
+        scale =np.abs(load).sum(axis=1) * np.sqrt((d1 * d1).sum(axis=1)) * np.sqrt((d2 * d2).sum(axis=1))
         for i in range(nn):
             np.add.at(S[:, :3], conn[:, i], share)
             np.add.at(T, conn[:, i], scale)

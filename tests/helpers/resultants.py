@@ -16,7 +16,8 @@ eps and kappa the element means of the element's own strain operators by the qua
            -(w,xx, w,yy, 2 w,xy), so its negative is the kappa above.  (The stiffness, quadratic in it, does not see the sign; the
            bending patch test of tests/test_resultants_cpu.py fixes it.)
 The QUAD4 operators restate oracle/femshell_oracle.c (quad4_membrane, quad4_dkq_B, quad4_plate) in numpy; the TRI3 ones come from
-the oracle itself (element_tri3 parts, specht_B).
+the oracle itself (element_tri3 parts, specht_B), or, with restated=True, from their restatement here (tri3_frame, specht_B), which
+a call with dtype=np.longdouble evaluates without rounding anything to double on the way.
 
 Beside the values every function returns the absolute-sum scale of each: S = sum_j |(D B)_j| |d_j| for the local components,
 carried through the rotation to global axes with absolute values; for the two von Mises values four times the largest scale of a
@@ -52,18 +53,177 @@ def specht_Y(dphi, area, flags):
     return Y / (4 * area * area)
 
 
-def tri3_operators(xyz, flags=oracle.REF_DEFAULT, dtype=np.float64, quad_parts=False):
+def _two_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _two_prod(a, b):
+    """(p, e) with p = fl(a b) and p + e = a b exactly (Dekker's product on Veltkamp's split, for the type of a and b)"""
+    half = (np.finfo(type(a)).nmant + 2) // 2
+    c = type(a)(2 ** half + 1)
+    ah = c * a - (c * a - a)
+    bh = c * b - (c * b - b)
+    al, bl = a - ah, b - bh
+    p = a * b
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def dot2(a, b):
+    """sum_i a_i b_i with the rounding errors of the products and of the partial sums carried along and added at the end: the
+    result as if formed in twice the precision of the entries' type and rounded once (Ogita, Rump and Oishi's Dot2)"""
+    s = c = type(a[0])(0)
+    for x, y in zip(a, b):
+        p, e = _two_prod(x, y)
+        s, f = _two_sum(s, p)
+        c = c + (e + f)
+    return s + c
+
+
+def cross2(a, b):
+    """a x b, every component by dot2"""
+    return np.array([dot2((a[1], -a[2]), (b[2], b[1])), dot2((a[2], -a[0]), (b[0], b[2])), dot2((a[0], -a[1]), (b[1], b[0]))],
+                    dtype=a.dtype)
+
+
+def tri3_frame(xyz, dtype=np.float64, twofold=False):
+    """SA:306-341, 378-411 as tri3_frame of the oracle states it, every step in `dtype`: ex along the first edge, ez along
+    (B - A) x (C - A), ey = ez x ex; node A is the local origin.  Returns (trafo (3,3), dphi (3,2): rows (12), (31), (23), area).
+    twofold: the same frame from products that keep their digits on slivers and needles -- the sides are differences of doubles,
+    exact in long double; their dot and cross products are formed by dot2; and the local coordinates are written with what the
+    frame makes of them in exact arithmetic: ex . U = |U|, ex . V = U . V / |U|, ey . V = |U x V| / |U|, x23 = U . (B - C) / |U|,
+    where projecting V on a rounded ex, or differencing two projections, cancels up to four digits on the family T4."""
+    X = np.asarray(xyz, dtype=dtype)
+    U, V = X[1] - X[0], X[2] - X[0]
+    W = cross2(U, V) if twofold else np.cross(U, V)
+    lw, lu = (np.sqrt(dot2(W, W)), np.sqrt(dot2(U, U))) if twofold else (np.sqrt(W @ W), np.sqrt(U @ U))
+    if not (lw > 0 and lu > 0):
+        raise ValueError("degenerate TRI3 element")
+    ex, ez = U / lu, W / lw
+    T = np.stack([ex, np.cross(ez, ex), ez])
+    if twofold:  # (y12 = -ey . U is zero in exact arithmetic: its residue stays where the oracle has one, and goes nowhere else)
+        dphi = np.array([[-lu, -(T[1] @ U)], [dot2(U, V) / lu, lw / lu], [dot2(U, X[1] - X[2]) / lu, -lw / lu]], dtype=dtype)
+    else:
+        tU, tV = T @ U, T @ V
+        dphi = np.array([[-tU[0], -tU[1]], [tV[0], tV[1]], [tU[0] - tV[0], tU[1] - tV[1]]], dtype=dtype)
+    return T, dphi, lw / 2
+
+
+def tri3_side_ratios(xyz, dtype=np.float64):
+    """Specht's mu (SA:702-704) from the sides in space: C_a - C_b = (s_a - s_b) . (s_a + s_b) by dot2 instead of the difference
+    of two squared lengths, which on a needle (two sides of length 1, one of 1e-4) cancels eight digits before it is divided by
+    the third"""
+    X = np.asarray(xyz, dtype=dtype)
+    s = [X[0] - X[1], X[2] - X[0], X[1] - X[2]]  # rows (12), (31), (23) of dphi
+    C = [dot2(v, v) for v in s]
+    return [dot2(s[a] - s[b], s[a] + s[b]) / C[c] for a, b, c in ((0, 1, 2), (2, 0, 1), (1, 2, 0))]
+
+
+def _p_mul(x, y):
+    r = np.zeros_like(x)
+    for i in range(5):
+        for j in range(5 - i):
+            if x[i, j] != 0:
+                for k in range(5 - i - j):
+                    for m in range(5 - i - j - k):
+                        r[i + k, j + m] += x[i, j] * y[k, m]
+    return r
+
+
+def _ipow(x, k):
+    """x^k for a small integer k >= 0 by repeated multiplication (the same bits wherever the type's multiplication is IEEE)"""
+    r = x.dtype.type(1)
+    for _ in range(k):
+        r = r * x
+    return r
+
+
+def _p_curv(p, L1, L2):
+    """(d2/dL1^2, d2/dL2^2, 2 d2/dL1 dL2) of the polynomial sum p[i, j] L1^i L2^j at (L1, L2)"""
+    d11 = d22 = d12 = p.dtype.type(0)
+    for i in range(5):
+        for j in range(5 - i):
+            c = p[i, j]
+            if c == 0:
+                continue
+            if i >= 2:
+                d11 += c * (i * (i - 1)) * _ipow(L1, i - 2) * _ipow(L2, j)
+            if j >= 2:
+                d22 += c * (j * (j - 1)) * _ipow(L1, i) * _ipow(L2, j - 2)
+            if i >= 1 and j >= 1:
+                d12 += c * (i * j) * _ipow(L1, i - 1) * _ipow(L2, j - 1)
+    return np.array([d11, d22, 2 * d12], dtype=p.dtype)
+
+
+def specht_B(C, L1, L2, dphi, dtype=np.float64, mu=None):
+    """Specht's B~ (3,9) at the area coordinates (L1, L2), columns (w, tx, ty) per node: fso_tri3_specht_B of the oracle restated
+    in `dtype` -- the functions chi_1..chi_9 as polynomials in (L1, L2) for the side ratios mu, the shape functions as their
+    linear combinations, the rows their second derivatives.  C (3,): squared side lengths, dphi (3,2) as tri3_frame gives it;
+    mu: the side ratios, where the caller has them more accurately than C gives them (tri3_side_ratios)."""
+    C, dphi, L1, L2 = np.asarray(C, dtype=dtype), np.asarray(dphi, dtype=dtype), dtype(L1), dtype(L2)
+    if mu is None:
+        mu = [(C[0] - C[1]) / C[2], (C[2] - C[0]) / C[1], (C[1] - C[2]) / C[0]]
+
+    def lin(c0, c1, c2):
+        p = np.zeros((5, 5), dtype=dtype)
+        p[0, 0], p[1, 0], p[0, 1] = c0, c1, c2
+        return p
+
+    L = [lin(0, 1, 0), lin(0, 0, 1), lin(1, -1, -1)]
+    chi = list(L) + [_p_mul(L[0], L[1]), _p_mul(L[1], L[2]), _p_mul(L[2], L[0])]
+    L123 = _p_mul(chi[3], L[2])
+    for i in range(3):
+        j, k = (i + 1) % 3, (i + 2) % 3
+        m = mu[k]  # chi7 uses mu3, chi8 mu1, chi9 mu2
+        lead = _p_mul(L[j], _p_mul(L[i], L[i]))
+        a = (3 * (1 - m)) * L[i] + (-(1 + 3 * m)) * L[j]
+        chi.append(lead + dtype(0.5) * _p_mul(L123, a + (1 + 3 * m) * L[k]))
+    cc = [_p_curv(p, L1, L2) for p in chi]
+    row_ki, row_ji = (1, 0, 2), (0, 2, 1)
+    B = np.zeros((3, 9), dtype=dtype)
+    for i in range(3):
+        k = (i + 2) % 3
+        xki, yki = dphi[row_ki[i]]
+        xji, yji = -dphi[row_ji[i]]
+        d = cc[6 + k] - cc[3 + k]
+        e = cc[6 + i] - cc[6 + k]
+        B[:, 3 * i + 0] = cc[i] - cc[3 + i] + cc[3 + k] + 2 * e
+        B[:, 3 * i + 1] = -yki * d + yji * cc[6 + i]
+        B[:, 3 * i + 2] = xki * d - xji * cc[6 + i]
+    return B
+
+
+def tri3_operators(xyz, flags=oracle.REF_DEFAULT, dtype=np.float64, quad_parts=False, restated=False):
     """Frame and strain operators of one triangle.  Returns dict: trafo (3,3); Bm [(3,6)] and wm [area] (one point);
     Bp [three (3,9)] and wp [area / 3 each]: the Gauss-point operators and weights of the stiffness, node-major columns
-    (u, v) and (w, tx, ty).  quad_parts: frame, side vectors and area from the quad-precision build of the oracle."""
-    probe = oracle.material(0.3, 1.0, 1.0, flags)
-    if quad_parts:
-        from tests.helpers import oracle_quad
-        p = oracle_quad.element_tri3(xyz, probe)[1]
+    (u, v) and (w, tx, ty).  quad_parts: frame, side vectors and area from the quad-precision build of the oracle.
+    restated: nothing from the oracle -- frame, side vectors, area (tri3_frame), B~ (specht_B) and the Gauss points computed
+    here in `dtype` from the double coordinates, no intermediate rounded to double.  restated="twofold": the same, with the
+    frame and the side ratios from products that carry their rounding errors (tri3_frame twofold, tri3_side_ratios): with
+    dtype=np.longdouble the extended-precision truth of tests/helpers/derived_truth.py, within an ulp of double of binary128
+    on slivers too."""
+    if restated:
+        twofold = restated == "twofold"
+        T, dphi, area = tri3_frame(xyz, dtype, twofold)
+        C = (dphi * dphi).sum(axis=1)
+        mu = tri3_side_ratios(xyz, dtype) if twofold else None
+        sixth, two_thirds = dtype(1) / dtype(6), dtype(2) / dtype(3)
+        gauss = ((sixth, sixth), (two_thirds, sixth), (sixth, two_thirds))
+        B_of = lambda L1, L2: specht_B(C, L1, L2, dphi, dtype, mu)  # noqa: E731
     else:
-        p = oracle.element_tri3(xyz, probe, want_parts=True)[1]
-    dphi = p["dphi"].astype(dtype)
-    area = dtype(p["area"])
+        probe = oracle.material(0.3, 1.0, 1.0, flags)
+        if quad_parts:
+            from tests.helpers import oracle_quad
+            p = oracle_quad.element_tri3(xyz, probe)[1]
+        else:
+            p = oracle.element_tri3(xyz, probe, want_parts=True)[1]
+        dphi = p["dphi"].astype(dtype)
+        area = dtype(p["area"])
+        T = p["trafo"].astype(dtype)
+        C = (p["dphi"] ** 2).sum(axis=1)
+        gauss = GAUSS_TRI
+        B_of = lambda L1, L2: oracle.specht_B(C, L1, L2, p["dphi"]).astype(dtype)  # noqa: E731
     (x12, y12), (x31, y31), (x23, y23) = dphi
     s = 1 / (2 * area)
     Bm = np.zeros((3, 6), dtype=dtype)
@@ -71,17 +231,21 @@ def tri3_operators(xyz, flags=oracle.REF_DEFAULT, dtype=np.float64, quad_parts=F
     Bm[1, 1::2] = [-x23 * s, -x31 * s, -x12 * s]
     Bm[2, 0::2] = Bm[1, 1::2]
     Bm[2, 1::2] = Bm[0, 0::2]
-    C = (p["dphi"] ** 2).sum(axis=1)
     Y = specht_Y(dphi, area, flags)
-    Bp = [Y @ oracle.specht_B(C, L1, L2, p["dphi"]).astype(dtype) for L1, L2 in GAUSS_TRI]
-    return {"trafo": p["trafo"].astype(dtype), "Bm": [Bm], "wm": [area], "Bp": Bp, "wp": [area / 3] * 3}
+    Bp = [Y @ B_of(L1, L2) for L1, L2 in gauss]
+    return {"trafo": T, "Bm": [Bm], "wm": [area], "Bp": Bp, "wp": [area / 3] * 3}
 
 
 # ------------------------------------------------------------------ QUAD4
 
-def quad4_frame(xyz, dtype=np.float64):
-    """SA:342-375: frame from the mid-side points; local coordinates trafo @ X without translation.  Returns (trafo, loc (3,4))."""
+def quad4_frame(xyz, dtype=np.float64, relative=False):
+    """SA:342-375: frame from the mid-side points; local coordinates trafo @ X without translation.  Returns (trafo, loc (3,4)).
+    relative: X - X_first in place of X (formed in `dtype`; in long double the difference of two doubles of similar size is
+    exact).  Frame and operators use coordinate differences alone, so in exact arithmetic nothing changes; in floating point
+    the projections of coordinates at a distance D from the origin no longer cancel D / size digits when they are differenced."""
     X = np.asarray(xyz, dtype=dtype)
+    if relative:
+        X = X - X[0]
     mid = np.array([X[s] + 0.5 * (X[(s + 1) % 4] - X[s]) for s in range(4)])
     ex = mid[1] - mid[3]
     vr = mid[2] - mid[0]
@@ -118,11 +282,11 @@ def _dkq_B(H, xi, eta, Jinv, dtype):
                      Jinv[0] * Hy[0] + Jinv[1] * Hy[1] + Jinv[2] * Hx[0] + Jinv[3] * Hx[1]])
 
 
-def quad4_operators(xyz, dtype=np.float64):
+def quad4_operators(xyz, dtype=np.float64, relative=False):
     """Frame and strain operators of one quadrilateral at the 2 x 2 Gauss points (the order of the oracle's loops).  Returns dict:
     trafo; Bm [four (3,8)], Bp [four (3,12)], wm = wp = [det J at the point].  Bp is MINUS the DKQ operator of the stiffness: the
-    curvature (w,xx, w,yy, 2 w,xy), see the module's head."""
-    T, loc = quad4_frame(xyz, dtype)
+    curvature (w,xx, w,yy, 2 w,xy), see the module's head.  relative: as quad4_frame has it."""
+    T, loc = quad4_frame(xyz, dtype, relative)
     x, y = loc[0], loc[1]
     dphi = np.array([[x[s] - x[(s + 1) % 4], y[s] - y[(s + 1) % 4]] for s in range(4)])
     H = [[None] * 4 for _ in range(5)]
@@ -170,13 +334,15 @@ def von_mises(s):
     return np.sqrt(s[0] * s[0] + s[1] * s[1] - s[0] * s[1] + 3 * s[2] * s[2])
 
 
-def element_resultants(xyz, u, nu, E, t, flags=oracle.REF_DEFAULT, dtype=np.float64, quad_parts=False, with_local=False, uniform_abs=None):
+def element_resultants(xyz, u, nu, E, t, flags=oracle.REF_DEFAULT, dtype=np.float64, quad_parts=False, with_local=False, uniform_abs=None,
+                       restated=False):
     """xyz (nn, 3), u (nn, 6), nn = 3 or 4.  Returns (out[14], scale[14]) in float64 (and the local N, M with with_local).
     uniform_abs: the scale is formed with |d_j| = uniform_abs for every local nodal value instead: what an error of that size in
-    every entry of u can do to the element's values."""
+    every entry of u can do to the element's values.  restated: as tri3_operators has it; a quadrilateral's operators, restated
+    in `dtype` in any case, are then formed with relative=True."""
     xyz = np.asarray(xyz, dtype=np.float64)
     nn = len(xyz)
-    ops = tri3_operators(xyz, flags, dtype, quad_parts) if nn == 3 else quad4_operators(xyz, dtype)
+    ops = tri3_operators(xyz, flags, dtype, quad_parts, restated) if nn == 3 else quad4_operators(xyz, dtype, relative=bool(restated))
     T = ops["trafo"]
     u = np.asarray(u, dtype=dtype).reshape(nn, 6)
     ul, rl = u[:, :3] @ T.T, u[:, 3:] @ T.T
@@ -200,7 +366,8 @@ def element_resultants(xyz, u, nu, E, t, flags=oracle.REF_DEFAULT, dtype=np.floa
     return out.astype(np.float64), scale.astype(np.float64)
 
 
-def mesh_resultants(xyz, tri, quad, u, nu, E, t, sec=None, flags=oracle.REF_DEFAULT, dtype=np.float64, quad_parts=False, uniform_abs=None):
+def mesh_resultants(xyz, tri, quad, u, nu, E, t, sec=None, flags=oracle.REF_DEFAULT, dtype=np.float64, quad_parts=False, uniform_abs=None,
+                    restated=False):
     """(out, scale), each (n_tri + n_quad, 14): triangles in their order, then quadrilaterals.  sec = (sections (n, 3) of
     (nu, E, t), tri_section, quad_section) gives every element its own material."""
     xyz = np.asarray(xyz, dtype=np.float64)
@@ -211,7 +378,8 @@ def mesh_resultants(xyz, tri, quad, u, nu, E, t, sec=None, flags=oracle.REF_DEFA
             continue
         for e, c in enumerate(np.asarray(conn).reshape(-1, 3 if which == 1 else 4)):
             m = (nu, E, t) if sec is None else tuple(np.asarray(sec[0], dtype=np.float64).reshape(-1, 3)[sec[which][e]])
-            o, s = element_resultants(xyz[c], u[c], *m, flags=flags, dtype=dtype, quad_parts=quad_parts, uniform_abs=uniform_abs)
+            o, s = element_resultants(xyz[c], u[c], *m, flags=flags, dtype=dtype, quad_parts=quad_parts, uniform_abs=uniform_abs,
+                                      restated=restated)
             out.append(o)
             scale.append(s)
     return np.array(out).reshape(-1, 14), np.array(scale).reshape(-1, 14)
