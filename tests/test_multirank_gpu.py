@@ -108,6 +108,40 @@ def test_row_partitioned_assembly_and_solve_against_the_oracle(world, kind, tmp_
     assert err < 1e-8, err  # solver term ~1e-13 + kappa x (1e-16 rounding differences of the two assemblies)
 
 
+def test_true_rel_residual_of_two_ranks_is_the_exact_residual_of_the_returned_iterate(tmp_path, monkeypatch):
+    """femshell_residual refuses row-partitioned contexts, so the double-double residual over ghost columns (k_residual_dd_sym
+    behind halo_exchange in a refinement pass) is seen through the solve alone: the multigrid solve of the worker ends on a
+    refinement pass (refine_passes = 1, the default), and true_rel_residual is then the all-reduced double-double norm of the
+    residual of the iterate every rank returns.  Held to the exact residual (tests/helpers/residual_truth.py) of that iterate
+    on the ranks' own rows of K and F put together, to the tolerance of tests/test_gpu_residual_truth.py: two FP64 sums of N
+    non-negative terms, a quotient and a root on either side."""
+    from tests.helpers import residual_truth as rt
+
+    monkeypatch.setenv("FEMSHELL_TEST_EXPORT", "1")
+    ranks = sorted(run_ranks(2, "panel", tmp_path, pc="amg"), key=lambda q: int(q["begin"]))
+    rowptr, cols, vals, F = [np.zeros(1, np.int64)], [], [], []
+    for r in ranks:
+        b, e = int(r["begin"]), int(r["end"])
+        assert b == len(np.concatenate(rowptr)) - 1 and int(r["converged"]) == 1
+        rp = np.asarray(r["k_rowptr"], dtype=np.int64)
+        nb = int(rp[-1] - rp[0])
+        rowptr.append(rp[1:] - rp[0] + sum(len(c) for c in cols))
+        cols.append(np.asarray(r["k_cols"][:nb], dtype=np.int64))
+        vals.append(np.asarray(r["k_vals"][:nb]))
+        F.append(np.asarray(r["k_F"]))
+        np.testing.assert_array_equal(r["u"], ranks[0]["u"])
+        assert float(r["true_res"]) == float(ranks[0]["true_res"])
+    K, F, u = (np.concatenate(rowptr), np.concatenate(cols), np.concatenate(vals)), np.concatenate(F), ranks[0]["u"].ravel()
+    assert len(K[0]) - 1 == len(u) // 6 == int(ranks[-1]["end"]) and len(F) == len(u)
+    got = float(ranks[0]["true_res"])
+    assert got > 0.0  # (-1: no refinement pass ended the solve)
+    want = np.linalg.norm(rt.exact(K, F, u)) / np.linalg.norm(F)
+    rel = abs(got - want) / want
+    print("two ranks: true_rel_residual %.17e, exact %.17e, relative difference %.2e (allowed %.2e)"
+          % (got, want, rel, rt.norm_tolerance(len(F))))
+    assert rel <= rt.norm_tolerance(len(F))
+
+
 @pytest.mark.parametrize("world,order", [(2, "morton"), (3, "rcm")])
 def test_renumbered_row_partition_of_a_randomly_numbered_mesh_against_the_oracle(world, order, tmp_path, monkeypatch):
     """FEMSHELL_REORDER on a row-partitioned context (doc/implementation.tex:103-124: libMesh partitions for locality whatever the
