@@ -39,7 +39,7 @@ SYMBOLS = [
     "femshell_set_prescribed", "femshell_reactions", "femshell_element_product", "femshell_element_resultants",
     "femshell_set_element_loads", "femshell_element_load_vector",
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
-    "femshell_pool_stats",
+    "femshell_pool_stats", "femshell_amg_device_dense_inverse", "femshell_amg_dense_apply",
 ]
 
 
@@ -215,6 +215,8 @@ def load_library():
     L.femshell_buckling_defaults.argtypes = [C.POINTER(BucklingOptions)]
     L.femshell_buckling.argtypes = [vp, C.POINTER(BucklingOptions), dp, dp, dp, dp, C.POINTER(BucklingInfo)]
     L.femshell_pool_stats.argtypes = [dp]
+    L.femshell_amg_device_dense_inverse.argtypes = [vp, C.c_int32, ip, ip, dp, C.c_int32, dp, dp]
+    L.femshell_amg_dense_apply.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, dp, dp]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -663,6 +665,31 @@ class FemShell:
         return {"n": int(out[0]), "ms": out[1], "mfma_flops_issued": out[2], "useful_flops": out[3], "dropped_directions": int(out[4]),
                 "bytes": out[5]}
 
+    def amg_device_dense_inverse(self, rowptr, colidx, vals, single_precision=False):
+        """The device dense inverse (csrc/amg_dense.hip) of a caller's block CSR matrix, for tests: (inverse as doubles, stats as
+        amg_dense_stats gives them).  The context's own hierarchy is not touched."""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        colidx = np.ascontiguousarray(colidx, dtype=np.int32)
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        n = 6 * (len(rowptr) - 1)
+        inv, out = np.zeros((n, n)), np.zeros(6)
+        _check(self._L.femshell_amg_device_dense_inverse(self._h, len(rowptr) - 1, _i(rowptr), _i(colidx), _d(vals),
+                                                         1 if single_precision else 0, _d(inv), _d(out)))
+        return inv, {"n": int(out[0]), "ms": out[1], "mfma_flops_issued": out[2], "useful_flops": out[3],
+                     "dropped_directions": int(out[4]), "bytes": out[5]}
+
+    def amg_dense_apply(self, inv, b, n_pad6, as_float=False, y_prefill=None):
+        """One launch of k_dense_gemv_big on a caller's n x n inverse, for tests: y of n_pad6 + 8 doubles (prefilled by the
+        caller, NaN by default) as the device left it."""
+        inv = np.ascontiguousarray(inv, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        n = inv.shape[0]
+        assert inv.shape == (n, n) and b.shape == (n,)
+        y = np.full(n_pad6 + 8, np.nan) if y_prefill is None else np.array(y_prefill, dtype=np.float64)
+        assert y.shape == (n_pad6 + 8,)
+        _check(self._L.femshell_amg_dense_apply(self._h, n, int(n_pad6), _d(inv), 1 if as_float else 0, _d(b), _d(y)))
+        return y
+
     def amg_patch_info(self):
         """The patch smoother of level 0 (csrc/amg_patch.hpp): rigid edges, clusters, nodes in them; all zero without rigid edges."""
         out = np.zeros(6)
@@ -883,6 +910,20 @@ def amg_host_dense_inverse(rowptr, colidx, vals):
     inv = np.zeros((n, n))
     _check(L.femshell_amg_host_dense_inverse(len(rowptr) - 1, _i(rowptr), _i(colidx), _d(vals), _d(inv)))
     return inv
+
+
+def amg_host_dense_tile_map(nt):
+    """Super-block lists of the device dense inverse's trailing update for nt tiles per side: int32 array [8, per_xcd] of
+    (I << 16) | J, -1 = none."""
+    L = load_library()
+    L.femshell_amg_host_dense_tile_map.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.c_int32]
+    L.femshell_amg_host_dense_tile_map.restype = C.c_int32
+    per = L.femshell_amg_host_dense_tile_map(int(nt), None, 0)
+    if per < 0:
+        raise ValueError("femshell_amg_host_dense_tile_map: invalid nt")
+    out = np.full((8, per), -1, dtype=np.int32)
+    L.femshell_amg_host_dense_tile_map(int(nt), _i(out), out.size)
+    return out
 
 
 def amg_host_pack(rowptr, colidx, vals, diag_first):

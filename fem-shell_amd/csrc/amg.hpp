@@ -55,6 +55,33 @@ struct Bsr {
     int64_t nnzb() const { return (int64_t)col.size(); }
 };
 
+// false: the pattern is not what every routine behind the inspection entry points assumes -- row pointers ascending from 0, the
+// columns of a row strictly ascending and inside [0, n_cols) (merge intersections and binary searches walk them: graph_for_aggregation)
+inline bool bsr_pattern_ok(int32_t n, const int32_t *rowptr, const int32_t *colidx, int32_t n_cols)
+{
+    if (rowptr[0] != 0) return false;
+    for (int32_t i = 0; i < n; i++) {
+        if (rowptr[i + 1] < rowptr[i]) return false;
+        for (int32_t q = rowptr[i]; q < rowptr[i + 1]; q++)
+            if (colidx[q] < 0 || (n_cols != INT32_MAX && colidx[q] >= n_cols) || (q > rowptr[i] && colidx[q] <= colidx[q - 1])) return false;
+    }
+    return true;
+}
+// a caller's block CSR arrays as a Bsr (n_cols < 0: square); false on a pattern bsr_pattern_ok rejects
+inline bool bsr_from_block_csr(int32_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, Bsr *A, int32_t n_cols = -1)
+{
+    if (!bsr_pattern_ok(n, rowptr, colidx, n_cols < 0 ? n : n_cols)) return false;
+    A->nr = A->nc = n;
+    A->ptr.assign(rowptr, rowptr + n + 1);
+    A->col.assign(colidx, colidx + rowptr[n]);
+    A->val.assign(vals, vals + 36ll * rowptr[n]);
+    return true;
+}
+
+// Super-blocks (8 x 8 tiles of 64) of the dense inverse's trailing update, dealt out to the eight XCDs by weight and listed per
+// XCD in row-major order: flat[x * per_xcd + k] = (I << 16) | J, -1 = none (amg_dense.hip DenseTileMap reads it).  Returns per_xcd.
+int dense_tile_map_lists(int nt, std::vector<int32_t> *flat);
+
 // runs f(begin, end) over [0,n) split into contiguous chunks on the host's hardware threads
 void parallel_chunks(int64_t n, const std::function<void(int64_t, int64_t)> &f, int64_t min_chunk = 256);
 int host_threads();

@@ -1001,35 +1001,12 @@ int dense_inverse_once(femshell_ctx *c, const Bsr &A, bool single_precision, Dev
     DevBuf<int32_t> d_sb_list;
     DenseTileMap tmap;
     {
-        const int nsbr = (nt + kSb - 1) / kSb;
-        struct Sb { int I, J, weight; };
-        std::vector<Sb> sbs;
-        for (int I = 0; I < nsbr; I++)
-            for (int J = 0; J <= I; J++) {
-                int w = 0;
-                for (int a = 0; a < kSb; a++)
-                    for (int b = 0; b < kSb; b++) w += (kSb * I + a < nt && kSb * J + b <= kSb * I + a) ? 1 : 0;
-                sbs.push_back({I, J, w});
-            }
-        std::stable_sort(sbs.begin(), sbs.end(), [](const Sb &x, const Sb &y) { return x.weight > y.weight; });
-        std::vector<std::vector<Sb>> lists(8);
-        int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (const Sb &b : sbs) {
-            const int x = (int)(std::min_element(load, load + 8) - load);
-            lists[(size_t)x].push_back(b);
-            load[x] += b.weight;
-        }
-        size_t longest = 1;
-        for (auto &l : lists) {
-            std::sort(l.begin(), l.end(), [](const Sb &x, const Sb &y) { return x.I != y.I ? x.I < y.I : x.J < y.J; });
-            longest = std::max(longest, l.size());
-        }
-        std::vector<int32_t> flat(8 * longest, -1);
-        for (int x = 0; x < 8; x++)
-            for (size_t k = 0; k < lists[(size_t)x].size(); k++) flat[(size_t)x * longest + k] = (lists[(size_t)x][k].I << 16) | lists[(size_t)x][k].J;
+        // (the lists are host code of their own, amg_setup.cpp: the tests hold them to "every lower tile exactly once" without a GPU)
+        std::vector<int32_t> flat;
+        const int longest = dense_tile_map_lists(nt, &flat);
         FS_HIP(d_sb_list.upload(flat, st));
         tmap.list = d_sb_list.p;
-        tmap.per_xcd = (int)longest;
+        tmap.per_xcd = longest;
         tmap.nt = nt;
         tmap.linear = knob_flag("FEMSHELL_AMG_DENSE_XCD_MAP", true) ? 0 : 1;
     }

@@ -994,6 +994,39 @@ bool dense_inverse(const Bsr &A, std::vector<double> *invout)
     return true;
 }
 
+int dense_tile_map_lists(int nt, std::vector<int32_t> *flat_out)
+{
+    constexpr int kSb = 8; // tiles per side of a super-block (amg_dense.hip)
+    const int nsbr = (nt + kSb - 1) / kSb;
+    struct Sb { int I, J, weight; };
+    std::vector<Sb> sbs;
+    for (int I = 0; I < nsbr; I++)
+        for (int J = 0; J <= I; J++) {
+            int w = 0;
+            for (int a = 0; a < kSb; a++)
+                for (int b = 0; b < kSb; b++) w += (kSb * I + a < nt && kSb * J + b <= kSb * I + a) ? 1 : 0;
+            sbs.push_back({I, J, w});
+        }
+    std::stable_sort(sbs.begin(), sbs.end(), [](const Sb &x, const Sb &y) { return x.weight > y.weight; });
+    std::vector<std::vector<Sb>> lists(8);
+    int load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (const Sb &b : sbs) {
+        const int x = (int)(std::min_element(load, load + 8) - load);
+        lists[(size_t)x].push_back(b);
+        load[x] += b.weight;
+    }
+    size_t longest = 1;
+    for (auto &l : lists) {
+        std::sort(l.begin(), l.end(), [](const Sb &x, const Sb &y) { return x.I != y.I ? x.I < y.I : x.J < y.J; });
+        longest = std::max(longest, l.size());
+    }
+    std::vector<int32_t> &flat = *flat_out;
+    flat.assign(8 * longest, -1);
+    for (int x = 0; x < 8; x++)
+        for (size_t k = 0; k < lists[(size_t)x].size(); k++) flat[(size_t)x * longest + k] = (lists[(size_t)x][k].I << 16) | lists[(size_t)x][k].J;
+    return (int)longest;
+}
+
 void pack_sliced_ell(const Bsr &A, bool diag_first, SlicedEll *out)
 {
     SlicedEll &S = *out;

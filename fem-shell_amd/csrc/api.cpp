@@ -1355,6 +1355,76 @@ int femshell_amg_dense_stats(femshell_ctx *c, double out[6])
     return FEMSHELL_OK;
 }
 
+// ---- the dense coarsest inverse and its product by themselves (tests: the shapes the hierarchy never produces on purpose) ----
+int femshell_amg_device_dense_inverse(femshell_ctx *c, int32_t n_nodes, const int32_t *rowptr, const int32_t *colidx, const double *vals,
+                                      int32_t single_precision, double *inv_out, double stats_out[6])
+{
+    if (!c || n_nodes <= 0 || !rowptr || !colidx || !vals || !inv_out)
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_amg_device_dense_inverse: invalid argument");
+    if (n_nodes > 4096) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_amg_device_dense_inverse: too large for a dense inverse");
+    Bsr A;
+    if (!bsr_from_block_csr(n_nodes, rowptr, colidx, vals, &A))
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_amg_device_dense_inverse: rows of the block CSR pattern must hold strictly ascending columns in [0, n_nodes)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    // (buffers of this call alone: the context's hierarchy, its coarse inverse and its stale-state table are not touched)
+    DevBuf<double> inv64;
+    DevBuf<float> inv32;
+    int64_t lda = 0;
+    AmgDenseStats S;
+    rc = amg_dense_inverse_device(c, A, single_precision != 0, &inv64, &inv32, &lda, &S);
+    if (stats_out) {
+        stats_out[0] = (double)S.n;
+        stats_out[1] = S.ms;
+        stats_out[2] = S.mfma_flops;
+        stats_out[3] = S.useful_flops;
+        stats_out[4] = (double)S.dropped;
+        stats_out[5] = S.bytes;
+    }
+    if (rc) return rc;
+    const int64_t n = 6ll * n_nodes;
+    if (single_precision) {
+        std::vector<float> h((size_t)(n * lda));
+        FS_HIP(hipMemcpy(h.data(), inv32.p, h.size() * sizeof(float), hipMemcpyDeviceToHost));
+        for (int64_t r = 0; r < n; r++)
+            for (int64_t q = 0; q < n; q++) inv_out[r * n + q] = (double)h[(size_t)(r * lda + q)];
+    } else {
+        FS_HIP(hipMemcpy2D(inv_out, (size_t)n * 8, inv64.p, (size_t)lda * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost));
+    }
+    return FEMSHELL_OK;
+}
+
+int femshell_amg_dense_apply(femshell_ctx *c, int32_t n, int32_t n_pad6, const double *inv, int32_t as_float, const double *b, double *y)
+{
+    if (!c || n <= 0 || n_pad6 < n || !inv || !b || !y) return set_err(FEMSHELL_ERR_INVALID, "femshell_amg_dense_apply: invalid argument");
+    const int rc = select_device(c);
+    if (rc) return rc;
+    hipStream_t st = c->stream;
+    const int64_t lda = ((int64_t)n + 1) / 2 * 2; // (dense_inverse_once: even, the padding column zero)
+    std::vector<double> h64;
+    std::vector<float> h32;
+    if (as_float) h32.assign((size_t)(n * lda), 0.f);
+    else h64.assign((size_t)(n * lda), 0.0);
+    for (int64_t r = 0; r < n; r++)
+        for (int64_t q = 0; q < n; q++) {
+            if (as_float) h32[(size_t)(r * lda + q)] = (float)inv[r * n + q];
+            else h64[(size_t)(r * lda + q)] = inv[r * n + q];
+        }
+    std::vector<double> hb((size_t)std::max<int64_t>(n_pad6, lda), 0.0), hy(y, y + (size_t)n_pad6 + 8);
+    std::copy(b, b + n, hb.begin());
+    DevBuf<double> d64, db, dy;
+    DevBuf<float> d32;
+    if (as_float) FS_HIP(d32.upload(h32, st));
+    else FS_HIP(d64.upload(h64, st));
+    FS_HIP(db.upload(hb, st));
+    FS_HIP(dy.upload(hy, st));
+    launch_dense_gemv_big(d64.p, d32.p, lda, db.p, dy.p, n, n_pad6, nullptr, st);
+    FS_HIP(hipGetLastError());
+    FS_HIP(hipMemcpyAsync(y, dy.p, ((size_t)n_pad6 + 8) * sizeof(double), hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    return FEMSHELL_OK;
+}
+
 int64_t femshell_amg_export(femshell_ctx *c, int32_t level, int32_t which, void *out)
 {
     if (!c || level < 0 || level >= femshell_amg_levels(c)) return -1;

@@ -143,26 +143,11 @@ struct femshell_amg_coarsening {
 };
 
 namespace {
-// false: the pattern is not what every routine behind these entry points assumes -- row pointers ascending from 0, the columns
-// of a row strictly ascending and inside [0, n_cols) (merge intersections and binary searches walk them: graph_for_aggregation)
-bool pattern_ok(int32_t n, const int32_t *rowptr, const int32_t *colidx, int32_t n_cols)
-{
-    if (rowptr[0] != 0) return false;
-    for (int32_t i = 0; i < n; i++) {
-        if (rowptr[i + 1] < rowptr[i]) return false;
-        for (int32_t q = rowptr[i]; q < rowptr[i + 1]; q++)
-            if (colidx[q] < 0 || (n_cols != INT32_MAX && colidx[q] >= n_cols) || (q > rowptr[i] && colidx[q] <= colidx[q - 1])) return false;
-    }
-    return true;
-}
+// (the validation every entry point below shares with femshell_amg_device_dense_inverse: amg.hpp)
+bool pattern_ok(int32_t n, const int32_t *rowptr, const int32_t *colidx, int32_t n_cols) { return bsr_pattern_ok(n, rowptr, colidx, n_cols); }
 bool to_bsr(int32_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, Bsr *A, int32_t n_cols = -1)
 {
-    if (!pattern_ok(n, rowptr, colidx, n_cols < 0 ? n : n_cols)) return false;
-    A->nr = A->nc = n;
-    A->ptr.assign(rowptr, rowptr + n + 1);
-    A->col.assign(colidx, colidx + rowptr[n]);
-    A->val.assign(vals, vals + 36ll * rowptr[n]);
-    return true;
+    return bsr_from_block_csr(n, rowptr, colidx, vals, A, n_cols);
 }
 } // namespace
 
@@ -318,6 +303,15 @@ int femshell_amg_host_dense_inverse(int32_t n_nodes, const int32_t *rowptr, cons
     if (!dense_inverse(A, &inv)) return set_err(FEMSHELL_ERR_BREAKDOWN, "femshell_amg_host_dense_inverse: matrix is not positive definite");
     std::memcpy(inv_out, inv.data(), inv.size() * sizeof(double));
     return FEMSHELL_OK;
+}
+
+int32_t femshell_amg_host_dense_tile_map(int32_t nt, int32_t *list_out, int32_t cap)
+{
+    if (nt <= 0 || nt > 512) return -1; // (the device inverts at most 4096 nodes: 384 tiles per side)
+    std::vector<int32_t> flat;
+    const int per_xcd = dense_tile_map_lists(nt, &flat);
+    for (size_t k = 0; list_out != nullptr && k < flat.size() && (int64_t)k < cap; k++) list_out[k] = flat[k];
+    return per_xcd;
 }
 
 int64_t femshell_amg_host_pack(int32_t n_rows, const int32_t *rowptr, const int32_t *colidx, const double *vals,

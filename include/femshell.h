@@ -320,6 +320,19 @@ int femshell_amg_symbolic_info(femshell_ctx *ctx, int32_t out[3]);
  * out[2] = flops issued on the matrix cores, out[3] = n^3 (the flops of a symmetric inversion), out[4] = dropped
  * (semi-definite) directions, out[5] = bytes of the lower triangle read and written over all steps */
 int femshell_amg_dense_stats(femshell_ctx *ctx, double out[6]);
+/* For tests: the device dense inverse (csrc/amg_dense.hip) of a caller's SPD block CSR matrix (6 x 6 blocks, row-major; the
+ * arguments and their validation are those of femshell_amg_host_dense_inverse, femshell_plan.h), on the context's streams and
+ * with the setup's run-again-without-look-ahead path.  inv_out: (6 n_nodes)^2 doubles (single_precision != 0: the stored floats,
+ * widened); stats_out (may be NULL): the six numbers of femshell_amg_dense_stats for this call.  The context's own hierarchy and
+ * state are not touched.  FEMSHELL_ERR_BREAKDOWN where the multigrid setup would return it. */
+int femshell_amg_device_dense_inverse(femshell_ctx *ctx, int32_t n_nodes, const int32_t *rowptr, const int32_t *colidx,
+                                      const double *vals, int32_t single_precision, double *inv_out, double stats_out[6]);
+/* For tests: one product y = inv b by the kernel every multigrid cycle applies the dense inverse with (k_dense_gemv_big), no gate.
+ * inv: n x n doubles, stored on the device with the production leading dimension (as_float != 0: rounded to float first);
+ * b: n doubles (uploaded zero-padded); y: n_pad6 + 8 doubles, uploaded as they are and copied back after the launch -- the
+ * kernel writes rows [0, n_pad6), zeros in [n, n_pad6). */
+int femshell_amg_dense_apply(femshell_ctx *ctx, int32_t n, int32_t n_pad6, const double *inv, int32_t as_float, const double *b,
+                             double *y);
 /* The device-memory pool of this process as it stands (csrc/dev_pool.hpp; every buffer of every context comes out of it, so the
  * call takes no context and also answers after the last one was destroyed): out[0] = bytes the driver has handed out through
  * the pool and not got back, out[1] = bytes in use by buffers, out[2] = bytes kept for reuse (what FEMSHELL_POOL_GB bounds),

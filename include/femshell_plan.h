@@ -119,6 +119,10 @@ int32_t femshell_amg_host_aggregate_glued(int32_t n_nodes, const int32_t *rowptr
 /* dense inverse of a small SPD block matrix (coarsest level): inv_out (6n)^2 doubles */
 int femshell_amg_host_dense_inverse(int32_t n_nodes, const int32_t *rowptr, const int32_t *colidx, const double *vals,
                                     double *inv_out);
+/* the super-block lists of the device dense inverse's trailing update for nt 64-tiles per side (csrc/amg_dense.hip DenseTileMap):
+ * returns per_xcd, the length of each of the eight lists; list_out (8 * per_xcd entries, at most cap are written; may be NULL)
+ * [x * per_xcd + k] = (I << 16) | J of the k-th 8 x 8 super-block of XCD x, -1 = none.  < 0: invalid argument. */
+int32_t femshell_amg_host_dense_tile_map(int32_t nt, int32_t *list_out, int32_t cap);
 /* the sliced block ELL image the device kernels read, for layout tests: returns total slots; arrays may be NULL */
 int64_t femshell_amg_host_pack(int32_t n_rows, const int32_t *rowptr, const int32_t *colidx, const double *vals,
                                int32_t diag_first, int32_t *slice_width, int64_t *slice_base, int32_t *cols, double *ell_vals);

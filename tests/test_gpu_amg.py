@@ -506,6 +506,24 @@ def test_dense_inverse_on_the_matrix_cores_equals_the_host_inverse(monkeypatch, 
             assert len(levels) == 2 and inv.shape == Ac.shape == (6 * lv[-1]["n_nodes"],) * 2
             defect = np.abs(Ac @ inv - np.eye(len(Ac))).max()
             assert defect <= (1e-9 if not f32 else 2e-4), defect
+            # ... and, scaled to the operator, against LAPACK's inverse of the operator the library itself exports (nt = 26: two
+            # super-blocks per XCD; the long-double truth of tests/test_gpu_dense_inverse.py stops at 1026 dofs): the distance of
+            # two double methods is at most the sum of their errors, the device's is held to 4 x the restatement's, and a stored
+            # float is rounded once more
+            from tests.helpers import dense_truth
+
+            ex = fs.amg_export(len(lv) - 1)
+            Ae = _bsr(ex["A_rowptr"], ex["A_cols"], ex["A_vals"], lv[-1]["n_nodes"]).toarray()
+            Ae = np.tril(Ae) + np.tril(Ae, -1).T  # (the device reads the lower triangle)
+            lap = np.linalg.inv(Ae)
+            restated, dropped, failed = dense_truth.restated_inverse(Ae)
+            assert failed is None and dropped == []
+            scale = np.abs(lap).max()
+            allowed = dense_truth.bound(np.abs(restated - lap).max() / scale, len(Ae)) + (2.0 ** -24 if f32 else 0.0)
+            dist = np.abs(inv - lap).max() / scale
+            print("%s f32=%d: |device - lapack| / max|lapack| = %.2e, |restated - lapack| = %.2e, allowed %.2e"
+                  % (path, f32, dist, np.abs(restated - lap).max() / scale, allowed))
+            assert dist <= allowed, (dist, allowed)
         fs.close()
     assert out["device128"][1] == out["device"][1] and np.linalg.norm(out["device128"][0] - out["device"][0]) <= 1e-12 * np.linalg.norm(out["device"][0])
     assert out["host"][2]["n"] == 0 and out["device"][2]["n"] == 6 * out["device"][3]
