@@ -40,6 +40,7 @@ SYMBOLS = [
     "femshell_set_element_loads", "femshell_element_load_vector",
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
     "femshell_pool_stats", "femshell_amg_device_dense_inverse", "femshell_amg_dense_apply",
+    "femshell_amg_device_block_jacobi", "femshell_block_jacobi_export", "femshell_block_jacobi_apply",
 ]
 
 
@@ -217,6 +218,9 @@ def load_library():
     L.femshell_pool_stats.argtypes = [dp]
     L.femshell_amg_device_dense_inverse.argtypes = [vp, C.c_int32, ip, ip, dp, C.c_int32, dp, dp]
     L.femshell_amg_dense_apply.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, dp, dp]
+    L.femshell_amg_device_block_jacobi.argtypes = [vp, C.c_int32, ip, ip, dp, C.c_int32, dp, ip]
+    L.femshell_block_jacobi_export.argtypes = [vp, C.c_int32, C.c_int32, dp]
+    L.femshell_block_jacobi_apply.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -690,6 +694,44 @@ class FemShell:
         _check(self._L.femshell_amg_dense_apply(self._h, n, int(n_pad6), _d(inv), 1 if as_float else 0, _d(b), _d(y)))
         return y
 
+    def amg_device_block_jacobi(self, rowptr, colidx, vals, symmetric_storage=0):
+        """The block-Jacobi setup kernel (k_block_jacobi) on a caller's block CSR matrix packed as a coarse level operator is, for
+        tests: (inverse diagonal blocks [n, 6, 6], status word).  symmetric_storage 0: full; 1: diagonal + upper blocks; 2: the
+        same, read as K's own diagonal slots are (upper triangle only).  The context's own state is not touched."""
+        rowptr = np.ascontiguousarray(rowptr, dtype=np.int32)
+        colidx = np.ascontiguousarray(colidx, dtype=np.int32)
+        vals = np.ascontiguousarray(vals, dtype=np.float64)
+        n = len(rowptr) - 1
+        inv, status = np.zeros((n, 6, 6)), np.zeros(1, dtype=np.int32)
+        _check(self._L.femshell_amg_device_block_jacobi(self._h, n, _i(rowptr), _i(colidx), _d(vals), int(symmetric_storage), _d(inv),
+                                                        _i(status)))
+        return inv, int(status[0])
+
+    def _block_jacobi_nodes(self, level):
+        return self.n_nodes if level <= 0 or level >= self._L.femshell_amg_levels(self._h) else self.amg_levels()[level]["n_nodes"]
+
+    def block_jacobi_export(self, level=0, single_precision=False):
+        """The block-Jacobi inverse the context holds, [n, 6, 6]: level 0 of K (the caller's numbering), level >= 1 of that
+        operator of the multigrid hierarchy; single_precision: the copy the smoothers read, widened."""
+        if self._L.femshell_amg_levels(self._h) == 0 and level > 0:  # (builds what is missing, or refuses)
+            _check(self._L.femshell_block_jacobi_export(self._h, 0, 0, _d(np.zeros((self.n_nodes, 6, 6)))))
+        out = np.zeros((self._block_jacobi_nodes(level), 6, 6))
+        _check(self._L.femshell_block_jacobi_export(self._h, int(level), 1 if single_precision else 0, _d(out)))
+        return out
+
+    def block_jacobi_apply(self, level, path, r):
+        """z = D^-1 r over the padded vector of a level (6 x 32 x ceil(n / 32) doubles as they lie in HBM) by the lane-per-row
+        reader (path 0) or the lane-per-node reader (path 1: the smoothers', from the single-precision copy where there is one)."""
+        r = np.ascontiguousarray(r, dtype=np.float64).reshape(-1)
+        if self._L.femshell_amg_levels(self._h) == 0 and level > 0:
+            _check(self._L.femshell_block_jacobi_export(self._h, 0, 0, _d(np.zeros((self.n_nodes, 6, 6)))))
+        n_pad = (self._block_jacobi_nodes(level) + 31) // 32 * 32
+        if len(r) != 6 * n_pad:
+            raise ValueError("r needs 6 values per node of the padded level: %d" % (6 * n_pad))
+        z = np.zeros_like(r)
+        _check(self._L.femshell_block_jacobi_apply(self._h, int(level), int(path), _d(r), _d(z)))
+        return z
+
     def amg_patch_info(self):
         """The patch smoother of level 0 (csrc/amg_patch.hpp): rigid edges, clusters, nodes in them; all zero without rigid edges."""
         out = np.zeros(6)
@@ -910,6 +952,18 @@ def amg_host_dense_inverse(rowptr, colidx, vals):
     inv = np.zeros((n, n))
     _check(L.femshell_amg_host_dense_inverse(len(rowptr) - 1, _i(rowptr), _i(colidx), _d(vals), _d(inv)))
     return inv
+
+
+def amg_host_block_inverse(blocks):
+    """The host's 6 x 6 block-Jacobi inverse (block_diagonal_inverse) of [n, 6, 6] blocks: (inverses [n, 6, 6], ok [n]: 1 =
+    inverted, 0 = not positive definite and the identity returned)."""
+    L = load_library()
+    L.femshell_amg_host_block_inverse.argtypes = [C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
+    L.femshell_amg_host_block_inverse.restype = C.c_int32
+    blocks = np.ascontiguousarray(blocks, dtype=np.float64).reshape(-1, 6, 6)
+    inv, ok = np.zeros_like(blocks), np.zeros(len(blocks), dtype=np.int32)
+    _check(L.femshell_amg_host_block_inverse(len(blocks), _d(blocks), _d(inv), _i(ok)))
+    return inv, ok
 
 
 def amg_host_dense_tile_map(nt):

@@ -133,8 +133,9 @@ int32_t aggregate_nodes_glued(const Bsr &A, const std::vector<int32_t> &label, s
 void tentative_prolongator(const std::vector<int32_t> &agg, int32_t na, const std::vector<double> &B,
                            std::vector<double> *Q, std::vector<double> *Bc);
 
-// inverse of the 6x6 diagonal blocks (Cholesky; identity for blocks that are not positive definite)
-void block_diagonal_inverse(const Bsr &A, std::vector<double> *Dinv);
+// inverse of the 6x6 diagonal blocks (Cholesky; identity for blocks that are not positive definite, or absent; ok, where asked
+// for, says per node which it was: 1 = inverted)
+void block_diagonal_inverse(const Bsr &A, std::vector<double> *Dinv, std::vector<uint8_t> *ok = nullptr);
 
 void bsr_multiply(const Bsr &A, const Bsr &B, Bsr *C);  // C = A B
 void bsr_transpose(const Bsr &A, Bsr *T);

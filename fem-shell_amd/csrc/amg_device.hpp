@@ -230,6 +230,13 @@ int amg_dense_inverse_device(femshell_ctx *c, const Bsr &A, bool single_precisio
 // y = Ainv b for such an inverse (one of A64 / A32 non-null); rows [n, n_pad6) of y are set to zero
 void launch_dense_gemv_big(const double *A64, const float *A32, int64_t lda, const double *b, double *y, int32_t n, int32_t n_pad6,
                            const CgScalars *gate, hipStream_t st);
+// For tests (amg_solve.cpp; the entry points are in api.cpp): k_block_jacobi on a caller's matrix packed as a coarse level operator
+// is (storage 0 full, 1 diagonal + upper blocks, 2 the same with DeviceMatrix::diag_upper), with a status word of the call;
+// the 21 packed words per node of the inverse a level holds (level 0: K; single_precision: the smoothers' copy); z = D^-1 r over
+// the padded vector of a level by the lane-per-row reader (path 0) or the lane-per-node reader (path 1)
+int amg_block_jacobi_device(femshell_ctx *c, const Bsr &A, int storage, std::vector<double> *minv_out, int32_t *status_out);
+int amg_block_jacobi_words(femshell_ctx *c, int level, bool single_precision, std::vector<double> *words, int32_t *n_nodes, int32_t *n_pad);
+int amg_block_jacobi_apply(femshell_ctx *c, int level, int path, const double *r, double *z);
 // first coarsening step with the numerics on the device (amg_device_setup.cpp)
 // (A: the level operator in HBM, block-Jacobi inverse valid; pat: host copy of its pattern; want_host(coarse nodes): bring
 //  the coarse operator back as a host matrix -- needed when the next step runs on the host or the level is the coarsest)

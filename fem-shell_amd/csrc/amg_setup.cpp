@@ -749,10 +749,11 @@ void tentative_prolongator(const std::vector<int32_t> &agg, int32_t na, const st
     }, 16);
 }
 
-void block_diagonal_inverse(const Bsr &A, std::vector<double> *Dout)
+void block_diagonal_inverse(const Bsr &A, std::vector<double> *Dout, std::vector<uint8_t> *ok_out)
 {
     std::vector<double> &D = *Dout;
     D.assign((size_t)A.nr * 36, 0.0);
+    if (ok_out) ok_out->assign((size_t)A.nr, 0);
     parallel_chunks(A.nr, [&](int64_t r0, int64_t r1) {
         for (int64_t i = r0; i < r1; i++) {
             double *inv = &D[(size_t)i * 36];
@@ -766,6 +767,7 @@ void block_diagonal_inverse(const Bsr &A, std::vector<double> *Dout)
                 std::fill(inv, inv + 36, 0.0);
                 for (int d = 0; d < 6; d++) inv[7 * d] = 1.0;
             }
+            if (ok_out) (*ok_out)[(size_t)i] = ok ? 1 : 0;
         }
     });
 }

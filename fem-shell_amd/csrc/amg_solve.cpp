@@ -387,6 +387,99 @@ void amg_default_options(femshell_pc_options *o)
 
 const DeviceMatrix &amg_level_matrix(const femshell_ctx *c, int l) { return l == 0 ? c->dm : c->amg->levels[l]->A.dm; }
 
+// ---- the block-Jacobi inverse by itself (tests: femshell_amg_device_block_jacobi, api.cpp) -------------------------------------
+// A is packed and uploaded the way amg_finish_hierarchy packs a coarse level operator (storage 0: full, pack_sliced_ell; 1:
+// diagonal + upper blocks, pack_sliced_ell_sym + in-lists; 2: as 1 with DeviceMatrix::diag_upper set, K's own layout, in which
+// k_block_jacobi takes the strict lower triangle of a diagonal block from its mirror image), k_block_jacobi runs on it with a
+// status word of this call, and the 21 packed words per node come back: minv_out[(slice * 21 + word) * 32 + node], n_pad nodes.
+int amg_block_jacobi_device(femshell_ctx *c, const Bsr &A, int storage, std::vector<double> *minv_out, int32_t *status_out)
+{
+    hipStream_t st = c->stream;
+    AmgOperator op;
+    int rc;
+    if (storage != 0) {
+        SlicedEllSym S;
+        pack_sliced_ell_sym(A, &S);
+        rc = upload_operator(op, S, S.n_pad, (A.nnzb() + A.nr) / 2, st);
+        if (!rc) rc = attach_in_lists(op, S, S.slice_base.back(), st);
+    } else {
+        SlicedEll S;
+        pack_sliced_ell(A, true, &S);
+        rc = upload_operator(op, S, S.n_pad, A.nnzb(), st);
+    }
+    if (rc) return rc;
+    DevBuf<double> minv;
+    DevBuf<int32_t> status;
+    FS_HIP(minv.alloc((size_t)op.dm.n_slices * 21 * kSliceNodes));
+    FS_HIP(status.alloc(1));
+    FS_HIP(status.zero(st));
+    op.dm.minv = minv.p;
+    op.dm.status = status.p;
+    op.dm.diag_upper = storage == 2 ? 1 : 0;
+    launch_block_jacobi(op.dm, st);
+    FS_HIP(hipGetLastError());
+    minv_out->resize(minv.n);
+    FS_HIP(hipMemcpyAsync(minv_out->data(), minv.p, minv.n * sizeof(double), hipMemcpyDeviceToHost, st));
+    FS_HIP(hipMemcpyAsync(status_out, status.p, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    return FEMSHELL_OK;
+}
+
+// ---- the inverse a level holds, and its two readers (tests: femshell_block_jacobi_export / _apply, api.cpp) ------------------
+// the level's matrix as the smoothers see it (minv32 set where the level has the copy); levels without a smoother and
+// block-Jacobi contexts: the operator itself
+static const DeviceMatrix &inspected_level_matrix(const femshell_ctx *c, int level)
+{
+    if (c->amg && c->amg->valid && level < (int)c->amg->levels.size() && c->amg->levels[(size_t)level]->smooth_ready)
+        return c->amg->levels[(size_t)level]->smooth_dm;
+    return amg_level_matrix(c, level);
+}
+
+int amg_block_jacobi_words(femshell_ctx *c, int level, bool single_precision, std::vector<double> *words, int32_t *n_nodes, int32_t *n_pad)
+{
+    const DeviceMatrix &m = inspected_level_matrix(c, level);
+    *n_nodes = m.n_own;
+    *n_pad = m.n_pad;
+    const size_t nw = (size_t)m.n_slices * 21 * kSliceNodes;
+    words->assign(nw, 0.0);
+    if (single_precision) {
+        if (m.minv32 == nullptr) return set_err(FEMSHELL_ERR_INVALID, "femshell_block_jacobi_export: the level keeps no single-precision copy of its block-Jacobi inverse");
+        std::vector<float> h(nw);
+        FS_HIP(hipMemcpyAsync(h.data(), m.minv32, nw * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(hipStreamSynchronize(c->stream));
+        for (size_t i = 0; i < nw; i++) (*words)[i] = (double)h[i];
+    } else {
+        if (m.minv == nullptr) return set_err(FEMSHELL_ERR_INVALID, "femshell_block_jacobi_export: the level has no block-Jacobi inverse");
+        FS_HIP(hipMemcpyAsync(words->data(), m.minv, nw * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        FS_HIP(hipStreamSynchronize(c->stream));
+    }
+    return FEMSHELL_OK;
+}
+
+int amg_block_jacobi_apply(femshell_ctx *c, int level, int path, const double *r, double *z)
+{
+    const DeviceMatrix &m = inspected_level_matrix(c, level);
+    if (m.minv == nullptr) return set_err(FEMSHELL_ERR_INVALID, "femshell_block_jacobi_apply: the level has no block-Jacobi inverse");
+    hipStream_t st = c->stream;
+    const size_t n6 = (size_t)m.n_pad * 6;
+    DevBuf<double> dr, dz, dd, part;
+    FS_HIP(dr.alloc(n6));
+    FS_HIP(dz.alloc(n6));
+    FS_HIP(hipMemcpyAsync(dr.p, r, n6 * sizeof(double), hipMemcpyHostToDevice, st));
+    FS_HIP(hipMemsetAsync(dz.p, 0xff, n6 * sizeof(double), st)); // (NaN: every entry of z has to be written by the reader)
+    if (path == 0) {
+        FS_HIP(part.alloc((size_t)slice_grid(m)));
+        launch_minv_apply_norm(m, dr.p, dz.p, part.p, st);
+    } else {
+        FS_HIP(dd.alloc(n6));
+        launch_cheb_start(m, dr.p, dd.p, dz.p, 1.0, false, nullptr, st, 0);
+    }
+    FS_HIP(hipGetLastError());
+    FS_HIP(hipMemcpyAsync(z, dz.p, n6 * sizeof(double), hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    return FEMSHELL_OK;
+}
+
 // Builds the hierarchy for the matrix currently in HBM.  Host: aggregation, prolongators, Galerkin products
 // (amg_setup.cpp); device: lambda_max of every level, block-Jacobi inverses of the coarse operators.
 namespace {

@@ -1425,6 +1425,81 @@ int femshell_amg_dense_apply(femshell_ctx *c, int32_t n, int32_t n_pad6, const d
     return FEMSHELL_OK;
 }
 
+// ---- the 6 x 6 block-Jacobi inverse by itself (tests: the blocks, storages and slice shapes no mesh produces on purpose; the
+// inverse a context holds; its two readers).  No production path runs through these.
+namespace {
+// 21 packed words per node (per slice: word-major, nodes fastest; device_common.hpp minv_word) -> full symmetric 6 x 6 blocks
+void unpack_minv_words(const std::vector<double> &words, int32_t n_nodes, const std::function<int32_t(int32_t)> &node_out, double *out)
+{
+    for (int32_t a = 0; a < n_nodes; a++) {
+        const size_t base = (size_t)(a / kSliceNodes) * 21 * kSliceNodes + (size_t)(a % kSliceNodes);
+        double *B = out + 36ull * (size_t)node_out(a);
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j < 6; j++) {
+                const int lo = std::min(i, j), hi = std::max(i, j);
+                B[6 * i + j] = words[base + (size_t)((lo * (11 - lo)) / 2 + hi) * kSliceNodes];
+            }
+    }
+}
+// what the export and the apply refuse alike, and the state they need: K, its block-Jacobi inverse, the hierarchy of a multigrid context
+int block_jacobi_level_ready(femshell_ctx *c, int32_t level, const char *what)
+{
+    const std::string w(what);
+    if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, w + ": single-rank contexts only");
+    if (!c->have_mesh) return set_err(FEMSHELL_ERR_INVALID, w + ": no mesh set");
+    if (const int prc = finish_pending_assembly(c)) return prc;
+    int rc = select_device(c);
+    if (rc) return rc;
+    const bool amg = c->pc.type == FEMSHELL_PC_AMG;
+    if (level < 0 || (level > 0 && !amg)) return set_err(FEMSHELL_ERR_INVALID, w + ": no such level");
+    rc = ensure(c, kK | kJacobi | (amg ? kHierarchy : 0u));
+    if (rc) return rc;
+    if (level > 0 && level >= femshell_amg_levels(c)) return set_err(FEMSHELL_ERR_INVALID, w + ": no such level");
+    return FEMSHELL_OK;
+}
+} // namespace
+
+int femshell_amg_device_block_jacobi(femshell_ctx *c, int32_t n_nodes, const int32_t *rowptr, const int32_t *colidx, const double *vals,
+                                     int32_t symmetric_storage, double *inv_out, int32_t *status_out)
+{
+    if (!c || n_nodes <= 0 || !rowptr || !colidx || !vals || !inv_out || !status_out || symmetric_storage < 0 || symmetric_storage > 2)
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_amg_device_block_jacobi: invalid argument");
+    Bsr A;
+    if (!bsr_from_block_csr(n_nodes, rowptr, colidx, vals, &A))
+        return set_err(FEMSHELL_ERR_INVALID, "femshell_amg_device_block_jacobi: rows of the block CSR pattern must hold strictly ascending columns in [0, n_nodes)");
+    int rc = select_device(c);
+    if (rc) return rc;
+    // (buffers and a status word of this call alone: the context's matrix, hierarchy and stale-state table are not touched)
+    std::vector<double> words;
+    rc = amg_block_jacobi_device(c, A, symmetric_storage, &words, status_out);
+    if (rc) return rc;
+    unpack_minv_words(words, n_nodes, [](int32_t a) { return a; }, inv_out);
+    return FEMSHELL_OK;
+}
+
+int femshell_block_jacobi_export(femshell_ctx *c, int32_t level, int32_t single_precision, double *out)
+{
+    if (!c || !out) return set_err(FEMSHELL_ERR_INVALID, "femshell_block_jacobi_export: null argument");
+    int rc = block_jacobi_level_ready(c, level, "femshell_block_jacobi_export");
+    if (rc) return rc;
+    std::vector<double> words;
+    int32_t n = 0, n_pad = 0;
+    rc = amg_block_jacobi_words(c, level, single_precision != 0, &words, &n, &n_pad);
+    if (rc) return rc;
+    // level 0: the rows lie in HBM in the library's numbering, the blocks leave in the caller's
+    unpack_minv_words(words, n, [&](int32_t a) { return level == 0 ? caller_node(c, a) : a; }, out);
+    return FEMSHELL_OK;
+}
+
+int femshell_block_jacobi_apply(femshell_ctx *c, int32_t level, int32_t path, const double *r, double *z)
+{
+    if (!c || !r || !z) return set_err(FEMSHELL_ERR_INVALID, "femshell_block_jacobi_apply: null argument");
+    if (path != 0 && path != 1) return set_err(FEMSHELL_ERR_INVALID, "femshell_block_jacobi_apply: path is 0 (lane per row) or 1 (lane per node)");
+    const int rc = block_jacobi_level_ready(c, level, "femshell_block_jacobi_apply");
+    if (rc) return rc;
+    return amg_block_jacobi_apply(c, level, path, r, z);
+}
+
 int64_t femshell_amg_export(femshell_ctx *c, int32_t level, int32_t which, void *out)
 {
     if (!c || level < 0 || level >= femshell_amg_levels(c)) return -1;

@@ -305,6 +305,24 @@ int femshell_amg_host_dense_inverse(int32_t n_nodes, const int32_t *rowptr, cons
     return FEMSHELL_OK;
 }
 
+int femshell_amg_host_block_inverse(int32_t n, const double *blocks, double *inv_out, int32_t *ok_out)
+{
+    if (n <= 0 || !blocks || !inv_out) return set_err(FEMSHELL_ERR_INVALID, "femshell_amg_host_block_inverse: invalid argument");
+    Bsr A; // the blocks as a block-diagonal matrix: what block_diagonal_inverse looks for in every row
+    A.nr = A.nc = n;
+    A.ptr.resize((size_t)n + 1);
+    A.col.resize((size_t)n);
+    for (int32_t i = 0; i <= n; i++) A.ptr[(size_t)i] = i;
+    for (int32_t i = 0; i < n; i++) A.col[(size_t)i] = i;
+    A.val.assign(blocks, blocks + 36ll * n);
+    std::vector<double> inv;
+    std::vector<uint8_t> ok;
+    block_diagonal_inverse(A, &inv, &ok);
+    std::memcpy(inv_out, inv.data(), inv.size() * sizeof(double));
+    for (int32_t i = 0; ok_out != nullptr && i < n; i++) ok_out[i] = ok[(size_t)i];
+    return FEMSHELL_OK;
+}
+
 int32_t femshell_amg_host_dense_tile_map(int32_t nt, int32_t *list_out, int32_t cap)
 {
     if (nt <= 0 || nt > 512) return -1; // (the device inverts at most 4096 nodes: 384 tiles per side)

@@ -333,6 +333,26 @@ int femshell_amg_device_dense_inverse(femshell_ctx *ctx, int32_t n_nodes, const 
  * kernel writes rows [0, n_pad6), zeros in [n, n_pad6). */
 int femshell_amg_dense_apply(femshell_ctx *ctx, int32_t n, int32_t n_pad6, const double *inv, int32_t as_float, const double *b,
                              double *y);
+/* For tests: the block-Jacobi setup kernel (k_block_jacobi) on a caller's block CSR matrix (arguments and validation as above),
+ * packed and uploaded as a coarse level operator of the multigrid is -- symmetric_storage 0: every block; 1: diagonal and upper
+ * blocks with their in-lists; 2: as 1 and read as K itself is under symmetric storage, the strict lower triangle of a diagonal
+ * block taken from its mirror image and never loaded -- with a status word of this call.  inv_out: n_nodes x 36, the inverse
+ * diagonal blocks unpacked from the 21 stored words to full symmetric blocks; *status_out: 0, or -(a + 1) of a node a whose
+ * diagonal block is not positive definite (its inverse is then the identity).  The context's matrix, hierarchy and state are
+ * not touched. */
+int femshell_amg_device_block_jacobi(femshell_ctx *ctx, int32_t n_nodes, const int32_t *rowptr, const int32_t *colidx,
+                                     const double *vals, int32_t symmetric_storage, double *inv_out, int32_t *status_out);
+/* For tests: the block-Jacobi inverse the context holds, n x 36 doubles as full symmetric blocks.  level 0: of K (block-Jacobi
+ * and multigrid contexts; n = nodes of the mesh, in the caller's numbering); level >= 1: of that level operator of the multigrid
+ * hierarchy (n = its nodes).  single_precision != 0: the copy the smoothers read, widened; FEMSHELL_ERR_INVALID where the level
+ * keeps none, and for a level the context does not have.  Assembles and builds what is missing, as femshell_pc_apply does.
+ * One rank only: FEMSHELL_ERR_UNSUPPORTED for a row-partitioned context. */
+int femshell_block_jacobi_export(femshell_ctx *ctx, int32_t level, int32_t single_precision, double *out);
+/* For tests: z = D^-1 r with that inverse by one of its two readers -- path 0: one lane per row through LDS (the kernel of the
+ * power iteration, arithmetic of the CG kernels); path 1: one lane per node (the first Chebyshev step with 1 / theta = 1 on the
+ * level as the smoothers see it: the single-precision copy where the level has one).  r and z: 6 x 32 x ceil(n / 32) doubles,
+ * the level's padded vector as it lies in HBM (level 0 of a renumbering context: the library's numbering).  Same refusals. */
+int femshell_block_jacobi_apply(femshell_ctx *ctx, int32_t level, int32_t path, const double *r, double *z);
 /* The device-memory pool of this process as it stands (csrc/dev_pool.hpp; every buffer of every context comes out of it, so the
  * call takes no context and also answers after the last one was destroyed): out[0] = bytes the driver has handed out through
  * the pool and not got back, out[1] = bytes in use by buffers, out[2] = bytes kept for reuse (what FEMSHELL_POOL_GB bounds),

@@ -119,6 +119,10 @@ int32_t femshell_amg_host_aggregate_glued(int32_t n_nodes, const int32_t *rowptr
 /* dense inverse of a small SPD block matrix (coarsest level): inv_out (6n)^2 doubles */
 int femshell_amg_host_dense_inverse(int32_t n_nodes, const int32_t *rowptr, const int32_t *colidx, const double *vals,
                                     double *inv_out);
+/* the 6 x 6 block-Jacobi inverse of the host side of the multigrid setup (block_diagonal_inverse: it smooths the prolongator and feeds
+ * the patch smoother) on n blocks of 36 doubles, row-major: inv_out n x 36; ok_out (may be NULL) per block 1 = inverted, 0 = not
+ * positive definite, the identity was returned */
+int femshell_amg_host_block_inverse(int32_t n, const double *blocks, double *inv_out, int32_t *ok_out);
 /* the super-block lists of the device dense inverse's trailing update for nt 64-tiles per side (csrc/amg_dense.hip DenseTileMap):
  * returns per_xcd, the length of each of the eight lists; list_out (8 * per_xcd entries, at most cap are written; may be NULL)
  * [x * per_xcd + k] = (I << 16) | J of the k-th 8 x 8 super-block of XCD x, -1 = none.  < 0: invalid argument. */

@@ -253,6 +253,27 @@ def test_row_partitioned_hierarchy_follows_the_restatement(world, kind, dist_min
     check_hierarchy_against_the_restatement(world, kind, dist_min, tmp_path)
 
 
+def stacked_level_rows(ranks, level, what):
+    """the ranks' rows of an operator of a row-partitioned level, one under the other: (rowptr, cols, vals [nnzb, 6, 6]);
+    ranks: the workers' outputs in the order of their rows"""
+    rp, ci, va = [np.zeros(1, dtype=np.int64)], [], []
+    for r in ranks:
+        p = np.asarray(r["amg_L%d_%s_rowptr" % (level, what)], dtype=np.int64)
+        rp.append(p[1:] + rp[-1][-1])
+        ci.append(r["amg_L%d_%s_cols" % (level, what)])
+        va.append(r["amg_L%d_%s_vals" % (level, what)].reshape(-1, 6, 6))
+    return np.concatenate(rp), np.concatenate(ci), np.concatenate(va)
+
+
+def stacked_k_rows(ranks):
+    """K as the ranks assembled it (FEMSHELL_TEST_EXPORT=1), their rows one under the other: (rowptr, cols, vals [nnzb, 6, 6])"""
+    off = np.cumsum([0] + [int(np.asarray(r["k_rowptr"])[-1]) for r in ranks])
+    rp = np.concatenate([[0]] + [np.asarray(r["k_rowptr"], dtype=np.int64)[1:] + off[i] for i, r in enumerate(ranks)])
+    ci = np.concatenate([r["k_cols"][:int(np.asarray(r["k_rowptr"])[-1])] for r in ranks])
+    va = np.concatenate([r["k_vals"][:int(np.asarray(r["k_rowptr"])[-1])].reshape(-1, 6, 6) for r in ranks])
+    return rp, ci, va
+
+
 def check_hierarchy_against_the_restatement(world, kind, dist_min, tmp_path, extra_env=None):
     """(extra_env: more environment for the ranks -- tests/test_gpu_slice_walk.py runs the same assertions under a small grid.)
     oracle/amg_oracle.py restates the rank-local aggregation (aggregate_by_rank); tentative prolongator, smoothing and
@@ -275,21 +296,11 @@ def check_hierarchy_against_the_restatement(world, kind, dist_min, tmp_path, ext
         return sp.bsr_matrix((np.asarray(vals).reshape(-1, 6, 6), np.asarray(cols), np.asarray(rowptr)), shape=(6 * nr, 6 * nc))
 
     def stack(level, what, nc):
-        """the ranks' rows of an operator of a row-partitioned level, one under the other"""
-        rp, ci, va = [np.zeros(1, dtype=np.int64)], [], []
-        for r in ranks:
-            p = np.asarray(r["amg_L%d_%s_rowptr" % (level, what)], dtype=np.int64)
-            rp.append(p[1:] + rp[-1][-1])
-            ci.append(r["amg_L%d_%s_cols" % (level, what)])
-            va.append(r["amg_L%d_%s_vals" % (level, what)].reshape(-1, 6, 6))
-        rp = np.concatenate(rp)
-        return bsr(rp, np.concatenate(ci), np.concatenate(va), len(rp) - 1, nc)
+        rp, ci, va = stacked_level_rows(ranks, level, what)
+        return bsr(rp, ci, va, len(rp) - 1, nc)
 
     # K as the ranks assembled it
-    off = np.cumsum([0] + [int(np.asarray(r["k_rowptr"])[-1]) for r in ranks])
-    rp = np.concatenate([[0]] + [np.asarray(r["k_rowptr"], dtype=np.int64)[1:] + off[i] for i, r in enumerate(ranks)])
-    ci = np.concatenate([r["k_cols"][:int(np.asarray(r["k_rowptr"])[-1])] for r in ranks])
-    va = np.concatenate([r["k_vals"][:int(np.asarray(r["k_rowptr"])[-1])].reshape(-1, 6, 6) for r in ranks])
+    rp, ci, va = stacked_k_rows(ranks)
     A = bsr(rp, ci, va, n, n)
     F = np.concatenate([r["k_F"] for r in ranks])
     bounds = [int(r["begin"]) for r in ranks] + [n]
