@@ -41,6 +41,7 @@ SYMBOLS = [
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
     "femshell_pool_stats", "femshell_amg_device_dense_inverse", "femshell_amg_dense_apply",
     "femshell_amg_device_block_jacobi", "femshell_block_jacobi_export", "femshell_block_jacobi_apply",
+    "femshell_krylov_grid", "femshell_krylov_set", "femshell_krylov_get", "femshell_krylov_launch", "femshell_cg_reduce",
 ]
 
 
@@ -102,6 +103,22 @@ class BucklingInfo(C.Structure):
                 ("seconds_total", C.c_double), ("seconds_solves", C.c_double), ("seconds_products", C.c_double),
                 ("seconds_gram", C.c_double), ("seconds_update", C.c_double)]
 
+
+class KrylovScalars(C.Structure):
+    """femshell_krylov_scalars of include/femshell.h: the scalars of the recurrence as they lie in HBM (csrc/kernels.hpp CgScalars)"""
+    _fields_ = [("rz", C.c_double), ("alpha", C.c_double), ("beta", C.c_double), ("rr", C.c_double), ("bb", C.c_double),
+                ("tol2", C.c_double), ("red", C.c_double * 3), ("done", C.c_int32), ("iters", C.c_int32), ("ticket", C.c_uint32),
+                ("pad", C.c_uint32), ("stage", (C.c_double * 64) * 3), ("ring_rz", C.c_double * 2), ("ring_alpha", C.c_double * 2),
+                ("pass_xx", C.c_double), ("pass_rhs_rr", C.c_double), ("pass_rtol", C.c_double)]
+
+
+# femshell_krylov_set / _get: the arrays, and femshell_krylov_launch: the steps (include/femshell.h)
+KRYLOV_ARRAYS = {"x": 0, "r": 1, "z": 2, "p": 3, "q": 4, "sv": 5, "b": 6, "partials": 7, "scalars": 8, "history": 9, "history_cap": 10}
+KRYLOV_STEPS = {"cg_init": 0, "cg_update": 1, "cg_direction": 2, "cgcg_init": 3, "cgcg_update": 4, "pcg_init": 5, "pcg_update": 6,
+                "pcg_update_start": 7, "pcg_norm": 8, "pcg_dots": 9, "minv_apply_norm": 10, "product": 11, "sym_gather": 12,
+                "two_dots": 13, "scalar_step": 14, "pc_apply": 15, "copy_z_to_p": 16}
+CG_PHASES = {"none": 0, "init": 1, "alpha": 2, "beta": 3, "restart": 4, "fused_init": 5, "fused_step": 6, "flex_init": 7,
+             "flex_rz0": 8, "flex_conv": 9, "flex_beta": 10, "flex_restart": 11, "flex_warm": 12}
 
 PC_BLOCK_JACOBI, PC_AMG = 0, 1
 CYCLE_V, CYCLE_K = 0, 1
@@ -221,6 +238,11 @@ def load_library():
     L.femshell_amg_device_block_jacobi.argtypes = [vp, C.c_int32, ip, ip, dp, C.c_int32, dp, ip]
     L.femshell_block_jacobi_export.argtypes = [vp, C.c_int32, C.c_int32, dp]
     L.femshell_block_jacobi_apply.argtypes = [vp, C.c_int32, C.c_int32, dp, dp]
+    L.femshell_krylov_grid.argtypes = [vp]
+    L.femshell_krylov_set.argtypes = [vp, C.c_int32, dp, C.c_int64]
+    L.femshell_krylov_get.argtypes = [vp, C.c_int32, dp, C.c_int64]
+    L.femshell_krylov_launch.argtypes = [vp, C.c_int32, ip, C.c_double, ip, dp]
+    L.femshell_cg_reduce.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, C.POINTER(C.c_uint32)]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -732,6 +754,54 @@ class FemShell:
         _check(self._L.femshell_block_jacobi_apply(self._h, int(level), int(path), _d(r), _d(z)))
         return z
 
+    # ---- the Krylov loops launch by launch, for tests (femshell_krylov_*, csrc/api_krylov_probe.cpp)
+    def krylov_grid(self):
+        """workgroups of the per-slice kernels = partial sums per array"""
+        return int(self._L.femshell_krylov_grid(self._h))
+
+    def krylov_set(self, which, data):
+        """Writes one array of the context's CG state (KRYLOV_ARRAYS): a vector as (n_nodes, 6) in the caller's numbering, the
+        partial sums as raw words from the start, the scalars as a KrylovScalars, the history buffer (its length becomes the cap),
+        "history_cap" as a number."""
+        if isinstance(data, KrylovScalars):
+            data = np.frombuffer(bytes(data), dtype=np.float64).copy()
+        data = np.ascontiguousarray(np.atleast_1d(data), dtype=np.float64).reshape(-1)
+        _check(self._L.femshell_krylov_set(self._h, KRYLOV_ARRAYS[which], _d(data), data.size))
+
+    def krylov_get(self, which, n=None):
+        """Reads one array of the CG state back: a vector as (n_nodes, 6), n words of the partial sums or of the history, the
+        scalars as a KrylovScalars."""
+        if which == "scalars":
+            out = np.zeros(C.sizeof(KrylovScalars) // 8)
+            _check(self._L.femshell_krylov_get(self._h, KRYLOV_ARRAYS[which], _d(out), out.size))
+            return KrylovScalars.from_buffer_copy(out.tobytes())
+        vector = KRYLOV_ARRAYS[which] <= KRYLOV_ARRAYS["b"]
+        if not vector and which != "history_cap" and n is None:
+            raise ValueError("krylov_get(%r) needs n, the number of words to read" % which)
+        out = np.zeros(6 * self.n_nodes if vector else (1 if which == "history_cap" else int(n)))
+        _check(self._L.femshell_krylov_get(self._h, KRYLOV_ARRAYS[which], _d(out), out.size))
+        return out.reshape(-1, 6) if vector else (int(out[0]) if which == "history_cap" else out)
+
+    def krylov_launch(self, step, *args, rtol=0.0):
+        """One production launch of KRYLOV_STEPS on the CG state, synchronised.  Returns (n_partials the step reports -- 0: the
+        grid --, the grid, the two sums of "two_dots")."""
+        a = np.zeros(5, dtype=np.int32)
+        a[:len(args)] = args
+        iout, dout = np.zeros(2, dtype=np.int32), np.zeros(2)
+        _check(self._L.femshell_krylov_launch(self._h, KRYLOV_STEPS[step], _i(a), float(rtol), _i(iout), _d(dout)))
+        return int(iout[0]), int(iout[1]), dout
+
+    def cg_reduce(self, partials, n_partials, nsums=1, len3=0):
+        """The two-stage reduction (k_cg_scalar, reduce only) on the caller's arrays: nsums arrays of n_partials words one behind
+        the other, the third len3 long.  Returns (red[3], the ticket behind the launch)."""
+        partials = np.ascontiguousarray(partials, dtype=np.float64).reshape(-1)
+        need = 2 * n_partials + len3 if nsums == 3 else nsums * n_partials
+        if partials.size != need:
+            raise ValueError("partials needs %d words" % need)
+        red, ticket = np.zeros(3), C.c_uint32(12345)
+        _check(self._L.femshell_cg_reduce(self._h, int(n_partials), int(nsums), int(len3), _d(partials), _d(red), C.byref(ticket)))
+        return red, int(ticket.value)
+
     def amg_patch_info(self):
         """The patch smoother of level 0 (csrc/amg_patch.hpp): rigid edges, clusters, nodes in them; all zero without rigid edges."""
         out = np.zeros(6)
@@ -1069,7 +1139,7 @@ def knob_flag(name, default):
 # the derived products of a context and the changes that make them stale, in the order of csrc/derived.hpp
 DERIVED_PRODUCTS = ["K", "F", "Jacobi", "Hierarchy", "Mass", "Ubar", "Solution", "WarmStart", "Fp64Only"]
 STATE_CHANGES = ["mesh", "dirichlet", "sections", "sections_cleared_none_set", "loads", "prescribed", "density", "pc_options",
-                 "assembled", "matrix_shifted", "dynamics_begin", "matrix_spoiled", "dynamics_end", "fp64_fallback"]
+                 "assembled", "matrix_shifted", "dynamics_begin", "matrix_spoiled", "dynamics_end", "fp64_fallback", "krylov_probe"]
 
 
 def stale_after(change):

@@ -215,6 +215,9 @@ double *amg_apply_iterate(femshell_ctx *c, double *z);
 // *rec_rr_out: recurrence ||r||^2 the stopping rule saw last
 // (x0: the iterate to start from -- owned rows, n_pad * 6 doubles in HBM -- or nullptr for zero)
 int cg_amg(femshell_ctx *c, const CgVectors &v, double rtol, int32_t max_it, double *true_rr_out, double *rec_rr_out, const double *x0 = nullptr);
+// sums = (a.a, b.b) over the owned rows of all ranks: launch_two_dots, the host's sum of its stage-1 sums, the all-reduce (cg_amg's
+// error estimate and ||x||^2 of a refinement pass; femshell_krylov_launch shows it to the tests)
+int two_squared_norms(femshell_ctx *c, const double *a, const double *b, int64_t n6, double sums[2]);
 // algorithmic HBM bytes of one cycle as it is built (single-precision copies, increments, the real product counts), and per level
 double amg_cycle_bytes(const femshell_ctx *c, std::vector<double> *per_level = nullptr);
 // K of a single-rank context as host BSR with ascending columns (api.cpp)

@@ -1457,7 +1457,7 @@ int amg_apply(femshell_ctx *c, const double *r, double *z, const CgScalars *gate
 
 // ||a||^2 and ||b||^2 over the owned rows of all ranks (two partial arrays of 128 groups, room for a third, and behind them the
 // two-word staging slot of the all-reduce)
-static int two_squared_norms(femshell_ctx *c, const double *a, const double *b, int64_t n6, double sums[2])
+int two_squared_norms(femshell_ctx *c, const double *a, const double *b, int64_t n6, double sums[2])
 {
     hipStream_t st = c->stream;
     constexpr size_t kDotsStage = 3 * 128;

@@ -172,6 +172,11 @@ struct femshell_ctx {
     femshell::DevBuf<double> x, r, z, p, q, sv, partials, hist, sendbuf, ufull;
     femshell::DevBuf<double> xacc, rres; // iterative refinement of the multigrid-preconditioned solve: accumulated solution, residual
     femshell::DevBuf<femshell::CgScalars> scal;
+    // femshell_krylov_* (api_krylov_probe.cpp, tests): the residual history its launches write, with the cap the caller chose
+    femshell::DevBuf<double> probe_hist;
+    int32_t probe_hist_cap = 0;
+    // femshell_cg_reduce: its scalars, zeroed once and kept from call to call (every launch starts from the ticket the last one left)
+    femshell::DevBuf<femshell::CgScalars> probe_scal;
     femshell::DevBuf<int32_t> send_nodes, spmv_order;
     std::vector<int32_t> send_offsets; // per peer, in nodes
     // scratch for femshell_time_kernel

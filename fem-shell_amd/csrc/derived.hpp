@@ -39,6 +39,7 @@ enum class Change : int32_t {
                                // shift, a failed asynchronous assembly)
     dynamics_end,              // ... femshell_dynamics_end: the same, and a pending warm start is dropped
     fp64_fallback,             // a solve broke down under single-precision copies: the hierarchy again, all FP64
+    krylov_probe,              // femshell_krylov_set / _launch wrote the vectors of the solve: x is no solution any more
     count
 };
 
@@ -62,6 +63,7 @@ constexpr uint32_t stale_after(Change what)
     case Change::matrix_spoiled: return kWithK;
     case Change::dynamics_end: return kWithK | kWarmStart;
     case Change::fp64_fallback: return kHierarchy;
+    case Change::krylov_probe: return kSolution;
     case Change::count: break;
     }
     return 0;

@@ -353,6 +353,67 @@ int femshell_block_jacobi_export(femshell_ctx *ctx, int32_t level, int32_t singl
  * level as the smoothers see it: the single-precision copy where the level has one).  r and z: 6 x 32 x ceil(n / 32) doubles,
  * the level's padded vector as it lies in HBM (level 0 of a renumbering context: the library's numbering).  Same refusals. */
 int femshell_block_jacobi_apply(femshell_ctx *ctx, int32_t level, int32_t path, const double *r, double *z);
+/* ---- For tests: the Krylov loops launch by launch (csrc/api_krylov_probe.cpp).  "Set, launch one, get" on the
+ * context's own CG state -- the vectors and scalars femshell_solve iterates in -- through the production launchers and nothing
+ * else.  No production path runs through these.  All three refuse (FEMSHELL_ERR_INVALID, the context as it was) without a mesh,
+ * without an assembled K and its block-Jacobi inverse, and while dynamics is active; they never assemble or build anything. */
+/* A plain mirror of the scalars of the recurrence in HBM (csrc/kernels.hpp CgScalars: same size, same offsets). */
+typedef struct femshell_krylov_scalars {
+    double rz, alpha, beta, rr, bb, tol2;
+    double red[3];
+    int32_t done, iters;
+    uint32_t ticket, pad;
+    double stage[3][64];
+    double ring_rz[2], ring_alpha[2];
+    double pass_xx, pass_rhs_rr, pass_rtol;
+} femshell_krylov_scalars;
+enum {
+    /* node vectors, n_nodes x 6 in the caller's numbering (a row-partitioned context moves its owned rows only and leaves the
+     * rest of `data` alone); padding rows are written as zeros and never returned.  Writing b makes F stale, as new loads do. */
+    FEMSHELL_KRYLOV_X = 0, FEMSHELL_KRYLOV_R = 1, FEMSHELL_KRYLOV_Z = 2, FEMSHELL_KRYLOV_P = 3, FEMSHELL_KRYLOV_Q = 4,
+    FEMSHELL_KRYLOV_SV = 5, FEMSHELL_KRYLOV_B = 6,
+    FEMSHELL_KRYLOV_PARTIALS = 7, /* the partial-sum arrays as raw words: n <= 4 G doubles from the start, G = femshell_krylov_grid */
+    FEMSHELL_KRYLOV_SCALARS = 8,  /* one femshell_krylov_scalars (n = its size in doubles) */
+    FEMSHELL_KRYLOV_HISTORY = 9,  /* the history buffer of the probe, its own: set allocates n <= 4096 words, fills them and makes n
+                                   * the cap; get reads n <= that many */
+    FEMSHELL_KRYLOV_HISTORY_CAP = 10 /* data[0]: the cap the launches see, 0 .. the words of the buffer (words beyond stay as set) */
+};
+enum {
+    FEMSHELL_KSTEP_CG_INIT = 0,         /* args[0]: restart */
+    FEMSHELL_KSTEP_CG_UPDATE = 1,       /* args[0]: gather (symmetric storage) */
+    FEMSHELL_KSTEP_CG_DIRECTION = 2,
+    FEMSHELL_KSTEP_CGCG_INIT = 3,
+    FEMSHELL_KSTEP_CGCG_UPDATE = 4,     /* args[0]: step -1, 0 or 1; args[1]: gather */
+    FEMSHELL_KSTEP_PCG_INIT = 5,
+    FEMSHELL_KSTEP_PCG_UPDATE = 6,
+    FEMSHELL_KSTEP_PCG_UPDATE_START = 7, /* args[0]: gather.  Multigrid contexts with a built hierarchy of two levels or more; the
+                                          * direction goes to level 0's d vector, the iterate to z */
+    FEMSHELL_KSTEP_PCG_NORM = 8,
+    FEMSHELL_KSTEP_PCG_DOTS = 9,
+    FEMSHELL_KSTEP_MINV_APPLY_NORM = 10, /* z = D^-1 q, partial sums of z.z */
+    FEMSHELL_KSTEP_PRODUCT = 11,        /* spmv_with_halo: args[0] = 0: q = K p, sums from partials[0]; 1: q = K z, sums from
+                                         * partials[2 G] (single-reduction); args[1]: the gather is left to the next kernel.
+                                         * iout[0] = the partial sums it reports (0: G) */
+    FEMSHELL_KSTEP_SYM_GATHER = 12,     /* q += the transposed products (symmetric storage) */
+    FEMSHELL_KSTEP_TWO_DOTS = 13,       /* args[0], args[1]: two of the vectors above, 0 .. 6: dout = (a.a, b.b) */
+    FEMSHELL_KSTEP_SCALAR_STEP = 14,    /* scalar_step: args = nsums, phase, n_partials (0: G), len3, gate_phase (-1: the phase's) */
+    FEMSHELL_KSTEP_PC_APPLY = 15,       /* z = M(r) as the flexible recurrence issues it, gated by the scalars; args[0]: the first
+                                         * pre-smoothing step was taken by PCG_UPDATE_START.  Multigrid contexts with a hierarchy */
+    FEMSHELL_KSTEP_COPY_Z_TO_P = 16     /* p = z, gated by the scalars (the first direction of the flexible recurrence) */
+};
+int32_t femshell_krylov_grid(femshell_ctx *ctx); /* workgroups of the per-slice kernels = partial sums per array; -1 without a mesh */
+int femshell_krylov_set(femshell_ctx *ctx, int32_t which, const double *data, int64_t n);
+int femshell_krylov_get(femshell_ctx *ctx, int32_t which, double *data, int64_t n);
+/* Exactly one production launch (PRODUCT, TWO_DOTS, SCALAR_STEP, PC_APPLY: the production sequence of that name) on that state,
+ * then a stream synchronisation and hipGetLastError.  args: five words (unused ones 0); iout (two words) and dout (two doubles)
+ * may be NULL where the step returns nothing. */
+int femshell_krylov_launch(femshell_ctx *ctx, int32_t step, const int32_t *args, double rtol, int32_t *iout, double *dout);
+/* launch_cg_scalar(reduce, phase NONE) on the caller's arrays, in a buffer of this call alone and with scalars of the probe's own,
+ * kept from call to call as a solve keeps its: partials holds nsums (1 .. 3) arrays of n_partials (1 .. 2^20) doubles one behind the
+ * other, the third of them len3 (1 .. n_partials) long.  red_out[3]: the sums (NaN where the launch wrote none); *ticket_out: the
+ * arrival counter behind the launch.  Needs no mesh. */
+int femshell_cg_reduce(femshell_ctx *ctx, int32_t n_partials, int32_t nsums, int32_t len3, const double *partials, double *red_out,
+                       uint32_t *ticket_out);
 /* The device-memory pool of this process as it stands (csrc/dev_pool.hpp; every buffer of every context comes out of it, so the
  * call takes no context and also answers after the last one was destroyed): out[0] = bytes the driver has handed out through
  * the pool and not got back, out[1] = bytes in use by buffers, out[2] = bytes kept for reuse (what FEMSHELL_POOL_GB bounds),

@@ -28,6 +28,7 @@ TABLE = {
     "matrix_spoiled": {"K", "F", "Jacobi", "Hierarchy"},
     "dynamics_end": {"K", "F", "Jacobi", "Hierarchy", "WarmStart"},
     "fp64_fallback": {"Hierarchy"},
+    "krylov_probe": {"Solution"},
 }
 # the flags only api_state.cpp may assign to (have_solution: but for the one place where a solve produces it, below)
 FLAGS = ["matrix_valid", "rhs_valid", "jacobi_valid", "mass_valid", "ubar_valid", "have_solution", "amg_fp64_only"]
