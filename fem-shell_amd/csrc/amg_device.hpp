@@ -1,4 +1,5 @@
-// amg_device.hpp -- the multigrid hierarchy in HBM (amg_solve.cpp) as the context sees it.
+// amg_device.hpp -- the multigrid hierarchy in HBM as the context sees it: built by amg_hierarchy.cpp (one rank, replicated levels),
+// amg_device_setup.cpp and amg_dist.cpp, applied by amg_solve.cpp.
 #pragma once
 #include "amg_patch.hpp"
 
@@ -8,6 +9,7 @@
 #include "amg.hpp"
 #include "amg_kernels.hpp"
 #include "context.hpp"
+#include "trace.hpp"
 
 namespace femshell {
 
@@ -72,7 +74,7 @@ struct AmgPatches {
     DevBuf<double> M;
     std::vector<int32_t> label; // per node: its cluster or -1
     // ... and the same without the clusters that hold a node another rank reads (row-partitioned levels): those smooth -- a purely
-    // local matter -- but neither widen their members' rows of P nor are glued (amg_solve.cpp amg_build_patches)
+    // local matter -- but neither widen their members' rows of P nor are glued (amg_hierarchy.cpp amg_build_patches)
     std::vector<int32_t> label_p;
     DevBuf<uint8_t> in_p;
     std::vector<int32_t> h_ptr, h_nodes;
@@ -169,10 +171,10 @@ struct Amg {
     std::shared_ptr<AmgDist> dist; // row-partitioned contexts only
 };
 
-// K itself (level 0) is the coarsest level -- a dense inverse and nothing else -- only up to this many nodes (amg_solve.cpp)
+// K itself (level 0) is the coarsest level -- a dense inverse and nothing else -- only up to this many nodes (amg_hierarchy.cpp)
 constexpr int32_t kDirectNodes = 200;
 void amg_default_options(femshell_pc_options *o);
-// symmetric storage of a coarse level operator of n_nodes nodes (large levels only, see amg_solve.cpp)
+// symmetric storage of a coarse level operator of n_nodes nodes (large levels only, see amg_hierarchy.cpp)
 bool coarse_symmetric_storage(int32_t n_nodes);
 // in-lists of a symmetric-storage operator into HBM and into op.dm (the slot arrays of op are in place already)
 int attach_in_lists(AmgOperator &op, const SlicedEllSym &S, int64_t total_slots, hipStream_t st);
@@ -189,6 +191,50 @@ int amg_setup_dist(femshell_ctx *c);
 // coarsest level, dense inverse, Chebyshev coefficients of all levels
 int amg_finish_hierarchy(femshell_ctx *c, Bsr &A, std::vector<double> &B, DevBuf<double> &Bdev, int first_level);
 int alloc_level_vectors(AmgLevel &L, bool top, bool kcycle, hipStream_t st);
+// the operator of level l as the products see it: K on level 0, the level's own below
+const DeviceMatrix &amg_level_matrix(const femshell_ctx *c, int l);
+// (shared by the files that build the hierarchy, not part of what libfemshell.so exports)
+#pragma GCC visibility push(hidden)
+// block-Jacobi inverse of the operator of coarse level `level` into L.minv; *bad: a diagonal block is not positive definite -- the
+// status word is cleared again and the error text set, what becomes of it is the caller's (a row partition agrees on it first)
+int level_block_jacobi(femshell_ctx *c, AmgLevel &L, int level, bool *bad);
+// lambda_max(D^-1 A) of a level by power iteration on the device, in two halves (amg_hierarchy.cpp): the launches, and the one
+// synchronisation that brings the last two norms back.  Row-partitioned levels: a halo exchange in front of every product, the
+// two sums all-reduced.
+struct PowerIteration {
+    DevBuf<double> part; // the partials of the last two norms by parity of the step, and behind them their two sums
+    int G = 0, iterations = 0;
+    bool dist = false;
+    hipStream_t st = nullptr; // the stream its launches went to
+};
+int power_iteration_start(femshell_ctx *c, AmgLevel &L, const DeviceMatrix &A, int iterations, PowerIteration *pw, bool beside = false);
+int power_iteration_finish(femshell_ctx *c, PowerIteration &pw, double *lam_out);
+// FEMSHELL_AMG_VERBOSE, read once per process
+inline bool setup_verbose()
+{
+    static const bool verbose = amg_verbose();
+    return verbose;
+}
+// the stopwatch of a setup: one line per step when verbose, and the heartbeat
+struct SetupLap {
+    std::string prefix; // "[femshell amg setup]" or "[femshell amg setup, rank N]"
+    int width;          // of the column of step names
+    int level = 0;
+    double tl = now_s();
+    void operator()(const char *what)
+    {
+        const double t = now_s();
+        if (setup_verbose()) fprintf(stderr, "%s level %d %-*s %.3f s\n", prefix.c_str(), level, width, what, t - tl);
+        tl = t;
+        CommWatch::heartbeat(); // (progress of the phase the watchdog of a multi-rank context times)
+    }
+    void operator()(const char *what, int l)
+    {
+        level = l;
+        (*this)(what);
+    }
+};
+#pragma GCC visibility pop
 // ghost entries of vec (width doubles per node, ghosts behind the n_pad owned rows) from their owners
 int level_halo_exchange(femshell_ctx *c, LevelHalo &H, double *vec, int width, hipStream_t st);
 // nodes above which a coarse level stays row-partitioned (FEMSHELL_AMG_DIST_MIN, default 60000)
@@ -233,7 +279,7 @@ int amg_dense_inverse_device(femshell_ctx *c, const Bsr &A, bool single_precisio
 // y = Ainv b for such an inverse (one of A64 / A32 non-null); rows [n, n_pad6) of y are set to zero
 void launch_dense_gemv_big(const double *A64, const float *A32, int64_t lda, const double *b, double *y, int32_t n, int32_t n_pad6,
                            const CgScalars *gate, hipStream_t st);
-// For tests (amg_solve.cpp; the entry points are in api.cpp): k_block_jacobi on a caller's matrix packed as a coarse level operator
+// For tests (amg_hierarchy.cpp; the entry points are in api.cpp): k_block_jacobi on a caller's matrix packed as a coarse level operator
 // is (storage 0 full, 1 diagonal + upper blocks, 2 the same with DeviceMatrix::diag_upper), with a status word of the call;
 // the 21 packed words per node of the inverse a level holds (level 0: K; single_precision: the smoothers' copy); z = D^-1 r over
 // the padded vector of a level by the lane-per-row reader (path 0) or the lane-per-node reader (path 1)
@@ -256,7 +302,7 @@ int amg_device_coarsen(femshell_ctx *c, const DeviceMatrix &A, const HostEllPatt
 // HostEllPattern::borrowed)
 void pattern_of_plan(const Plan &p, HostEllPattern *out, bool light = false);
 
-// clusters of rigidly coupled nodes of a level whose operator is in HBM, and their smoother blocks (amg_solve.cpp; amg_patch.hpp).
+// clusters of rigidly coupled nodes of a level whose operator is in HBM, and their smoother blocks (amg_hierarchy.cpp; amg_patch.hpp).
 // collective: the ranks of a row partition decide together whether the mesh needs them.  L.patches stays null when it does not.
 // excluded (optional, one flag per own node): nodes no cluster may take -- those another rank reads.
 int amg_build_patches(femshell_ctx *c, const DeviceMatrix &A, AmgLevel &L, bool collective, const std::vector<uint8_t> *excluded = nullptr);

@@ -1,5 +1,5 @@
 // amg_device_setup.cpp -- coarsening steps of the multigrid setup with the numerics on the device (every level above
-// FEMSHELL_AMG_DEVICE_MIN nodes, amg_solve.cpp).
+// FEMSHELL_AMG_DEVICE_MIN nodes, amg_hierarchy.cpp).
 //
 // The finest level dominates the setup: K has 14M blocks on the 4M-triangle meshes, and the host path (amg_setup.cpp)
 // first has to bring it over PCIe and mirror it.  Here the host only does integer work on the block graph the plan (or
@@ -102,16 +102,11 @@ int upload_pattern(const EllPattern &E, DevPattern &D, double *vals, EllView *vi
 // the pattern's device arrays become the operator's own (the cycle multiplies with them)
 void adopt(AmgOperator &op, const EllPattern &E, DevPattern &D, DevBuf<double> &vals, int32_t n_cols_pad)
 {
-    std::swap(op.slice_width.p, D.slice_width.p);
-    std::swap(op.slice_width.n, D.slice_width.n);
-    std::swap(op.slice_base.p, D.slice_base.p);
-    std::swap(op.slice_base.n, D.slice_base.n);
-    std::swap(op.cols.p, D.cols.p);
-    std::swap(op.cols.n, D.cols.n);
-    std::swap(op.count.p, D.count.p); // (the row lengths: the next coarsening step's symbolic kernels read them)
-    std::swap(op.count.n, D.count.n);
-    std::swap(op.vals.p, vals.p);
-    std::swap(op.vals.n, vals.n);
+    op.slice_width.swap(D.slice_width);
+    op.slice_base.swap(D.slice_base);
+    op.cols.swap(D.cols);
+    op.count.swap(D.count); // (the row lengths: the next coarsening step's symbolic kernels read them)
+    op.vals.swap(vals);
     op.nnzb = E.nnzb;
     op.n_cols_pad = n_cols_pad;
     op.dm = DeviceMatrix();

@@ -3,7 +3,7 @@
 // The reference partitions its elements over the MPI ranks and leaves the preconditioner to PETSc, which builds it on the
 // distributed matrix (doc/implementation.tex:463-472: only the mesh is replicated).  Here: levels 0 .. d-1 of the hierarchy
 // are row-partitioned like K, the first level of at most FEMSHELL_AMG_DIST_MIN nodes is all-gathered once and it and
-// everything below run replicated on every rank (amg_solve.cpp: amg_finish_hierarchy).
+// everything below run replicated on every rank (amg_hierarchy.cpp: amg_finish_hierarchy).
 //
 // A row-partitioned coarsening step.  Only the aggregation knows about the ranks: every rank aggregates the graph of its own
 // rows without the edges that leave it, so aggregates never span ranks and the coarse rows are numbered rank by rank.
@@ -24,10 +24,8 @@
 // the ghost entries of the coarse correction: one halo exchange each, no reduction across ranks.
 #include "amg_device.hpp"
 #include "amg_pattern.hpp"
-#include "trace.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -37,8 +35,6 @@
 namespace femshell {
 
 namespace {
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // every rank's value (one-hot all-reduce)
 int allgather_i64(femshell_ctx *c, int64_t mine, std::vector<int64_t> *all)
@@ -88,6 +84,25 @@ int allgather_doubles(femshell_ctx *c, const double *mine, int64_t count, std::v
 // rows of `width` doubles of the ghost nodes of a level into their places behind the owned rows of src (in place)
 int exchange_rows(femshell_ctx *c, LevelHalo &H, double *vec, int width) { return level_halo_exchange(c, H, vec, width, c->stream); }
 
+// the send lists of a halo whose peers are known: per peer where its nodes begin, the nodes peer after peer in HBM, and a buffer
+// of six doubles per node sent
+int upload_send_lists(LevelHalo &H, hipStream_t st)
+{
+    H.send_offsets.clear();
+    std::vector<int32_t> flat;
+    for (const HaloPeer &p : H.peers) {
+        H.send_offsets.push_back((int32_t)flat.size());
+        flat.insert(flat.end(), p.send_nodes.begin(), p.send_nodes.end());
+    }
+    H.total_send = (int32_t)flat.size();
+    if (flat.empty()) flat.push_back(0);
+    FS_HIP(H.send_nodes.upload(flat, st));
+    FS_HIP(H.sendbuf.alloc((size_t)std::max(H.total_send, 1) * 6));
+    H.sendbuf_width = 6;
+    FS_HIP(hipStreamSynchronize(st));
+    return FEMSHELL_OK;
+}
+
 // Ghost exchange of the coarse level a step creates.  ghost_keys: the global ids of the coarse nodes this rank reads besides
 // its own, ascending (= grouped by owner).  Every rank learns all lists, so it knows what its neighbours read of its rows.
 int build_level_halo(femshell_ctx *c, const std::vector<int32_t> &part, int32_t n_pad, const std::vector<int32_t> &ghost_keys,
@@ -118,19 +133,7 @@ int build_level_halo(femshell_ctx *c, const std::vector<int32_t> &part, int32_t 
         }
         if (p.recv_count > 0 || !p.send_nodes.empty()) H.peers.push_back(std::move(p));
     }
-    H.send_offsets.clear();
-    std::vector<int32_t> flat;
-    for (const HaloPeer &p : H.peers) {
-        H.send_offsets.push_back((int32_t)flat.size());
-        flat.insert(flat.end(), p.send_nodes.begin(), p.send_nodes.end());
-    }
-    H.total_send = (int32_t)flat.size();
-    if (flat.empty()) flat.push_back(0);
-    FS_HIP(H.send_nodes.upload(flat, c->stream));
-    FS_HIP(H.sendbuf.alloc((size_t)std::max(H.total_send, 1) * 6));
-    H.sendbuf_width = 6;
-    FS_HIP(hipStreamSynchronize(c->stream));
-    return FEMSHELL_OK;
+    return upload_send_lists(H, c->stream);
 }
 
 // fixed-width ghost rows behind the own rows of a pattern: slices of width W, cols / count filled once the keys are known
@@ -197,7 +200,7 @@ struct StepResult {
 // local: own rows, padding, ghosts), Bsrc: near-null space of the own rows.
 int dist_coarsen(femshell_ctx *c, const femshell_pc_options &opt, int level, const DeviceMatrix &Adev, const HostEllPattern &pat,
                  AmgLevel &L, AmgLevel &N, const NearNullSrc &Bsrc, bool keep_host, int max_level_index, StepResult *res,
-                 const std::function<void(const char *)> &lap)
+                 SetupLap &lap)
 {
     hipStream_t st = c->stream;
     const int world = c->comm.world, me = c->comm.rank;
@@ -746,47 +749,6 @@ int dist_coarsen(femshell_ctx *c, const femshell_pc_options &opt, int level, con
     return FEMSHELL_OK;
 }
 
-// lambda_max(D^-1 A) of a row-partitioned level: the power iteration of amg_solve.cpp with the halo exchange in front of
-// every product and the two last norms summed over the ranks
-int power_iteration_dist(femshell_ctx *c, AmgLevel &L, const DeviceMatrix &A, int iterations, double *lam_out)
-{
-    hipStream_t st = c->stream;
-    const int G = slice_grid(A);
-    DevBuf<double> part;
-    FS_HIP(part.alloc(2 * (size_t)G + 2));
-    double *x = L.d.p, *z = L.r.p;
-    launch_fill_hash(x, 6ll * L.n, 6ll * L.n_pad, st);
-    if (iterations < 2) iterations = 2;
-    for (int it = 0; it < iterations; it++) {
-        int rc = level_halo_exchange(c, *L.halo, x, 6, st);
-        if (rc) return rc;
-        launch_spmv(A, x, L.q.p, SpmvEpilogue(), nullptr, st);
-        launch_minv_apply_norm(A, L.q.p, z, part.p + (size_t)(it & 1) * G, st);
-        if (L.patches) { // the level's smoother applies the cluster blocks: lambda_max of THAT operator (amg_solve.cpp)
-            launch_patch_correct(L.patches->view(), L.q.p, 1.0, z, false, nullptr, nullptr, st);
-            launch_sqnorm_partials(z, 6ll * L.n_pad, part.p + (size_t)(it & 1) * G, G, st);
-        }
-        std::swap(x, z);
-    }
-    FS_HIP(hipGetLastError());
-    // the rank's two norms: sums over its G partials in index order, taken on the device (launch_sums_in_order -- the host's loop of
-    // rounds 4-5, same bits, without the megabyte that went to the host and the sixteen bytes that came back): stage[j] = the sum
-    // over part[j G, (j + 1) G); all-reduced as they lie, which of the two is the last norm is sorted out afterwards
-    double s[2] = {0.0, 0.0};
-    double *stage = part.p + 2 * (size_t)G;
-    launch_sums_in_order(part.p, G, stage, st);
-    FS_HIP(hipGetLastError());
-    std::string e;
-    if (!comm_allreduce_sum(c->comm, stage, 2, st, &e)) return set_err(FEMSHELL_ERR_COMM, e);
-    FS_HIP(hipMemcpyAsync(s, stage, sizeof s, hipMemcpyDeviceToHost, st));
-    FS_HIP(hipStreamSynchronize(st));
-    const double n_last = std::sqrt(s[(iterations - 1) & 1]), n_prev = std::sqrt(s[(iterations - 2) & 1]);
-    if (!(n_prev > 0.0) || !std::isfinite(n_last) || !(n_last > 0.0))
-        return set_err(FEMSHELL_ERR_BREAKDOWN, "multigrid setup: power iteration broke down");
-    *lam_out = n_last / n_prev;
-    return FEMSHELL_OK;
-}
-
 double operator_bytes(const AmgOperator &op)
 {
     return (double)op.vals.n * 8.0 + (double)op.cols.n * 4.0 + (double)op.tbuf.n * 8.0 + (double)op.in_slots.n * 8.0;
@@ -827,15 +789,7 @@ int amg_setup_dist(femshell_ctx *c)
     Amg &H = *c->amg;
     H.opt = opt;
     H.dist.reset(new AmgDist());
-    static const bool verbose = amg_verbose();
-    double tl = now_s();
-    int lap_level = 0;
-    auto lap = [&](const char *what) {
-        const double t = now_s();
-        if (verbose) fprintf(stderr, "[femshell amg setup, rank %d] level %d %-32s %.3f s\n", c->comm.rank, lap_level, what, t - tl);
-        tl = t;
-        CommWatch::heartbeat(); // (progress of the phase the watchdog times)
-    };
+    SetupLap lap{"[femshell amg setup, rank " + std::to_string(c->comm.rank) + "]", 32};
     const bool keep_host = amg_keep_host(pl.nnz_blocks); // inspection exports (tests)
     static const bool plain = amg_plain_rbm();
 
@@ -855,17 +809,8 @@ int amg_setup_dist(femshell_ctx *c)
         h.n_pad = pl.n_pad;
         h.n_ghost = pl.n_ghost;
         h.peers = pl.peers;
-        std::vector<int32_t> flat;
-        for (const HaloPeer &p : h.peers) {
-            h.send_offsets.push_back((int32_t)flat.size());
-            flat.insert(flat.end(), p.send_nodes.begin(), p.send_nodes.end());
-        }
-        h.total_send = (int32_t)flat.size();
-        if (flat.empty()) flat.push_back(0);
-        FS_HIP(h.send_nodes.upload(flat, st));
-        FS_HIP(h.sendbuf.alloc((size_t)std::max(h.total_send, 1) * 6));
-        h.sendbuf_width = 6;
-        FS_HIP(hipStreamSynchronize(st));
+        const int rc0 = upload_send_lists(h, st);
+        if (rc0) return rc0;
     }
     DevBuf<double> d_normals, Bdev;
     NearNullSrc src;
@@ -902,29 +847,13 @@ int amg_setup_dist(femshell_ctx *c)
     std::vector<double> B;
     int first_replicated = 0;
     for (int l = 0;; l++) {
-        lap_level = l;
+        lap.level = l;
         AmgLevel &L = *H.levels[(size_t)l];
         const DeviceMatrix &Adev = l == 0 ? c->dm : L.A.dm;
         if (l > 0) {
-            FS_HIP(L.minv.alloc((size_t)L.A.dm.n_slices * 21 * kSliceNodes));
-            L.A.dm.minv = L.minv.p;
-            L.A.dm.status = c->status_word;
-            launch_block_jacobi(L.A.dm, st);
-            FS_HIP(hipGetLastError());
-            int32_t status_now = 0;
-            {
-                const int rcs = fetch_status_word(c, st, &status_now);
-                if (rcs) return rcs;
-            }
-            const bool bad = status_now != 0; // (seen by the rank that owns the block only: the ranks agree below)
-            if (bad) {
-                {
-                    const int rcc = clear_status_word(c, st);
-                    if (rcc) return rcc;
-                }
-                (void)set_err(FEMSHELL_ERR_BREAKDOWN, "multigrid setup: a diagonal block of coarse level " + std::to_string(l) +
-                                                          " is not positive definite");
-            }
+            bool bad = false; // (seen by the rank that owns the block only: the ranks agree below)
+            const int rcj = level_block_jacobi(c, L, l, &bad);
+            if (rcj) return rcj;
             int64_t unused = 0;
             const int arc = global_max(c, bad ? -1 : 0, &unused, "the block-Jacobi inverse of a coarse level");
             if (arc) return bad ? FEMSHELL_ERR_BREAKDOWN : arc;
@@ -949,7 +878,9 @@ int amg_setup_dist(femshell_ctx *c)
             lap("patch smoother: clusters");
         }
         double lam = 0.0;
-        rc = power_iteration_dist(c, L, Adev, amg_power_iterations(), &lam);
+        PowerIteration pw;
+        rc = power_iteration_start(c, L, Adev, amg_power_iterations(), &pw);
+        if (!rc) rc = power_iteration_finish(c, pw, &lam);
         if (rc) return rc;
         L.lam = amg_lambda_safety() * lam;
         lap("block-Jacobi, power iteration");
@@ -971,8 +902,7 @@ int amg_setup_dist(femshell_ctx *c)
             first_replicated = l + 1;
             break;
         }
-        std::swap(Bdev.p, res.Bc_dev.p);
-        std::swap(Bdev.n, res.Bc_dev.n);
+        Bdev.swap(res.Bc_dev);
     }
     H.dist->dist_levels = first_replicated;
     FS_HIP(H.dist->x0.alloc((size_t)(pl.n_pad + pl.n_ghost) * 6));

@@ -13,7 +13,7 @@
 // reach 0.836, the coupled flap's 5 : 1 cells 0.965) where the point-block method works; what it does not cope with are NEARLY
 // COINCIDENT nodes, sigma > 0.98: 2.6 % of the edges of the random-point shells, 0.13 % of a jittered-grid Delaunay shell (90
 // iterations without cluster blocks), none of any structured mesh.  The method switches itself on when more than 1 % of the pairs
-// exceed 0.98 (FEMSHELL_AMG_PATCH_TRIGGER; amg_solve.cpp amg_build_patches) -- the ranks of a row partition decide together.
+// exceed 0.98 (FEMSHELL_AMG_PATCH_TRIGGER; amg_hierarchy.cpp amg_build_patches) -- the ranks of a row partition decide together.
 //
 // How.  Clusters: the edges of the block graph with sigma_max(D_i^-1/2 A_ij D_j^-1/2) > tau (0.8), strongest first, united while a
 // cluster stays within eight nodes (FEMSHELL_AMG_PATCH_TAU / _MAX; swept on 700 ... 50,000-point shells in four numberings:
@@ -25,7 +25,7 @@
 // Restated in oracle/amg_oracle.py (patch_*).  Level 0 only: the coarse operators of such a mesh are not the problem.  A level with
 // clusters keeps FP64 copies throughout (the flexible CG broke down under the single-precision ones on every such shell tried).
 // Row partitions: every rank clusters its own rows; a cluster that holds a node another rank reads smooths like the others but
-// neither widens its members' rows of P nor is glued (PatchView::in_p; amg_solve.cpp says why).
+// neither widens its members' rows of P nor is glued (PatchView::in_p; amg_hierarchy.cpp says why).
 #pragma once
 #include <cstdint>
 

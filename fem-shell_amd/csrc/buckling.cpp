@@ -22,7 +22,6 @@
 #include "trace.hpp"
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <numeric>
 
@@ -36,12 +35,6 @@ struct BucklingWork {
 void BucklingWorkDeleter::operator()(BucklingWork *w) const { delete w; }
 
 namespace {
-
-double now_s()
-{
-    using namespace std::chrono;
-    return duration<double>(steady_clock::now().time_since_epoch()).count();
-}
 
 struct Solver {
     const BucklingProblem &p;

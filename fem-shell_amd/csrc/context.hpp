@@ -84,7 +84,7 @@ struct femshell_ctx {
     femshell::DevBuf<double> x0;
     bool warm_next = false;
     hipStream_t aux_stream = nullptr; // the look-ahead of the dense inverse (amg_dense.hip)
-    // uploads a helper thread of the multigrid setup makes beside the main stream (the node normals, amg_solve.cpp): made by that
+    // uploads a helper thread of the multigrid setup makes beside the main stream (the node normals, amg_hierarchy.cpp): made by that
     // thread at its first use in a single-rank context and kept.  (Not at femshell_create: HIP maps streams onto four hardware queues,
     // and one stream more per context was enough, with two ranks sharing a card in the tests, for the look-ahead of the dense
     // inverse -- two streams that must run side by side -- to run into its bounded wait one time in four.)

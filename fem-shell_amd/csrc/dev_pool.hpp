@@ -13,6 +13,7 @@
 #include <map>
 #include <mutex>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "knobs.hpp"
@@ -482,7 +483,25 @@ class DevPool {
 template <class T> struct DevBuf {
     T *p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
     ~DevBuf() { release(); }
+    // owns its block: moves, never copies
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept { swap(o); }
+    DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) {
+            release();
+            swap(o);
+        }
+        return *this;
+    }
+    void swap(DevBuf &o) noexcept
+    {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+    }
     void release()
     {
         if (p) DevPool::get().free(p);

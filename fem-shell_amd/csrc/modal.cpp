@@ -17,7 +17,6 @@
 #include "context.hpp"
 #include "trace.hpp"
 
-#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -33,12 +32,6 @@ struct ModalWork {
 void ModalWorkDeleter::operator()(ModalWork *w) const { delete w; }
 
 namespace {
-
-double now_s()
-{
-    using namespace std::chrono;
-    return duration<double>(steady_clock::now().time_since_epoch()).count();
-}
 
 struct Solver {
     const ModalProblem &p;

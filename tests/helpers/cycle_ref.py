@@ -3,7 +3,7 @@ the hierarchy the library exports -- its level operators, prolongators, spectral
 amg_oracle.cycle() on it differs from the device's cycle by the solve-phase kernels alone (smoothers, transfers, the K cycle's
 Krylov steps, the coarsest solve), not by the setup, which tests/test_gpu_amg.py holds to the restatement on its own.  CPU code.
 
-float_mode mirrors the single-precision copies of csrc/amg_solve.cpp (FEMSHELL_AMG_SMOOTH_F32, amg_finish_hierarchy) rule for
+float_mode mirrors the single-precision copies of csrc/amg_hierarchy.cpp (FEMSHELL_AMG_SMOOTH_F32, amg_finish_hierarchy) rule for
 rule: on a level that keeps them the smoothing products and the residual increments read A rounded to float32 (L.As), the
 smoother's block inverse is rounded to float32, P and R are rounded where the next level has at least 4096 nodes (every level
 with mode 3, none with mode 2); the K cycle's products, the Galerkin operators and every vector stay FP64, and a level with
@@ -19,7 +19,7 @@ TOL_FP64 = 5e-12  # FP64 levels
 TOL_F32 = 1e-11   # single-precision copies of the values, FEMSHELL_AMG_VEC_F32=0, against the float model
 TOL_VEC = 5e-6    # FEMSHELL_AMG_VEC_F32=1/2 against the values-only float model
 
-DEFAULTS = {"smoother_degree": 3, "coarse_degree": 4, "eig_ratio": 30.0}  # csrc/amg_solve.cpp amg_default_options
+DEFAULTS = {"smoother_degree": 3, "coarse_degree": 4, "eig_ratio": 30.0}  # csrc/amg_hierarchy.cpp amg_default_options
 F32_MIN_NODES = 4096  # FEMSHELL_AMG_SMOOTH_F32=1: levels of at least this many nodes keep the copies
 
 
@@ -38,7 +38,7 @@ def to_f32(M):
 
 
 def chebyshev(L, lam, degree, eig_ratio):
-    """The smoother's coefficients of a level with spectral bound lam (csrc/amg_solve.cpp amg_finish_hierarchy)."""
+    """The smoother's coefficients of a level with spectral bound lam (csrc/amg_hierarchy.cpp amg_finish_hierarchy)."""
     lmax, lmin = lam, lam / eig_ratio
     theta, delta = 0.5 * (lmax + lmin), 0.5 * (lmax - lmin)
     sigma = theta / delta
@@ -87,7 +87,7 @@ def build_levels(As, Ps, lams, coarse_inverse, opts=None, patch_labels=None, flo
 
 def apply_float_copies(levels, mode, f32_min_nodes=F32_MIN_NODES):
     """The single-precision copies of FEMSHELL_AMG_SMOOTH_F32 = mode (0 off, 1 levels of at least f32_min_nodes nodes, 2 level 0
-    only, 3 every level), rule for rule as csrc/amg_solve.cpp sets them up.  Returns the indices of the levels that got them."""
+    only, 3 every level), rule for rule as csrc/amg_hierarchy.cpp sets them up.  Returns the indices of the levels that got them."""
     got = []
     for l, L in enumerate(levels[:-1]):
         if mode == 0 or (mode == 2 and l > 0) or (mode == 1 and L.n < f32_min_nodes) or L.patch is not None:

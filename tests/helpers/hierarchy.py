@@ -1,7 +1,7 @@
 """The multigrid hierarchy a single-rank context built, held level by level to the restatement oracle/amg_oracle.py.
 
 compare() restates the setup from the context's own K, spectral bounds and clusters, and holds aggregates, prolongators and
-level operators to it.  It also works out which coarsening steps ran their numerics on the device (csrc/amg_solve.cpp: level 0
+level operators to it.  It also works out which coarsening steps ran their numerics on the device (csrc/amg_hierarchy.cpp: level 0
 whenever it is coarsened above coarsest_nodes or has clusters, the coarser levels by SetupRules::device_step) and checks that
 the library accounts for exactly those.  What it returns says what the comparison exercised, so that a case can show that it
 reached the kernel path it is there for."""
@@ -52,7 +52,7 @@ def device_steps(sizes, coarsest_nodes, max_levels=12, clusters=False):
 
 
 def coarse_symmetric(n):
-    """csrc/amg_solve.cpp coarse_symmetric_storage: a coarse operator stored as diagonal + upper blocks."""
+    """csrc/amg_hierarchy.cpp coarse_symmetric_storage: a coarse operator stored as diagonal + upper blocks."""
     return 0 < _atol("FEMSHELL_AMG_COARSE_SYM", 100000) <= n and _atol("FEMSHELL_SYMMETRIC", 1) != 0
 
 

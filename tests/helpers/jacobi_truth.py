@@ -1,5 +1,5 @@
 """The 6 x 6 block-Jacobi inverse (csrc/kernels.hip k_block_jacobi, csrc/amg_setup.cpp spd_inverse6, oracle/amg_oracle.py
-block_diag_inverse) and the spectral bound of a multigrid level (power_iteration_start / _finish, power_iteration_dist) against
+block_diag_inverse) and the spectral bound of a multigrid level (power_iteration_start / _finish, on one rank and on a row partition) against
 truths that owe nothing to either: pure numpy, runs anywhere.
 
 truth(A)      the exact inverse of a 6 x 6 matrix of doubles in rational arithmetic, rounded once to long double -- exact, so there

@@ -1,5 +1,5 @@
 """The spectral bound lambda of every smoothed multigrid level -- a power iteration of 30 steps from a hash vector, times 1.1
-(csrc/amg_solve.cpp power_iteration_start / _finish, csrc/amg_dist.cpp power_iteration_dist) -- against lambda_max(D^-1 A) itself.
+(csrc/amg_hierarchy.cpp power_iteration_start / _finish, on one rank and on a row-partitioned level) -- against lambda_max(D^-1 A) itself.
 It sets the Chebyshev interval and the damping 4 / (3 lambda) of every prolongator; every restatement test takes the device's
 value as an input and cannot see a wrong one.
 
@@ -137,7 +137,7 @@ def test_safety_factor_and_iteration_count_do_what_they_say(monkeypatch):
 
 def test_row_partitioned_levels_report_one_lambda_that_meets_the_condition(tmp_path):
     """Two ranks, the panel of tests/helpers/multirank_worker.py (2337 nodes), FEMSHELL_AMG_DIST_MIN=100: levels 0 and 1 are
-    row-partitioned and their bound comes from power_iteration_dist.  Every rank reports the same bits; condition (1) against
+    row-partitioned and their bound comes from the same power iteration, halo exchanges and all-reduce included.  Every rank reports the same bits; condition (1) against
     the ranks' rows stacked.  Level 0 has 14,022 dofs, beyond a dense eigh in a test: true_lambda_sparse (the same reduced
     pencil, Lanczos to convergence; equal to the dense value to 1e-13 where both can run, tests/test_jacobi_truth_cpu.py)."""
     from tests.test_multirank_gpu import run_ranks, stacked_k_rows, stacked_level_rows
