@@ -42,6 +42,7 @@ SYMBOLS = [
     "femshell_pool_stats", "femshell_amg_device_dense_inverse", "femshell_amg_dense_apply",
     "femshell_amg_device_block_jacobi", "femshell_block_jacobi_export", "femshell_block_jacobi_apply",
     "femshell_krylov_grid", "femshell_krylov_set", "femshell_krylov_get", "femshell_krylov_launch", "femshell_cg_reduce",
+    "femshell_modal_combine", "femshell_modal_residual", "femshell_modal_block_jacobi", "femshell_modal_mask", "femshell_modal_start",
 ]
 
 
@@ -243,6 +244,12 @@ def load_library():
     L.femshell_krylov_get.argtypes = [vp, C.c_int32, dp, C.c_int64]
     L.femshell_krylov_launch.argtypes = [vp, C.c_int32, ip, C.c_double, ip, dp]
     L.femshell_cg_reduce.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, dp, dp, C.POINTER(C.c_uint32)]
+    i64p = C.POINTER(C.c_int64)
+    L.femshell_modal_combine.argtypes = [vp, C.c_int32, ip, C.POINTER(dp), dp, C.c_int32, C.c_int32, dp, i64p]
+    L.femshell_modal_residual.argtypes = [vp, C.c_int32, dp, dp, dp, C.c_int32, ip, dp, dp, dp, i64p]
+    L.femshell_modal_block_jacobi.argtypes = [vp, C.c_int32, dp, dp, i64p]
+    L.femshell_modal_mask.argtypes = [vp, C.c_int32, dp, i64p]
+    L.femshell_modal_start.argtypes = [vp, C.c_int32, dp, i64p]
     for name in SYMBOLS:
         if name != "femshell_last_error" and not name.startswith("femshell_nnz") and \
                 not name.startswith("femshell_row") and name != "femshell_residual_history" and \
@@ -801,6 +808,66 @@ class FemShell:
         red, ticket = np.zeros(3), C.c_uint32(12345)
         _check(self._L.femshell_cg_reduce(self._h, int(n_partials), int(nsums), int(len3), _d(partials), _d(red), C.byref(ticket)))
         return red, int(ticket.value)
+
+    # ---- the block kernels of the eigen-solvers one launch at a time, for tests (femshell_modal_*, csrc/api_modal_probe.cpp)
+    def _block(self, X, name):
+        X = np.ascontiguousarray(X, dtype=np.float64)
+        X = X.reshape(len(X), -1)
+        if X.shape[1] != 6 * self.n_nodes:
+            raise ValueError("%s needs n_nodes x 6 entries per column" % name)
+        return X
+
+    def modal_combine(self, sources, Cm, n_out):
+        """Y = sum_k S_k C_k by k_block_combine: sources, up to three blocks (q_k, n_nodes * 6), None or empty for q_k = 0; Cm
+        (sum q_k, ldc) with ldc >= n_out, the rows of source k behind those of source k - 1.  Returns (Y (n_out, n_nodes * 6),
+        stray)."""
+        S = [None if s is None or len(s) == 0 else self._block(s, "a source") for s in sources]
+        q = np.array([0 if s is None else len(s) for s in S], dtype=np.int32)
+        Cm = np.ascontiguousarray(Cm, dtype=np.float64)
+        if Cm.ndim != 2 or Cm.shape[0] != int(q.sum()):
+            raise ValueError("Cm needs one row per source column")
+        ptrs = (C.POINTER(C.c_double) * 3)(*[_d(s) for s in S] + [None] * (3 - len(S)))
+        Y = np.zeros((max(int(n_out), 0), 6 * self.n_nodes))
+        stray = C.c_int64(-1)
+        _check(self._L.femshell_modal_combine(self._h, len(S), _i(q), ptrs, _d(Cm), Cm.shape[1], int(n_out), _d(Y), C.byref(stray)))
+        return Y, int(stray.value)
+
+    def modal_residual(self, KX, X, theta, cols):
+        """R_i = KX_c - theta[c] m o X_c, c = cols[i], by k_block_residual: KX, X (mb, n_nodes * 6), theta[mb].  Returns
+        (R (n, n_nodes * 6), norms[n], partials (n, 128) as the kernel left them, stray)."""
+        KX, X = self._block(KX, "KX"), self._block(X, "X")
+        theta = np.ascontiguousarray(theta, dtype=np.float64).reshape(-1)
+        cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+        if len(KX) != len(X) or len(theta) != len(X):
+            raise ValueError("KX, X and theta need the same number of columns")
+        n = len(cols)
+        R, norms, partials = np.zeros((n, 6 * self.n_nodes)), np.zeros(n), np.zeros((n, 128))
+        stray = C.c_int64(-1)
+        _check(self._L.femshell_modal_residual(self._h, len(X), _d(KX), _d(X), _d(theta), n, _i(cols), _d(R), _d(norms), _d(partials),
+                                               C.byref(stray)))
+        return R, norms, partials, int(stray.value)
+
+    def modal_block_jacobi(self, R):
+        """Z = D^-1 R, masked, by k_block_bj: R (n, n_nodes * 6).  Returns (Z, stray)."""
+        R = self._block(R, "R")
+        Z = np.zeros_like(R)
+        stray = C.c_int64(-1)
+        _check(self._L.femshell_modal_block_jacobi(self._h, len(R), _d(R), _d(Z), C.byref(stray)))
+        return Z, int(stray.value)
+
+    def modal_mask(self, X):
+        """mask(X) by k_block_mask: X (n, n_nodes * 6), left as it is.  Returns (the masked copy, stray)."""
+        X = self._block(X, "X").copy()
+        stray = C.c_int64(-1)
+        _check(self._L.femshell_modal_mask(self._h, len(X), _d(X), C.byref(stray)))
+        return X, int(stray.value)
+
+    def modal_start(self, n_cols):
+        """The start vectors of modes() by k_modal_init.  Returns (X (n_cols, n_nodes * 6), stray)."""
+        X = np.zeros((max(int(n_cols), 0), 6 * self.n_nodes))
+        stray = C.c_int64(-1)
+        _check(self._L.femshell_modal_start(self._h, int(n_cols), _d(X), C.byref(stray)))
+        return X, int(stray.value)
 
     def amg_patch_info(self):
         """The patch smoother of level 0 (csrc/amg_patch.hpp): rigid edges, clusters, nodes in them; all zero without rigid edges."""

@@ -414,6 +414,30 @@ int femshell_krylov_launch(femshell_ctx *ctx, int32_t step, const int32_t *args,
  * arrival counter behind the launch.  Needs no mesh. */
 int femshell_cg_reduce(femshell_ctx *ctx, int32_t n_partials, int32_t nsums, int32_t len3, const double *partials, double *red_out,
                        uint32_t *ticket_out);
+/* ---- For tests: the block kernels of the eigen-solvers one launch at a time (csrc/api_modal_probe.cpp): those
+ * of csrc/modal.hip that otherwise run only inside femshell_modes / femshell_buckling.  Each call uploads its blocks (columns of
+ * n_nodes x 6 doubles in the caller's numbering, one behind the other) into device buffers of its own, calls the production
+ * launcher once and downloads; nothing the context keeps is written, no production path runs through these.  Every output buffer
+ * is filled with bytes that read as NaN before the launch: a row the kernel does not write comes back as NaN.  *stray: the 8-byte
+ * words in the rows behind the owned ones (the padding of every output column) that are not +0.0 bit for bit.  One rank only
+ * (FEMSHELL_ERR_UNSUPPORTED for a row-partitioned context); FEMSHELL_ERR_INVALID without a mesh, the context as it was. */
+/* Y = sum_k S[k] C_k (k_block_combine): n_src (1 .. 3) sources of q[k] (0 .. 96, not all 0) columns, S[k] may be NULL where q[k] = 0;
+ * C: (sum q) x ldc row-major, the rows of source k behind those of source k - 1; Y: n_out (1 .. 64, <= ldc) columns. */
+int femshell_modal_combine(femshell_ctx *ctx, int32_t n_src, const int32_t *q, const double *const *S, const double *C, int32_t ldc,
+                           int32_t n_out, double *Y, int64_t *stray);
+/* R_i = KX_c - theta[c] m o X_c, c = cols[i], on the free dofs (k_block_residual, k_block_residual_sums; m: the lumped mass, so a
+ * density must be set): KX, X: mb (1 .. 96) columns, theta[mb], cols[n] (n 1 .. 96, each in 0 .. mb - 1).  R: n columns;
+ * norms[n]: sum r^2 / m; partials (may be NULL): n x 128, the partial sums of every column as the first kernel left them. */
+int femshell_modal_residual(femshell_ctx *ctx, int32_t mb, const double *KX, const double *X, const double *theta, int32_t n,
+                            const int32_t *cols, double *R, double *norms, double *partials, int64_t *stray);
+/* Z = D^-1 R masked on the constrained dofs (k_block_bj), n (1 .. 96) columns; assembles K and builds its block-Jacobi inverse
+ * where they are missing (the inverse femshell_block_jacobi_export shows at level 0).  Not while dynamics is active. */
+int femshell_modal_block_jacobi(femshell_ctx *ctx, int32_t n, const double *R, double *Z, int64_t *stray);
+/* X = mask(X) in place (k_block_mask), n (1 .. 96) columns */
+int femshell_modal_mask(femshell_ctx *ctx, int32_t n, double *X, int64_t *stray);
+/* the hashed start vectors of femshell_modes (k_modal_init), n_cols (1 .. 96) columns, with the node numbering femshell_modes
+ * passes: the context's permutation, or none */
+int femshell_modal_start(femshell_ctx *ctx, int32_t n_cols, double *X, int64_t *stray);
 /* The device-memory pool of this process as it stands (csrc/dev_pool.hpp; every buffer of every context comes out of it, so the
  * call takes no context and also answers after the last one was destroyed): out[0] = bytes the driver has handed out through
  * the pool and not got back, out[1] = bytes in use by buffers, out[2] = bytes kept for reuse (what FEMSHELL_POOL_GB bounds),

@@ -15,7 +15,9 @@ from tests.helpers.product import ROOT, ensure_built
 
 NU, E, T, RHO = 0.3, 2.1e5, 0.04, 7.8e-3
 
-NEW_NAMES = ["femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram"]
+NEW_NAMES = ["femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram",
+             # the block kernels one launch at a time, for tests (csrc/api_modal_probe.cpp)
+             "femshell_modal_combine", "femshell_modal_residual", "femshell_modal_block_jacobi", "femshell_modal_mask", "femshell_modal_start"]
 
 
 # ------------------------------------------------------------------ the reference against the closed form
@@ -130,7 +132,7 @@ def test_new_entry_points_are_declared_exported_and_bound():
     for k, name in ((8, "SPMM"), (9, "GRAM"), (10, "BLOCK_COMBINE")):
         assert re.search(r"FEMSHELL_KERNEL_%s\s*=\s*%d\b" % (name, k), header), name
         assert getattr(binding, "KERNEL_" + name) == k
-    for method in ("modes", "spmm", "modal_gram"):
+    for method in ("modes", "spmm", "modal_gram", "modal_combine", "modal_residual", "modal_block_jacobi", "modal_mask", "modal_start"):
         assert callable(getattr(pkg.FemShell, method, None)), method
     # the structures the binding mirrors have the C layout: 4 int32 + 2 doubles, 6 int32 + 7 doubles
     assert ctypes.sizeof(binding.ModalOptions) == 32 and ctypes.sizeof(binding.ModalInfo) == 80
