@@ -18,6 +18,7 @@ from .binding import (  # noqa: F401
     KERNEL_ELEMENT_LOADS,
     KERNEL_ELEMENT_PRODUCT,
     KERNEL_ELEMENT_RESULTANTS,
+    KERNEL_ELEMENT_THERMAL,
     KERNEL_GEOMETRIC_PRODUCT,
     KERNEL_SPMV,
     REASSEMBLE_EACH_SOLVE,

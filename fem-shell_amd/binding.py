@@ -22,6 +22,7 @@ KERNEL_ELEMENT_PRODUCT = 11
 KERNEL_ELEMENT_RESULTANTS = 12
 KERNEL_ELEMENT_LOADS = 13
 KERNEL_GEOMETRIC_PRODUCT = 14
+KERNEL_ELEMENT_THERMAL = 15
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -38,6 +39,7 @@ SYMBOLS = [
     "femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram",
     "femshell_set_prescribed", "femshell_reactions", "femshell_element_product", "femshell_element_resultants",
     "femshell_set_element_loads", "femshell_element_load_vector",
+    "femshell_set_expansion", "femshell_set_thermal", "femshell_thermal_load_vector",
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
     "femshell_pool_stats", "femshell_amg_device_dense_inverse", "femshell_amg_dense_apply",
     "femshell_amg_device_block_jacobi", "femshell_block_jacobi_export", "femshell_block_jacobi_apply",
@@ -230,6 +232,9 @@ def load_library():
     L.femshell_element_resultants.argtypes = [vp, dp, dp]
     L.femshell_set_element_loads.argtypes = [vp, dp, dp]
     L.femshell_element_load_vector.argtypes = [vp, dp]
+    L.femshell_set_expansion.argtypes = [vp, C.c_double, C.c_int32, dp]
+    L.femshell_set_thermal.argtypes = [vp, dp, dp]
+    L.femshell_thermal_load_vector.argtypes = [vp, dp]
     L.femshell_geometric_product.argtypes = [vp, dp, C.c_int32, dp, dp]
     L.femshell_buckling_defaults.argtypes = [C.POINTER(BucklingOptions)]
     L.femshell_buckling.argtypes = [vp, C.POINTER(BucklingOptions), dp, dp, dp, dp, C.POINTER(BucklingInfo)]
@@ -392,6 +397,36 @@ class FemShell:
         zeros when none are set (femshell_element_load_vector)."""
         f = np.zeros((self.n_nodes, 6))
         _check(self._L.femshell_element_load_vector(self._h, _d(f)))
+        return f
+
+    def set_expansion(self, alpha, section_alpha=None):
+        """Thermal expansion coefficient: one value for the whole shell, or section_alpha with one per section of set_sections
+        (femshell_set_expansion).  set_sections forgets it, and the temperatures with it."""
+        if section_alpha is None:
+            _check(self._L.femshell_set_expansion(self._h, float(alpha), 0, None))
+            return
+        sa = np.ascontiguousarray(section_alpha, dtype=np.float64).ravel()
+        _check(self._L.femshell_set_expansion(self._h, 0.0, len(sa), _d(sa)))
+
+    def set_thermal(self, tri_temp=None, quad_temp=None):
+        """Temperatures per element (femshell_set_thermal): tri_temp is (n_tri, 2), quad_temp (n_quad, 2), rows (Tm, Tg) in the
+        element order of set_mesh -- Tm the temperature change of the mid-surface, Tg = T_top - T_bottom with the top at +t/2
+        along the element's own normal.  None for one kind leaves it cold, both None clears.  The loads in force are
+        (nodal + element loads) + the work-equivalent thermal loads; element_resultants, geometric_product and buckling see the
+        stress state of the heated shell.  Needs set_expansion first."""
+        tt = None if tri_temp is None else np.ascontiguousarray(tri_temp, dtype=np.float64).reshape(-1, 2)
+        qt = None if quad_temp is None else np.ascontiguousarray(quad_temp, dtype=np.float64).reshape(-1, 2)
+        if tt is not None and len(tt) != self.n_tri:
+            raise ValueError("tri_temp needs one row per triangle (%d), got %d" % (self.n_tri, len(tt)))
+        if qt is not None and len(qt) != self.n_quad:
+            raise ValueError("quad_temp needs one row per quadrilateral (%d), got %d" % (self.n_quad, len(qt)))
+        _check(self._L.femshell_set_thermal(self._h, _d(tt), _d(qt)))
+
+    def thermal_load_vector(self):
+        """T, (n_nodes, 6): the nodal equivalents of the temperatures in force alone, in the caller's numbering, not masked;
+        zeros when none are set (femshell_thermal_load_vector)."""
+        f = np.zeros((self.n_nodes, 6))
+        _check(self._L.femshell_thermal_load_vector(self._h, _d(f)))
         return f
 
     def set_sections(self, sections, tri_section=None, quad_section=None):

@@ -746,8 +746,11 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     c->have_sections = false; // (the element count may change)
     c->n_sections = 0;
     c->sec_thickness.clear();
+    c->sec_nu.clear();
+    c->sec_E.clear();
     forget_density(c);
     forget_element_loads(c); // (per element of the previous mesh; kNodeCleared below zeroes the loads)
+    forget_thermal(c);       // (... and the temperatures and alpha with them)
     c->dyn.reset(); // (a new mesh ends dynamics)
     c->have_prescribed = c->ubar_nonzero = false; // (... and forgets the prescribed displacements)
     c->prescribed_global.clear();
@@ -1075,6 +1078,8 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
     std::string err;
     if (n_sections == 0) {
         forget_density(c);
+        rc = thermal_forget_and_restore(c); // (alpha belongs to the sections like the densities, the temperatures to alpha)
+        if (rc) return rc;
         invalidate(c, Change::sections_cleared_none_set);
         if (!c->have_sections) return FEMSHELL_OK; // nothing was set: nothing else changes
         if (c->pipe_without_sections && !p.pipe) { // back to the layout femshell_set_mesh chose: K is again what it was, bit for bit
@@ -1088,6 +1093,8 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
         c->have_sections = false;
         c->n_sections = 0;
         c->sec_thickness.clear();
+        c->sec_nu.clear();
+        c->sec_E.clear();
         c->ds = DeviceSections();
         c->sec_table.release();
         c->slice_elem_section.release();
@@ -1141,8 +1148,16 @@ int femshell_set_sections(femshell_ctx *c, int32_t n_sections, const femshell_se
     c->n_sections = n_sections;
     c->have_sections = true;
     c->sec_thickness.resize((size_t)n_sections);
-    for (int32_t s = 0; s < n_sections; s++) c->sec_thickness[(size_t)s] = sections[s].thickness;
+    c->sec_nu.resize((size_t)n_sections);
+    c->sec_E.resize((size_t)n_sections);
+    for (int32_t s = 0; s < n_sections; s++) {
+        c->sec_thickness[(size_t)s] = sections[s].thickness;
+        c->sec_nu[(size_t)s] = sections[s].nu;
+        c->sec_E[(size_t)s] = sections[s].E;
+    }
     forget_density(c); // (paired with the sections that were replaced)
+    rc = thermal_forget_and_restore(c); // (... and so are alpha and, with it, the temperatures: the loads are nodal + S again)
+    if (rc) return rc;
     invalidate(c, Change::sections);
     return FEMSHELL_OK;
 }

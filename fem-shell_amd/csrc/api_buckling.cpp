@@ -48,7 +48,8 @@ int geometric_coefficients(femshell_ctx *c, const double *u, DevBuf<double> *coe
     if (rc) return rc;
     FS_HIP(res.alloc(std::max<size_t>(ne, 1) * 14));
     FS_HIP(coeff->alloc(std::max<size_t>(ne, 1) * (size_t)geometric_coeff_words(c->dm)));
-    launch_element_resultants(c->dm, c->mc, c->sections_or_null(), sec_t, ux, up, res.p, c->stream);
+    ThermalView tv; // (temperatures in force: the membrane forces of the heated shell, through the same switch as the resultants)
+    launch_element_resultants(c->dm, c->mc, c->sections_or_null(), sec_t, ux, up, res.p, c->stream, thermal_view_or_null(c, &tv));
     launch_geometric_coeff(c->dm, res.p, coeff->p, c->stream);
     FS_HIP(hipGetLastError());
     return check_status(c, what); // (synchronises: x, res and the staging copy go out of scope)

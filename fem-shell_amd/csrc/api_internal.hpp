@@ -1,6 +1,6 @@
 // api_internal.hpp -- what the files of the C ABI share: api.cpp (context, mesh and its data, solve, export, products), api_state.cpp
 // (what of the context's derived state is valid, and the functions that make it so), api_dynamics.cpp, api_modal.cpp,
-// api_resultants.cpp, api_timing.cpp.  Not for the rest of the library.  Each function is described where it is defined: api.cpp, but
+// api_resultants.cpp, api_element_loads.cpp, api_thermal.cpp, api_timing.cpp.  Not for the rest of the library.  Each function is described where it is defined: api.cpp, but
 // for the block from invalidate to timed_assembly_done (api_state.cpp), the byte models of the hot-path kernels (api_timing.cpp)
 // and what api_resultants.cpp shares with the timing hook.
 #pragma once
@@ -45,6 +45,14 @@ int ensure_slice_elem_local(femshell_ctx *c);
 int combine_loads(femshell_ctx *c);
 int element_loads_apply(femshell_ctx *c, const RawVec<double> &rows);
 int element_loads_clear(femshell_ctx *c);
+// thermal loads (api_state.cpp): c->loads holds (nodal + S) + T; the same buffers and the same chain
+void forget_thermal(femshell_ctx *c);
+int thermal_forget_and_restore(femshell_ctx *c);
+int expansion_apply(femshell_ctx *c, double alpha, int32_t n_sections, const double *section_alpha);
+int thermal_apply(femshell_ctx *c, const RawVec<double> &rows);
+int thermal_clear(femshell_ctx *c);
+ThermalView thermal_view(const femshell_ctx *c);
+const ThermalView *thermal_view_or_null(const femshell_ctx *c, ThermalView *store);
 
 double bytes_assemble(const femshell_ctx *c);
 double bytes_spmv(const femshell_ctx *c);
@@ -54,6 +62,8 @@ double bytes_update_single_reduction(const femshell_ctx *c);
 double bytes_element_resultants(const femshell_ctx *c);
 double bytes_element_loads(const femshell_ctx *c);
 int time_element_loads(femshell_ctx *c, int32_t reps, double *mean_ms_out);
+double bytes_element_thermal(const femshell_ctx *c);
+int time_element_thermal(femshell_ctx *c, int32_t reps, double *mean_ms_out);
 double bytes_geometric_product(const femshell_ctx *c, int cols);
 int time_geometric_product(femshell_ctx *c, int32_t reps, double *mean_ms_out);
 int geometric_coefficients(femshell_ctx *c, const double *u, DevBuf<double> *coeff, const char *what);

@@ -64,7 +64,8 @@ int femshell_element_resultants(femshell_ctx *c, const double *u, double *out)
     rc = upload_section_thickness(c, &thick, &sec_t);
     if (rc) return rc;
     FS_HIP(res.alloc(ne * 14));
-    launch_element_resultants(c->dm, c->mc, c->sections_or_null(), sec_t, ux, up, res.p, c->stream);
+    ThermalView tv; // (temperatures in force: the thermal instantiations, N = t Dm (eps - eps0), M = -Dp (kappa - kappa0))
+    launch_element_resultants(c->dm, c->mc, c->sections_or_null(), sec_t, ux, up, res.p, c->stream, thermal_view_or_null(c, &tv));
     FS_HIP(hipGetLastError());
     rc = check_status(c, "femshell_element_resultants");
     if (rc) return rc;

@@ -1,7 +1,7 @@
 // api_state.cpp -- the derived state of a context (derived.hpp): the one place that says what is valid.
 // invalidate() applies the table of derived.hpp after a change, the functions below it make a product valid, ensure() brings
 // what an entry point needs up to date, have() answers for the entry points that refuse instead.  No other file assigns to
-// matrix_valid, rhs_valid, jacobi_valid, mass_valid, ubar_valid, have_element_loads or amg_fp64_only or drops the hierarchy; have_solution and
+// matrix_valid, rhs_valid, jacobi_valid, mass_valid, ubar_valid, have_element_loads, have_alpha, have_thermal or amg_fp64_only or drops the hierarchy; have_solution and
 // warm_next are set where a solve and a hand-over produce them (api.cpp, api_dynamics.cpp) and cleared here only.
 #include "api_internal.hpp"
 
@@ -69,19 +69,37 @@ void forget_density(femshell_ctx *c)
 // the nodal part lies beside it in c->loads_nodal, and whoever rewrites the nodal loads writes there (nodal_loads_buffer) and
 // calls combine_loads.
 
+// Temperatures (femshell_set_thermal, api_thermal.cpp) add T, the work-equivalent loads of the free thermal state: c->loads holds
+// (nodal + S) + T, one rounding per +.  The nodal part lies in c->loads_nodal while either is in force; where both are, the two
+// kernels chain through c->loads_mech = nodal + S.
+
 // femshell_set_mesh forgets the element loads: the flag, their buffers and the map of the previous mesh's lists
 void forget_element_loads(femshell_ctx *c)
 {
     c->have_element_loads = false;
     c->loads_nodal.release();
+    c->loads_mech.release();
     c->elem_load.release();
     c->slice_elem_local.release();
+}
+
+// ... and the temperatures and alpha (the loads are zeroed by the mesh: nothing to restore)
+void forget_thermal(femshell_ctx *c)
+{
+    c->have_thermal = false;
+    c->have_alpha = false;
+    c->alpha = 0.0;
+    c->sec_alpha.clear();
+    c->elem_temp.release();
+    c->loads_mech.release();
+    c->sec_thermal.release();
+    if (!c->have_element_loads) c->loads_nodal.release();
 }
 
 // where an upload of the nodal loads goes (n_pad x 6, allocated here)
 int nodal_loads_buffer(femshell_ctx *c, double **buf)
 {
-    DevBuf<double> &b = c->have_element_loads ? c->loads_nodal : c->loads;
+    DevBuf<double> &b = (c->have_element_loads || c->have_thermal) ? c->loads_nodal : c->loads;
     FS_HIP(b.alloc((size_t)c->plan.n_pad * 6));
     *buf = b.p;
     return FEMSHELL_OK;
@@ -95,12 +113,76 @@ int ensure_slice_elem_local(femshell_ctx *c)
     return FEMSHELL_OK;
 }
 
-// c->loads = nodal + S, one launch; nothing without element loads (c->loads is the nodal part itself then)
+// the factors of a material with expansion alpha (kernels.hpp ThermalSec): tcm = t E / (1 - nu^2), cp = E t^3 / (12 (1 - nu^2))
+static ThermalSec thermal_factors(double tcm, double cp, double nu, double t, double alpha)
+{
+    ThermalSec r;
+    r.nt = tcm * (1.0 + nu) * alpha;
+    r.mt = cp * (1.0 + nu) / t * alpha;
+    r.alpha = alpha;
+    r.alpha_t = alpha / t;
+    return r;
+}
+
+// what the kernels get of the temperatures in force
+ThermalView thermal_view(const femshell_ctx *c)
+{
+    ThermalView tv;
+    tv.elem_temp = reinterpret_cast<const double2 *>(c->elem_temp.p);
+    tv.uni = thermal_factors(c->mc.t * c->mc.cm, c->mc.cp, c->mc.nu, c->mc.t, c->alpha);
+    tv.sec = c->have_sections ? c->sec_thermal.p : nullptr;
+    return tv;
+}
+const ThermalView *thermal_view_or_null(const femshell_ctx *c, ThermalView *store)
+{
+    if (!c->have_thermal) return nullptr;
+    *store = thermal_view(c);
+    return store;
+}
+
+// c->loads = (nodal + S) + T, a launch each; nothing with neither in force (c->loads is the nodal part itself then)
 int combine_loads(femshell_ctx *c)
 {
-    if (!c->have_element_loads) return FEMSHELL_OK;
-    launch_element_loads(c->dm, c->slice_elem_local.p, c->elem_load.p, c->loads_nodal.p, c->loads.p, c->stream);
+    if (!c->have_element_loads && !c->have_thermal) return FEMSHELL_OK;
+    const double *src = c->loads_nodal.p;
+    if (c->have_element_loads) {
+        double *dst = c->loads.p;
+        if (c->have_thermal) {
+            FS_HIP(c->loads_mech.alloc((size_t)c->plan.n_pad * 6));
+            dst = c->loads_mech.p;
+        }
+        launch_element_loads(c->dm, c->slice_elem_local.p, c->elem_load.p, src, dst, c->stream);
+        src = dst;
+    }
+    if (c->have_thermal) launch_element_thermal(c->dm, c->slice_elem_local.p, c->ds.slice_elem_section, thermal_view(c), src, c->loads.p, c->stream);
     FS_HIP(hipGetLastError());
+    return FEMSHELL_OK;
+}
+
+// the first of the two that takes force moves the nodal part aside inside HBM
+static int move_nodal_aside(femshell_ctx *c)
+{
+    if (c->have_element_loads || c->have_thermal) return FEMSHELL_OK;
+    const size_t n6 = (size_t)c->plan.n_pad * 6;
+    FS_HIP(c->loads_nodal.alloc(n6));
+    if (n6) FS_HIP(hipMemcpyAsync(c->loads_nodal.p, c->loads.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return FEMSHELL_OK;
+}
+
+// one of the two left force: the chain again, or, with neither left, the nodal part back into c->loads.  Synchronises.
+static int loads_after_clear(femshell_ctx *c)
+{
+    c->loads_mech.release();
+    if (c->have_element_loads || c->have_thermal) {
+        const int rc = combine_loads(c);
+        if (rc) return rc;
+        FS_HIP(hipStreamSynchronize(c->stream));
+        return FEMSHELL_OK;
+    }
+    const size_t n6 = (size_t)c->plan.n_pad * 6;
+    if (n6) FS_HIP(hipMemcpyAsync(c->loads.p, c->loads_nodal.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    FS_HIP(hipStreamSynchronize(c->stream));
+    c->loads_nodal.release();
     return FEMSHELL_OK;
 }
 
@@ -108,14 +190,11 @@ int combine_loads(femshell_ctx *c)
 // aside inside HBM; no set uploads it again.  Returns after the upload of `rows` has completed.
 int element_loads_apply(femshell_ctx *c, const RawVec<double> &rows)
 {
-    const size_t n6 = (size_t)c->plan.n_pad * 6;
     hipStream_t st = c->stream;
     int rc = ensure_slice_elem_local(c);
     if (rc) return rc;
-    if (!c->have_element_loads) {
-        FS_HIP(c->loads_nodal.alloc(n6));
-        if (n6) FS_HIP(hipMemcpyAsync(c->loads_nodal.p, c->loads.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
+    rc = move_nodal_aside(c);
+    if (rc) return rc;
     FS_HIP(c->elem_load.upload(rows, st));
     c->have_element_loads = true;
     rc = combine_loads(c);
@@ -125,17 +204,86 @@ int element_loads_apply(femshell_ctx *c, const RawVec<double> &rows)
     return FEMSHELL_OK;
 }
 
-// no element loads any more: the nodal part goes back into c->loads
+// no element loads any more: the loads are nodal + T, or the nodal part goes back into c->loads
 int element_loads_clear(femshell_ctx *c)
 {
     if (!c->have_element_loads) return FEMSHELL_OK;
-    const size_t n6 = (size_t)c->plan.n_pad * 6;
-    if (n6) FS_HIP(hipMemcpyAsync(c->loads.p, c->loads_nodal.p, n6 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    FS_HIP(hipStreamSynchronize(c->stream));
     c->have_element_loads = false;
-    c->loads_nodal.release();
+    const int rc = loads_after_clear(c);
+    if (rc) return rc;
     c->elem_load.release();
     invalidate(c, Change::loads);
+    return FEMSHELL_OK;
+}
+
+// femshell_set_expansion, checked: alpha for every element, or one per section.  The factors of the sections go to HBM; where
+// temperatures are in force the loads follow.
+int expansion_apply(femshell_ctx *c, double alpha, int32_t n_sections, const double *section_alpha)
+{
+    hipStream_t st = c->stream;
+    if (c->have_sections) {
+        std::vector<ThermalSec> table((size_t)c->n_sections);
+        for (int32_t s = 0; s < c->n_sections; s++) {
+            const double nu = c->sec_nu[(size_t)s], E = c->sec_E[(size_t)s], t = c->sec_thickness[(size_t)s];
+            table[(size_t)s] = thermal_factors(t * (E / (1.0 - nu * nu)), E * t * t * t / (12.0 * (1.0 - nu * nu)), nu, t,
+                                               n_sections > 0 ? section_alpha[s] : alpha);
+        }
+        FS_HIP(hipStreamSynchronize(st)); // (a launch in flight reads the table that is replaced)
+        FS_HIP(c->sec_thermal.upload(table, st));
+        FS_HIP(hipStreamSynchronize(st)); // the host table goes out of scope
+    }
+    c->alpha = n_sections > 0 ? 0.0 : alpha;
+    if (n_sections > 0) c->sec_alpha.assign(section_alpha, section_alpha + n_sections);
+    else c->sec_alpha.clear();
+    c->have_alpha = true;
+    if (c->have_thermal) {
+        const int rc = combine_loads(c);
+        if (rc) return rc;
+        FS_HIP(hipStreamSynchronize(st));
+        invalidate(c, Change::loads);
+    }
+    return FEMSHELL_OK;
+}
+
+// rows: (Tm, Tg) per local element, which take force in place of the previous set: 16 bytes per local element go to HBM, the
+// nodal loads are not uploaded again.  Returns after the upload of `rows` has completed.
+int thermal_apply(femshell_ctx *c, const RawVec<double> &rows)
+{
+    hipStream_t st = c->stream;
+    int rc = ensure_slice_elem_local(c);
+    if (rc) return rc;
+    rc = move_nodal_aside(c);
+    if (rc) return rc;
+    FS_HIP(c->elem_temp.upload(rows, st));
+    c->have_thermal = true;
+    rc = combine_loads(c);
+    if (rc) return rc;
+    FS_HIP(hipStreamSynchronize(st));
+    invalidate(c, Change::loads);
+    return FEMSHELL_OK;
+}
+
+// no temperatures any more: the loads are nodal + S again
+int thermal_clear(femshell_ctx *c)
+{
+    if (!c->have_thermal) return FEMSHELL_OK;
+    c->have_thermal = false;
+    const int rc = loads_after_clear(c);
+    if (rc) return rc;
+    c->elem_temp.release();
+    invalidate(c, Change::loads);
+    return FEMSHELL_OK;
+}
+
+// femshell_set_sections forgets alpha, which belongs to the sections as the densities do, and with it the temperatures
+int thermal_forget_and_restore(femshell_ctx *c)
+{
+    const int rc = thermal_clear(c);
+    if (rc) return rc;
+    c->have_alpha = false;
+    c->alpha = 0.0;
+    c->sec_alpha.clear();
+    c->sec_thermal.release();
     return FEMSHELL_OK;
 }
 

@@ -206,6 +206,13 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         if (bytes_out) *bytes_out = bytes_element_loads(c);
         return FEMSHELL_OK;
     }
+    if (which == FEMSHELL_KERNEL_ELEMENT_THERMAL) {
+        // hashed temperatures from the loads in force into a scratch vector (api_thermal.cpp): every rank times its own rows
+        rc = time_element_thermal(c, reps, mean_ms_out);
+        if (rc) return rc;
+        if (bytes_out) *bytes_out = bytes_element_thermal(c);
+        return FEMSHELL_OK;
+    }
     if (which == FEMSHELL_KERNEL_GEOMETRIC_PRODUCT) {
         // one pass of four columns on hashed coefficients and vectors (api_buckling.cpp)
         if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_time_kernel: the geometric product runs on single-rank contexts");

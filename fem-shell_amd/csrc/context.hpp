@@ -129,6 +129,7 @@ struct femshell_ctx {
     // structural dynamics (femshell_set_density, femshell_dynamics_*).  The densities are the caller's; the diagonal of the lumped
     // mass matrix lies in HBM (owned rows, internal numbering) once it has been asked for, until mesh, sections or density change.
     std::vector<double> sec_thickness; // thickness of every section (the table in HBM keeps products only)
+    std::vector<double> sec_nu, sec_E; // ... and its material, for what is derived from a section later (the thermal factors)
     bool have_density = false, mass_valid = false;
     double rho = 0.0;
     std::vector<double> sec_rho;       // per section, or empty: rho for every element
@@ -168,6 +169,16 @@ struct femshell_ctx {
     bool have_element_loads = false;
     femshell::DevBuf<double> loads_nodal, elem_load;
     femshell::DevBuf<int32_t> slice_elem_local;
+    // thermal loads (femshell_set_expansion, femshell_set_thermal): alpha of the uniform material or one per
+    // section (sec_alpha, else empty), and while temperatures are in force elem_temp, (Tm, Tg) per LOCAL element.  `loads` then
+    // holds (nodal + S) + T: the nodal part lies in loads_nodal as with element loads, and where both are in force the kernels
+    // chain through loads_mech = nodal + S.  sec_thermal: the factors of every section in HBM (contexts with sections, from
+    // femshell_set_expansion on).  (have_alpha and have_thermal are written by api_state.cpp only.)
+    bool have_alpha = false, have_thermal = false;
+    double alpha = 0.0;
+    std::vector<double> sec_alpha;
+    femshell::DevBuf<double> elem_temp, loads_mech;
+    femshell::DevBuf<femshell::ThermalSec> sec_thermal;
     // CG state
     femshell::DevBuf<double> x, r, z, p, q, sv, partials, hist, sendbuf, ufull;
     femshell::DevBuf<double> xacc, rres; // iterative refinement of the multigrid-preconditioned solve: accumulated solution, residual

@@ -28,7 +28,8 @@ enum class Change : int32_t {
     dirichlet,                 // femshell_set_dirichlet
     sections,                  // femshell_set_sections: set, or cleared when some were set
     sections_cleared_none_set, // ... cleared when none were set: the densities are forgotten all the same
-    loads,                     // femshell_set_loads
+    loads,                     // femshell_set_loads, femshell_set_element_loads; femshell_set_thermal / femshell_set_expansion
+                               // changed the temperatures in force, or they were forgotten: temperatures are loads
     prescribed,                // femshell_set_prescribed: set or cleared
     density,                   // femshell_set_density
     pc_options,                // femshell_set_preconditioner, unless only the refinement passes changed

@@ -355,13 +355,123 @@ __global__ __launch_bounds__(kErThreads) void k_element_resultants(DeviceMatrix 
     }
 }
 
+// The same kernel while temperatures are in force: the element means lose the free thermal state before the material
+// is applied, N_loc = t Dm (eps - eps0), M_loc = -Dp (kappa - kappa0), from the element's (Tm, Tg) and the expansion of its section
+// (tv).  A kernel of its own, so that k_element_resultants above stays the code it was -- the only one launched when nothing is set.
+template <bool kHasQuads, bool kSections>
+__global__ __launch_bounds__(kErThreads) void k_element_resultants_thermal(DeviceMatrix m, MatConst mc, DeviceSections ds,
+                                                                          const double *__restrict__ sec_t, const double *__restrict__ u,
+                                                                          const double *__restrict__ up, ThermalView tv, double *__restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) double s_out[kErThreads * kErWords];
+    const int n = m.n_ltri + (kHasQuads ? m.n_lquad : 0);
+    const int64_t e64 = (int64_t)blockIdx.x * kErThreads + threadIdx.x;
+    double res[kErWords];
+#pragma unroll
+    for (int q = 0; q < kErWords; q++) res[q] = 0.0;
+    if (e64 < n) {
+        const int e = (int)e64;
+        ElemMeans f;
+        bool ok;
+        if (!kHasQuads || e < m.n_ltri) {
+            const int32_t *c = m.tri + 3 * (int64_t)e;
+            const int nid[3] = {c[0], c[1], c[2]};
+            double X[9], U[3][6];
+#pragma unroll
+            for (int i = 0; i < 3; i++) {
+                const double *pt = m.xyz + 3 * (int64_t)nid[i];
+                X[3 * i + 0] = pt[0];
+                X[3 * i + 1] = pt[1];
+                X[3 * i + 2] = pt[2];
+                gather_u(u, up, nid[i], U[i]);
+            }
+            ok = tri3_means(X, U, mc.flags, f);
+        } else {
+            const int4 c = reinterpret_cast<const int4 *>(m.quad)[e - m.n_ltri];
+            const int nid[4] = {c.x, c.y, c.z, c.w};
+            double X[12], U[4][6];
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const double *pt = m.xyz + 3 * (int64_t)nid[i];
+                X[3 * i + 0] = pt[0];
+                X[3 * i + 1] = pt[1];
+                X[3 * i + 2] = pt[2];
+                gather_u(u, up, nid[i], U[i]);
+            }
+            // coordinates relative to the first node, each difference rounded once: quad4_means projects the coordinates it is
+            // given onto the frame and differences the projections, which at a distance D from the origin costs D / size digits
+#pragma unroll
+            for (int i = 3; i >= 0; i--)
+#pragma unroll
+                for (int d = 0; d < 3; d++) X[3 * i + d] -= X[d];
+            ok = quad4_means(X, U, f);
+        }
+        double tcm = mc.t * mc.cm, cp = mc.cp, nu = mc.nu, g = mc.g, t = mc.t;
+        if (kSections) { // the element's own material
+            const int si = ds.elem_section[e];
+            const SecConst sc = fetch_section(ds.table, si);
+            tcm = sc.tcm;
+            cp = sc.cp;
+            nu = sc.nu;
+            g = sc.g;
+            t = sec_t[si];
+        }
+        { // the free thermal state leaves: eps0 = alpha Tm (1,1,0), kappa0 = -(alpha Tg / t) (1,1,0)
+            const double2 tmp = tv.elem_temp[e];
+            double2 al = make_double2(tv.uni.alpha, tv.uni.alpha_t);
+            if (kSections) al = reinterpret_cast<const double2 *>(tv.sec + ds.elem_section[e])[1];
+            const double e0 = al.x * tmp.x, k0 = -al.y * tmp.y;
+            f.eps[0] -= e0;
+            f.eps[1] -= e0;
+            f.kap[0] -= k0;
+            f.kap[1] -= k0;
+        }
+        double val[kErWords];
+        finish_element(f, tcm, cp, nu, g, t, val);
+#pragma unroll
+        for (int q = 0; q < kErWords; q++) res[q] = ok ? val[q] : 0.0; // (selects: a degenerate element's values may be Inf / NaN)
+        if (!ok) report_status(m.status, kStatusDirect + e);
+    }
+    // the lane's row into LDS, then the wave's rows out as contiguous 16-byte words
+    {
+        double2 *row = reinterpret_cast<double2 *>(s_out + (size_t)threadIdx.x * kErWords);
+#pragma unroll
+        for (int q = 0; q < kErWords / 2; q++) row[q] = make_double2(res[2 * q], res[2 * q + 1]);
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t first = (int64_t)blockIdx.x * kErThreads + 64 * wave; // first element of this wave
+    const int64_t left = (int64_t)n - first;
+    const int words = (int)(left < 0 ? 0 : (left > 64 ? 64 : left)) * (kErWords / 2); // 16-byte words of the wave's valid rows
+    const double2 *src = reinterpret_cast<const double2 *>(s_out + (size_t)wave * 64 * kErWords);
+    double2 *dst = reinterpret_cast<double2 *>(out + first * kErWords);
+#pragma unroll
+    for (int q = 0; q < kErWords / 2; q++) {
+        const int w = 64 * q + lane;
+        if (w < words) dst[w] = src[w];
+    }
+}
+
 void launch_element_resultants(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const double *sec_t, const double *u,
-                               const double *up, double *out, hipStream_t st)
+                               const double *up, double *out, hipStream_t st, const ThermalView *thermal)
 {
     const int64_t n = (int64_t)m.n_ltri + m.n_lquad;
     if (n == 0) return;
     const DeviceSections ds = sections ? *sections : DeviceSections();
     const unsigned g = (unsigned)((n + kErThreads - 1) / kErThreads);
+    if (thermal) {
+        const ThermalView tv = *thermal;
+        auto launch_t = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(g), dim3(kErThreads), 0, st, m, mc, ds, sec_t, u, up, tv, out); };
+        if (sections) {
+            if (m.n_lquad > 0) launch_t(k_element_resultants_thermal<true, true>);
+            else launch_t(k_element_resultants_thermal<false, true>);
+        } else if (m.n_lquad > 0) {
+            launch_t(k_element_resultants_thermal<true, false>);
+        } else {
+            launch_t(k_element_resultants_thermal<false, false>);
+        }
+        return;
+    }
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(g), dim3(kErThreads), 0, st, m, mc, ds, sec_t, u, up, out); };
     if (sections) { // (the instantiations with sections: contexts without never launch them)
         if (m.n_lquad > 0) launch(k_element_resultants<true, true>);

@@ -195,8 +195,32 @@ void launch_element_product(const DeviceMatrix &m, const MatConst &mc, const Dev
 // (n_pad + n_ghost) x 6; up may be nullptr).  sec_t: the thickness of every section where `sections` is given (its table keeps
 // products only), nullptr otherwise.  One lane per element, no atomics: two launches give the same bits.  A degenerate element
 // writes zeros and reports kStatusDirect + its index through m.status.
+// thermal != nullptr: temperatures are in force: N_loc = t Dm (eps - eps0), M_loc = -Dp (kappa - kappa0) with the
+// element's (Tm, Tg) and alpha -- the thermal instantiations of the kernel; nullptr launches the instantiations without, untouched.
+struct ThermalView;
 void launch_element_resultants(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const double *sec_t, const double *u,
-                               const double *up, double *out, hipStream_t st);
+                               const double *up, double *out, hipStream_t st, const ThermalView *thermal = nullptr);
+
+// Thermal loads (element_thermal.hip).  What the kernels take from a material and its expansion coefficient: the
+// factors of the equivalent loads, N_T = nt Tm and M_T = mt Tg, and of the free state, eps0 = alpha Tm, kappa0 = -alpha_t Tg.
+// 32 bytes: each kernel reads its half of a row as one 16-byte word.
+struct ThermalSec {
+    double nt;      // E t alpha / (1 - nu)
+    double mt;      // E t^2 alpha / (12 (1 - nu))
+    double alpha;
+    double alpha_t; // alpha / t
+};
+struct ThermalView {
+    const double2 *elem_temp = nullptr; // (Tm, Tg) per LOCAL element (triangles, then quadrilaterals)
+    ThermalSec uni{};                   // the context's uniform material
+    const ThermalSec *sec = nullptr;    // per section, or nullptr: uni for every element
+};
+// out[n_pad][6] = base + T on all six components of the owned rows, zero on padding rows; base == nullptr: zero.  T_a: the
+// work-equivalent nodal loads of the free thermal state of the elements that contain row a, added in the order of the slice's
+// list from zero, no atomics: two launches give the same bits at every grid size.  slice_elem_local as for launch_element_loads;
+// slice_elem_section: the section of every entry of the lists where tv.sec is given.  base may not be out.
+void launch_element_thermal(const DeviceMatrix &m, const int32_t *slice_elem_local, const int32_t *slice_elem_section, const ThermalView &tv,
+                            const double *base, double *out, hipStream_t st);
 
 // Nodal equivalents of per-element pressure and traction (element_loads.hip): out[n_pad][6] = base + S on the
 // translations of the owned rows, base on their rotations, zero on padding rows; base == nullptr: zero.  elem_load: four doubles

@@ -118,6 +118,104 @@ static void read_element_loads(Parameters &p)
     }
 }
 
+// -thermal FILE into p.thermal_*: the conventions of the -element_loads reader
+static void read_thermal(Parameters &p)
+{
+    std::ifstream in(p.thermal_file);
+    if (!in) throw std::runtime_error("cannot open " + p.thermal_file);
+    p.thermal_elems.clear();
+    p.thermal_lines.clear();
+    p.thermal_values.clear();
+    std::string line;
+    for (int no = 1; std::getline(in, line); no++) {
+        const size_t h = line.find('#');
+        if (h != std::string::npos) line.erase(h);
+        std::istringstream is(line);
+        std::string first;
+        if (!(is >> first)) continue; // blank or comment
+        const std::string where = p.thermal_file + ": line " + std::to_string(no) + ": ";
+        char *end = nullptr;
+        const long elem = std::strtol(first.c_str(), &end, 10);
+        double v[2];
+        std::string rest;
+        if (*end != '\0' || !(is >> v[0] >> v[1]) || (is >> rest)) throw std::runtime_error(where + "expected 'elem Tm Tg'");
+        for (double x : v)
+            if (!std::isfinite(x)) throw std::runtime_error(where + "a value is not finite");
+        if (elem < 0 || elem > 2147483647L) throw std::runtime_error(where + "element index " + first + " is out of range");
+        p.thermal_elems.push_back((int32_t)elem);
+        p.thermal_lines.push_back(no);
+        p.thermal_values.insert(p.thermal_values.end(), v, v + 2);
+    }
+}
+
+// -section_alpha FILE into p.section_alpha_*: lines 'tag alpha'
+static void read_section_alpha(Parameters &p)
+{
+    std::ifstream in(p.section_alpha_file);
+    if (!in) throw std::runtime_error("cannot open " + p.section_alpha_file);
+    p.section_alpha_tags.clear();
+    p.section_alpha_lines.clear();
+    p.section_alpha_values.clear();
+    std::string line;
+    for (int no = 1; std::getline(in, line); no++) {
+        const size_t h = line.find('#');
+        if (h != std::string::npos) line.erase(h);
+        std::istringstream is(line);
+        std::string first;
+        if (!(is >> first)) continue; // blank or comment
+        const std::string where = p.section_alpha_file + ": line " + std::to_string(no) + ": ";
+        char *end = nullptr;
+        const long tag = std::strtol(first.c_str(), &end, 10);
+        double a = 0.0;
+        std::string rest;
+        if (*end != '\0' || !(is >> a) || (is >> rest)) throw std::runtime_error(where + "expected 'tag alpha'");
+        if (!std::isfinite(a)) throw std::runtime_error(where + "a value is not finite");
+        if (std::find(p.section_alpha_tags.begin(), p.section_alpha_tags.end(), (int32_t)tag) != p.section_alpha_tags.end())
+            throw std::runtime_error(where + "tag " + first + " is listed twice");
+        p.section_alpha_tags.push_back((int32_t)tag);
+        p.section_alpha_lines.push_back(no);
+        p.section_alpha_values.push_back(a);
+    }
+}
+
+ThermalLoads build_thermal_loads(const Parameters &p, const ShellMesh &mesh, const SectionTable *sections)
+{
+    const size_t ne = mesh.order.size();
+    std::vector<double> rows(2 * ne, 0.0); // mesh-file order
+    std::vector<uint8_t> listed(ne, 0);
+    for (size_t i = 0; i < p.thermal_elems.size(); i++) {
+        const std::string where = p.thermal_file + ": line " + std::to_string(p.thermal_lines[i]) + ": ";
+        const size_t e = (size_t)p.thermal_elems[i];
+        if (e >= ne)
+            throw std::runtime_error(where + "element index " + std::to_string(e) + " is out of range (the mesh has " + std::to_string(ne) + " elements)");
+        if (listed[e]) throw std::runtime_error(where + "element " + std::to_string(e) + " is listed twice");
+        listed[e] = 1;
+        for (int v = 0; v < 2; v++) rows[2 * e + v] = p.thermal_values[2 * i + v];
+    }
+    ThermalLoads l;
+    l.tri_temp.assign(2 * (size_t)mesh.n_tri(), 0.0);
+    l.quad_temp.assign(2 * (size_t)mesh.n_quad(), 0.0);
+    for (size_t e = 0; e < ne; e++) {
+        const bool tri = mesh.order[e].first == 't';
+        const size_t k = (size_t)mesh.order[e].second;
+        double *dst = tri ? &l.tri_temp[2 * k] : &l.quad_temp[2 * k];
+        dst[0] = rows[2 * e] + (p.temperature_set ? p.temperature : 0.0);
+        dst[1] = rows[2 * e + 1] + (p.temperature_gradient_set ? p.temperature_gradient : 0.0);
+    }
+    if (!p.section_alpha_file.empty()) {
+        if (!sections) throw std::runtime_error(p.section_alpha_file + ": -section_alpha needs the sections of a -sections file");
+        l.section_alpha.assign(sections->sections.size(), p.alpha);
+        for (size_t i = 0; i < p.section_alpha_tags.size(); i++) {
+            const auto it = std::find(sections->tags.begin(), sections->tags.end(), p.section_alpha_tags[i]);
+            if (it == sections->tags.end())
+                throw std::runtime_error(p.section_alpha_file + ": line " + std::to_string(p.section_alpha_lines[i]) + ": tag " +
+                                         std::to_string(p.section_alpha_tags[i]) + " is not a tag of the -sections file");
+            l.section_alpha[(size_t)(it - sections->tags.begin()) + 1] = p.section_alpha_values[i];
+        }
+    }
+    return l;
+}
+
 ElementLoads build_element_loads(const Parameters &p, const ShellMesh &mesh, const SectionTable *sections)
 {
     const size_t ne = mesh.order.size();
@@ -188,6 +286,14 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-gravity:\t gx gy gz: self-weight rho t g per area of every element, t the element's own under -sections (needs -rho; without\n"
             << "\t -dt / -steps the solve stays static)\n"
             << "\t -pressure, -element_loads and -gravity add up and come on top of the force file's nodal loads; not with -modes\n"
+            << "-alpha:\t thermal expansion coefficient A (needed by the temperature options below)\n"
+            << "-section_alpha:\t file of lines 'tag alpha': expansion coefficient of the sections with that tag of the -sections file\n"
+            << "\t (optional; sections not listed keep -alpha)\n"
+            << "-temperature:\t temperature change TM of the mid-surface of every element (optional)\n"
+            << "-temperature_gradient:\t temperature difference TG = top - bottom of every element, top along the element's own normal\n"
+            << "-thermal:\t file of lines 'elem Tm Tg': temperatures of the element with that index in mesh-file order (optional)\n"
+            << "\t -temperature, -temperature_gradient and -thermal add up; the work-equivalent loads come on top of all other loads, and\n"
+            << "\t -stress, -reactions and -buckling work on the heated shell; not with -modes\n"
             << "-buckling:\t after the static solve: the N load factors of smallest magnitude (signed) at which the solved load case\n"
             << "\t buckles, N in 1 .. 28; writes <out>_buckling.txt, lines 'index lambda rho', and the shapes as point arrays\n"
             << "\t buckling_<k>_u / buckling_<k>_r of <out>.vtk (optional; not with -modes or -dt / -steps)\n"
@@ -456,6 +562,70 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             failed = true;
         }
     }
+    // thermal loads: refused here in the same way
+    if (has_flag(argc, argv, "-alpha")) {
+        p.alpha_set = true;
+        if (!number(arg_after(argc, argv, "-alpha"), &p.alpha)) {
+            err << "ERROR: -alpha needs a finite number!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-temperature")) {
+        p.temperature_set = true;
+        if (!number(arg_after(argc, argv, "-temperature"), &p.temperature)) {
+            err << "ERROR: -temperature needs a finite number!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-temperature_gradient")) {
+        p.temperature_gradient_set = true;
+        if (!number(arg_after(argc, argv, "-temperature_gradient"), &p.temperature_gradient)) {
+            err << "ERROR: -temperature_gradient needs a finite number!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-thermal")) {
+        const char *v = arg_after(argc, argv, "-thermal");
+        p.thermal_file = v ? v : "";
+        if (!v) {
+            err << "ERROR: -thermal needs a file!\n";
+            failed = true;
+        } else {
+            try {
+                read_thermal(p);
+            } catch (const std::exception &e) {
+                err << "ERROR: " << e.what() << "\n";
+                failed = true;
+            }
+        }
+    }
+    if (has_flag(argc, argv, "-section_alpha")) {
+        const char *v = arg_after(argc, argv, "-section_alpha");
+        p.section_alpha_file = v ? v : "";
+        if (!v) {
+            err << "ERROR: -section_alpha needs a file!\n";
+            failed = true;
+        } else {
+            try {
+                read_section_alpha(p);
+            } catch (const std::exception &e) {
+                err << "ERROR: " << e.what() << "\n";
+                failed = true;
+            }
+        }
+        if (!has_flag(argc, argv, "-sections")) {
+            err << "ERROR: -section_alpha needs the sections of a -sections file!\n";
+            failed = true;
+        }
+    }
+    if ((p.thermal_requested() || has_flag(argc, argv, "-section_alpha")) && !has_flag(argc, argv, "-alpha")) {
+        err << "ERROR: -temperature / -temperature_gradient / -thermal / -section_alpha need an expansion coefficient, -alpha!\n";
+        failed = true;
+    }
+    if ((p.thermal_requested() || p.alpha_set || has_flag(argc, argv, "-section_alpha")) && has_flag(argc, argv, "-modes")) {
+        err << "ERROR: -alpha / -section_alpha / -temperature / -temperature_gradient / -thermal do not go together with -modes (a modal analysis has no loads)!\n";
+        failed = true;
+    }
     if (p.element_loads_requested() && has_flag(argc, argv, "-modes")) {
         err << "ERROR: -pressure / -element_loads / -gravity do not go together with -modes (a modal analysis has no loads)!\n";
         failed = true;
@@ -624,6 +794,14 @@ void ShellSystem::set_element_loads(const ElementLoads &l)
           "femshell_set_element_loads");
 }
 
+void ShellSystem::set_thermal(const Parameters &p, const ThermalLoads &l)
+{
+    check(femshell_set_expansion(ctx_, p.alpha, (int32_t)l.section_alpha.size(), l.section_alpha.empty() ? nullptr : l.section_alpha.data()),
+          "femshell_set_expansion");
+    check(femshell_set_thermal(ctx_, l.tri_temp.empty() ? nullptr : l.tri_temp.data(), l.quad_temp.empty() ? nullptr : l.quad_temp.data()),
+          "femshell_set_thermal");
+}
+
 std::vector<double> ShellSystem::reactions()
 {
     std::vector<double> r((size_t)n_nodes_ * 6, 0.0);
@@ -666,6 +844,7 @@ SectionTable read_sections(const Parameters &p, ShellMesh &mesh)
                 throw std::runtime_error(p.sections_file + ": line " + std::to_string(no) + ": tag " + std::to_string(tag) + " is listed twice");
             listed.push_back((int32_t)tag);
             t.sections.push_back(s);
+            t.tags.push_back((int32_t)tag);
         }
     }
     const size_t ne = mesh.order.size();
@@ -859,6 +1038,8 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         if (p.prescribed_requested()) check_prescribed_nodes(p, mesh.n_nodes()); // (before any device is touched)
         ElementLoads element_loads;
         if (p.element_loads_requested()) element_loads = build_element_loads(p, mesh, p.sections_requested() ? &section_table : nullptr); // (likewise)
+        ThermalLoads thermal_loads;
+        if (p.thermal_requested()) thermal_loads = build_thermal_loads(p, mesh, p.sections_requested() ? &section_table : nullptr); // (likewise)
         clock.done("read mesh and loads");
         const Launch launch = Launch::from_environment();
         ShellSystem system(p, launch);
@@ -870,6 +1051,7 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
             system.set_prescribed(p);
         }
         if (p.element_loads_requested()) system.set_element_loads(element_loads); // (on top of the force file's nodal loads)
+        if (p.thermal_requested()) system.set_thermal(p, thermal_loads); // (on top of all other loads; after the sections: alpha belongs to them)
         if (p.reactions && launch.world_size != 1) throw std::runtime_error("-reactions runs on one rank");
         if (p.stress && launch.world_size != 1) throw std::runtime_error("-stress runs on one rank");
         if (p.buckling_requested() && launch.world_size != 1) throw std::runtime_error("-buckling runs on one rank");

@@ -100,6 +100,22 @@ struct Parameters {
     std::vector<int> element_load_lines;     // ... and its line number
     std::vector<double> element_load_values; // ... and its four values
     bool element_loads_requested() const { return pressure_set || gravity_set || !element_loads_file.empty(); }
+    // thermal loads (extension, stand-alone program only; the reference has none): temperatures per element
+    // (femshell_set_expansion, femshell_set_thermal).  -alpha A: the expansion coefficient, -section_alpha FILE: lines "tag alpha" for
+    // the tags of the -sections file (sections not listed keep A).  -temperature TM: the temperature change of the mid-surface of
+    // every element, -temperature_gradient TG: the difference top - bottom of every element, top along the element's own normal.
+    // -thermal FILE: lines "elem Tm Tg" with the conventions of -element_loads.  Uniform values and the file add up.  All need
+    // -alpha; constant in time under -dt / -steps.
+    bool alpha_set = false, temperature_set = false, temperature_gradient_set = false;
+    double alpha = 0.0, temperature = 0.0, temperature_gradient = 0.0;
+    std::string section_alpha_file, thermal_file;
+    std::vector<int32_t> section_alpha_tags; // tag of every line of the -section_alpha file
+    std::vector<int> section_alpha_lines;    // ... and its line number
+    std::vector<double> section_alpha_values;
+    std::vector<int32_t> thermal_elems;      // element of every line of the -thermal file
+    std::vector<int> thermal_lines;          // ... and its line number
+    std::vector<double> thermal_values;      // ... and its two values
+    bool thermal_requested() const { return temperature_set || temperature_gradient_set || !thermal_file.empty(); }
     // linear buckling (extension, stand-alone program only; the reference has no stability analysis): -buckling N [-buckling_tol T],
     // after the static solve, computes the N load factors of smallest magnitude of (K + lambda K_G(u)) x = 0 with the prestress of
     // the solution (femshell_buckling); writes <out>_buckling.txt -- a '#' header, then a line "index lambda rho" (%.15e) per mode
@@ -123,7 +139,17 @@ ElementLoads build_element_loads(const Parameters &p, const ShellMesh &mesh, con
 struct SectionTable {
     std::vector<femshell_section> sections;
     std::vector<int32_t> tri_section, quad_section;
+    std::vector<int32_t> tags; // of section 1 + i, as the -sections file lists them
 };
+// what femshell_set_expansion and femshell_set_thermal take: rows (Tm, Tg) of the triangles and of the quadrilaterals, and one
+// alpha per section under -section_alpha (empty: -alpha for every element)
+struct ThermalLoads {
+    std::vector<double> tri_temp, quad_temp, section_alpha;
+};
+// -temperature, -temperature_gradient and -thermal added up per element, -section_alpha held against the table's tags; throws
+// std::runtime_error with file name and line number on an element the mesh does not have, one listed twice, a tag the -sections
+// file does not list
+ThermalLoads build_thermal_loads(const Parameters &p, const ShellMesh &mesh, const SectionTable *sections);
 // Reads the files (std::runtime_error with file name and line number on a malformed line), gives every element its section
 // and leaves the tags that were used in mesh.elem_tag (the output files show them as the cell array "section").
 SectionTable read_sections(const Parameters &p, ShellMesh &mesh);
@@ -186,6 +212,8 @@ class ShellSystem {
     void set_prescribed(const Parameters &p);
     // -pressure / -element_loads / -gravity: the rows of build_element_loads (after set_mesh)
     void set_element_loads(const ElementLoads &l);
+    // -alpha / -temperature / -temperature_gradient / -thermal: the rows of build_thermal_loads (after set_mesh and set_sections)
+    void set_thermal(const Parameters &p, const ThermalLoads &l);
     // -reactions: r = K_unc u - loads of the last solve's solution, n_nodes x 6
     std::vector<double> reactions();
     // -stress: the element resultants of the last solve's solution, (n_tri + n_quad) x 14, triangles then quadrilaterals

@@ -97,6 +97,9 @@ typedef struct femshell_section { double nu, E, thickness; } femshell_section;
  * returns the context to the uniform material of its femshell_config.  Only values change: the plan and the
  * sparsity are kept, K and the multigrid hierarchy are rebuilt at the next assemble / solve.  femshell_set_mesh
  * forgets the sections (the element count may have changed).  The behaviour flags stay the context's.
+ * Every call -- also one that clears, or clears when none were set -- forgets the densities of femshell_set_density and the
+ * expansion coefficients of femshell_set_expansion, which belong to the sections they were given for, and with alpha the
+ * temperatures of femshell_set_thermal: the loads in force go back to nodal + S and the right-hand side is rebuilt.
  * FEMSHELL_ERR_INVALID (no mesh, a null array, an index outside [0, n_sections), a section that femshell_create
  * would refuse as a config) leaves the sections that were in force untouched.
  * A context with sections runs the sectioned instantiation of the kernel its mesh was laid out for; the pipelined one takes
@@ -171,6 +174,48 @@ int femshell_set_element_loads(femshell_ctx *ctx, const double *tri_load /* n_tr
  * Dirichlet set; on a row-partitioned context every rank receives all rows (gathered like femshell_lumped_mass).  Zeros when no
  * element loads are set.  Two calls give the same bits. */
 int femshell_element_load_vector(femshell_ctx *ctx, double *f6_out /* n_nodes x 6 */);
+
+/* extends: the reference has no thermal loads.  TEMPERATURE per element: two doubles (Tm, Tg),
+ *   Tm  the temperature change of the mid-surface,
+ *   Tg  = T_top - T_bottom, the difference through the thickness; "top" is z = +t/2 along the element's own ez, the top of
+ *       femshell_element_resultants and the normal the pressure of femshell_set_element_loads acts along,
+ * and per context an expansion coefficient alpha, optionally one per section (passed as femshell_set_density passes rho:
+ * n_sections == 0: alpha for every element; otherwise n_sections must be the context's section count).
+ * Free thermal state in the element frame, kappa = (w,xx, w,yy, 2 w,xy) as in the resultants:
+ *     eps0 = alpha Tm (1, 1, 0),   kappa0 = -(alpha Tg / t) (1, 1, 0)
+ * (a plate that is warmer on top bows towards +ez in the middle of its edges' chord: w,xx < 0).  Stress state, exact for a
+ * temperature that is linear through the thickness:
+ *     N_loc = t Dm (eps - eps0),   M_loc = -Dp (kappa - kappa0).
+ * Equivalent nodal loads, work-equivalent, with the element's OWN strain operators and the quadrature of its stiffness:
+ *     f_m = sum_g w_g Bm_g^T (t Dm eps0) =  N_T sum_g w_g Bm_g^T (1,1,0),   N_T = E t alpha Tm / (1 - nu)
+ *     f_p = sum_g w_g Bp_g^T (Dp kappa0) = -M_T sum_g w_g Bp_g^T (1,1,0),   M_T = E t^2 alpha Tg / (12 (1 - nu))
+ * TRI3: the CST operator at one point (f_m of a node is N_T / 2 times the in-plane normal of the opposite side that points towards
+ * the node -- outward at the node: a heated element pushes its nodes apart --, scaled by the side's length) and Specht's curvature operator at its three Gauss points, with the Y of the stiffness (FEMSHELL_REF_Y21
+ * included; the row of Y that the switch changes multiplies the zero of (1,1,0)).  QUAD4: the bilinear membrane operator and MINUS
+ * the DKQ operator at the 2 x 2 points with weights det J.  The loads are rotated to global axes with the element frame; they fill
+ * the rotational rows, the drilling row gets nothing.  A degenerate element contributes finite zeros and reports no status here
+ * (the assembly reports it).
+ * T_a = the sum over the elements that contain node a, in the order of the element list of the node's slice, from zero, without
+ * atomics: bitwise reproducible, independent of grid and tile size.  The loads in force are
+ *     loads_a = (nodal_a + S_a) + T_a   (one rounding per +),
+ * S the element loads: F, the right-hand side with prescribed values, femshell_reactions (r = K_unc u - loads: the internal force
+ * is K u - T) and the Newmark right-hand side all see the sum.  With no temperatures set every buffer and every bit is what it is
+ * without these functions.  While temperatures are in force femshell_element_resultants reports the stress state above (and the
+ * surface stresses computed from it), and femshell_geometric_product / femshell_buckling use its membrane forces.
+ * tri_temp[n_tri][2] / quad_temp[n_quad][2]: rows in the caller's element order; every rank passes the full arrays.  NULL for one
+ * kind leaves that kind cold; both NULL clears the temperatures.  The call replaces the previous set; only the right-hand side is
+ * rebuilt, and the nodal loads are not uploaded again (16 bytes per local element are).  Allowed wherever
+ * femshell_set_element_loads is.  FEMSHELL_ERR_INVALID (a non-finite value, no mesh, temperatures before alpha is set, a section
+ * count that does not match) leaves what was in force untouched.  femshell_set_expansion while temperatures are in force rebuilds
+ * the loads with the new alpha.  femshell_set_mesh forgets the temperatures and alpha; femshell_set_sections forgets alpha -- as
+ * it forgets the densities -- and with it the temperatures: the loads are nodal + S again.  Kernel: csrc/element_thermal.hip. */
+int femshell_set_expansion(femshell_ctx *ctx, double alpha, int32_t n_sections, const double *section_alpha);
+int femshell_set_thermal(femshell_ctx *ctx, const double *tri_temp /* n_tri x 2, or NULL */,
+                         const double *quad_temp /* n_quad x 2, or NULL */);
+/* f6_out[n_nodes][6]: T alone, in the caller's numbering (also under FEMSHELL_REORDER), NOT masked by the Dirichlet set; on a
+ * row-partitioned context every rank receives all rows (gathered like femshell_element_load_vector).  Zeros when no temperatures
+ * are set.  Two calls give the same bits. */
+int femshell_thermal_load_vector(femshell_ctx *ctx, double *f6_out /* n_nodes x 6 */);
 
 /* replaces: assemble_elasticity (SA:1160-1233): element stiffness (initElement, calcPlane,
  * calcPlate, constructStiffnessMatrix, localToGlobalTrafo), constraint handling, add_matrix /
@@ -767,7 +812,12 @@ typedef enum femshell_kernel {
     /* k_geometric_product, one pass of four columns back to back on hashed coefficients and hashed vectors; needs a mesh only.
      * bytes_out: 16 bytes of node ids, 4 of element index and 48 (80 on a mesh with quadrilaterals) of coefficients per entry of
      * the slices' element lists, 24 bytes read and 48 written per owned row and column */
-    FEMSHELL_KERNEL_GEOMETRIC_PRODUCT = 14
+    FEMSHELL_KERNEL_GEOMETRIC_PRODUCT = 14,
+    /* k_element_thermal back to back on hashed temperatures and a unit alpha, from the loads in force into a scratch vector; needs
+     * a mesh only, the loads in force are not disturbed.  bytes_out: 16 bytes of node ids, 4 of element index and 16 of
+     * temperatures per entry of the slices' element lists (4 more of a section index where the context has sections), 24 bytes
+     * of coordinates per node, 48 bytes of base read and 48 written per owned row -- all six components carry a sum */
+    FEMSHELL_KERNEL_ELEMENT_THERMAL = 15
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
