@@ -1,6 +1,6 @@
 // device_common.hpp -- device helpers shared by the kernel translation units (kernels.hip, spmv_kernels.hip, cg_kernels.hip,
 // amg_kernels.hip, ...):
-// the XCD-aware slice walk, workgroup sums, the packed block-Jacobi inverse.
+// the XCD-aware slice walk, the pieces of a slice's row sums in list order, workgroup sums, the packed block-Jacobi inverse.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -35,6 +35,58 @@ struct SliceWalk {
     __device__ __forceinline__ bool valid() const { return s < last; }
     __device__ __forceinline__ void next() { s += step; }
 };
+
+// ---- row sums of a slice over its element list, in list order (k_element_loads, k_element_thermal, k_geometric_product) ----------
+// A kernel walks the list in tiles.  Whole waves take 64 consecutive entries each; a lane leaves what its entry contributes in LDS,
+// and one ballot per row turns the entries' membership round: per wave of entries and row a 64-bit word, bit b = the wave's entry
+// b contains the row.  A lane that sums a row then visits the words of its row wave after wave and the set bits of a word from
+// the lowest -- the list order whatever the tile and the grid are, no atomics, the same bits from every launch.
+//
+// Node j of an entry: if it is a row of the slice (a triangle's fourth node, -1, and ghosts fall outside), its bit joins `rows`
+// (bit r: node row0 + r belongs to the entry) and its row becomes byte j of `word`.  `word` starts as 0xFFFFFFFF: 0xFF means none.
+// (One node per call, the loop over the nodes stays in the kernel: with the loop in here the compiler allots the instantiations
+// of k_geometric_product two to seven more vector registers for the same work.)
+__device__ __forceinline__ void entry_node(int j, int node, int row0, uint32_t &rows, uint32_t &word)
+{
+    const uint32_t r = (uint32_t)(node - row0);
+    if (r < (uint32_t)kSliceNodes) {
+        rows |= 1u << r;
+        word = (word & ~(0xFFu << (8 * j))) | (r << (8 * j));
+    }
+}
+// the row bit alone, for a kernel that does not ask where in the entry a row is (k_element_loads: with the unused word in
+// the source its triangle instantiation is allotted another register count)
+__device__ __forceinline__ void entry_row_bit(int node, int row0, uint32_t &rows)
+{
+    const uint32_t r = (uint32_t)(node - row0);
+    if (r < (uint32_t)kSliceNodes) rows |= 1u << r;
+}
+// which node of the entry the row is (a node occurs once in an element)
+__device__ __forceinline__ int entry_node_of_row(uint32_t word, uint32_t row)
+{
+    return (word & 0xFFu) == row ? 0 : (((word >> 8) & 0xFFu) == row ? 1 : (((word >> 16) & 0xFFu) == row ? 2 : 3));
+}
+// The wave's ballots into its words, wave_rows[kSliceNodes].  Every lane of the wave must call it (rows = 0 past the tile's end):
+// the wave's 64 entries are 64 consecutive entries of the list, so bit b of the ballot for row r is the wave's entry b.
+__device__ __forceinline__ void publish_rows(uint32_t rows, int lane, unsigned long long *wave_rows)
+{
+    for (int r = 0; r < kSliceNodes; r++) {
+        const unsigned long long has = __ballot((rows >> r) & 1u);
+        if (lane == r) wave_rows[r] = has;
+    }
+}
+// body(i) for the entries i < nt of the tile that contain `row`, in list order
+template <class Body>
+__device__ __forceinline__ void for_entries_of_row(const unsigned long long (*s_rows)[kSliceNodes], int nt, int row, Body body)
+{
+    for (int c0 = 0; c0 < nt; c0 += 64) {
+        unsigned long long has = s_rows[c0 >> 6][row];
+        while (has) {
+            body(c0 + __ffsll(has) - 1);
+            has &= has - 1;
+        }
+    }
+}
 
 __device__ __forceinline__ double wave_sum(double v)
 {

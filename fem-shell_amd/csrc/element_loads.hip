@@ -82,29 +82,13 @@ __global__ __launch_bounds__(kElThreads) void k_element_loads(DeviceMatrix m, co
                     s_share[3 * i + 2] = l0.x * cz / pdiv + l1.y * share;
                     const int nid[4] = {c.x, c.y, c.z, kHasQuads ? c.w : -1};
 #pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const uint32_t r = (uint32_t)(nid[j] - row0); // (a triangle's fourth node, -1, and ghosts fall outside)
-                        if (r < (uint32_t)kSliceNodes) rows |= 1u << r;
-                    }
+                    for (int j = 0; j < 4; j++) entry_row_bit(nid[j], row0, rows); // (every node of the element gets the same share)
                 }
-                // the wave's 64 entries are 64 consecutive entries of the list: bit b of the ballot for row r is entry i0 + b
-                for (int r = 0; r < kSliceNodes; r++) {
-                    const unsigned long long has = __ballot((rows >> r) & 1u);
-                    if (lane == r) s_rows[i0 >> 6][r] = has;
-                }
+                publish_rows(rows, lane, s_rows[i0 >> 6]);
             }
             __syncthreads();
             // ---- B: row sums in list order: waves of entries ascending, within one the set bits ascending
-            if (tid < kSliceNodes * 3) {
-                for (int c0 = 0; c0 < nt; c0 += 64) {
-                    unsigned long long has = s_rows[c0 >> 6][my_row];
-                    while (has) {
-                        const int b = __ffsll(has) - 1;
-                        sum += s_share[3 * (c0 + b) + my_v];
-                        has &= has - 1;
-                    }
-                }
-            }
+            if (tid < kSliceNodes * 3) for_entries_of_row(s_rows, nt, my_row, [&](int i) { sum += s_share[3 * i + my_v]; });
             __syncthreads(); // (the next tile overwrites the shares)
         }
         if (tid < kSliceNodes * 3) s_sum[tid] = sum;

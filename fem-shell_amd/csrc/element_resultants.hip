@@ -16,6 +16,8 @@
 // them into LDS and the wave writes its 64 rows -- 7168 contiguous bytes -- as 16-byte words, lane after lane.  No atomics, no sum
 // across lanes: two launches give the same bits.  A degenerate element writes zeros and reports kStatusDirect + its index.
 // Rows are in the LOCAL element order; the host maps them to the caller's (api_resultants.cpp).
+#include <type_traits>
+
 #include "kernels.hpp"
 #include "device_common.hpp"
 
@@ -25,23 +27,6 @@ constexpr int kErThreads = 256;
 constexpr int kErWords = 14; // doubles per element
 
 namespace {
-
-// sum over the three Gauss points of Specht's tables: sQ_n[r] = kSumQA[n][r] + mu_{(n+2)%3} kSumQB[n][r]
-struct SpechtSums {
-    double a[3][3], b[3][3];
-};
-constexpr SpechtSums specht_sums()
-{
-    constexpr double QA[3][3][3] = SPECHT_QA_INIT;
-    constexpr double QB[3][3][3] = SPECHT_QB_INIT;
-    SpechtSums s{};
-    for (int n = 0; n < 3; n++)
-        for (int r = 0; r < 3; r++) {
-            s.a[n][r] = QA[n][0][r] + QA[n][1][r] + QA[n][2][r];
-            s.b[n][r] = QB[n][0][r] + QB[n][1][r] + QB[n][2][r];
-        }
-    return s;
-}
 
 // what the element math hands on: local membrane strain and curvature means and the frame
 struct ElemMeans {
@@ -73,15 +58,8 @@ __device__ __forceinline__ bool tri3_means(const double X[9], const double U[3][
         o.ey[d] = f.ey[d];
         o.ez[d] = f.ez[d];
     }
-    double C[3], mu[3];
-#pragma unroll
-    for (int e = 0; e < 3; e++) C[e] = f.xs[e] * f.xs[e] + f.ys[e] * f.ys[e];
-    {
-        const double c01 = C[0] * C[1], rall = ok ? 1.0 / (c01 * C[2]) : 0.0; // as tri3_record
-        mu[0] = (C[0] - C[1]) * (c01 * rall);
-        mu[1] = (C[2] - C[0]) * (C[0] * C[2] * rall);
-        mu[2] = (C[1] - C[2]) * (C[1] * C[2] * rall);
-    }
+    double mu[3];
+    specht_mu(f, ok, mu);
     double mQ[3][3]; // (1/3) sum_g Q_n(g)
 #pragma unroll
     for (int n = 0; n < 3; n++)
@@ -99,9 +77,8 @@ __device__ __forceinline__ bool tri3_means(const double X[9], const double U[3][
         e1 += gi * ul[1];
         e2 += gi * ul[0] + bi * ul[1];
         // plate: rows seen from node i (tri_row_ki, tri_row_ji), d_i = (w, tx, ty)
-        constexpr int kPrev[3] = {2, 0, 1}, kRowKi[3] = {1, 0, 2}, kRowJi[3] = {0, 2, 1};
-        const int k = kPrev[i];
-        const double xki = f.xs[kRowKi[i]], yki = f.ys[kRowKi[i]], xji = -f.xs[kRowJi[i]], yji = -f.ys[kRowJi[i]];
+        const int k = tri_prev(i);
+        const double xki = f.xs[tri_row_ki(i)], yki = f.ys[tri_row_ki(i)], xji = -f.xs[tri_row_ji(i)], yji = -f.ys[tri_row_ji(i)];
         const double w = ul[2], tx = rl[0], ty = rl[1];
         const double ud = 2.0 * w + yji * tx - xji * ty;  // u_i . d_i
         const double vd = -2.0 * w - yki * tx + xki * ty; // v_i . d_i
@@ -125,38 +102,17 @@ __device__ __forceinline__ bool tri3_means(const double X[9], const double U[3][
 __device__ __forceinline__ bool quad4_means(const double X[12], const double U[4][6], ElemMeans &o)
 {
 #pragma clang fp reassociate(on) contract(fast) // element math only; parity bar is 1e-12, not bitwise
-    // frame from the mid-side points (SA:342-375), as quad4_record
-    double vr[3];
+    QuadFrame q;
+    const bool ok = quad4_frame(X, q); // (of X as given: the caller translates)
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-        const double mI = X[d] + 0.5 * (X[3 + d] - X[d]);
-        const double mJ = X[3 + d] + 0.5 * (X[6 + d] - X[3 + d]);
-        const double mK = X[6 + d] + 0.5 * (X[9 + d] - X[6 + d]);
-        const double mL = X[9 + d] + 0.5 * (X[d] - X[9 + d]);
-        o.ex[d] = mJ - mL;
-        vr[d] = mK - mI;
+        o.ex[d] = q.ex[d];
+        o.ey[d] = q.ey[d];
+        o.ez[d] = q.ez[d];
     }
-    const double lx2 = o.ex[0] * o.ex[0] + o.ex[1] * o.ex[1] + o.ex[2] * o.ex[2];
-    bool ok = lx2 > 0.0;
-    const double ilx = ok ? 1.0 / sqrt(lx2) : 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) o.ex[d] *= ilx;
-    o.ez[0] = o.ex[1] * vr[2] - o.ex[2] * vr[1];
-    o.ez[1] = o.ex[2] * vr[0] - o.ex[0] * vr[2];
-    o.ez[2] = o.ex[0] * vr[1] - o.ex[1] * vr[0];
-    const double lz2 = o.ez[0] * o.ez[0] + o.ez[1] * o.ez[1] + o.ez[2] * o.ez[2];
-    ok = ok && lz2 > 0.0;
-    const double ilz = ok ? 1.0 / sqrt(lz2) : 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) o.ez[d] *= ilz;
-    o.ey[0] = o.ez[1] * o.ex[2] - o.ez[2] * o.ex[1];
-    o.ey[1] = o.ez[2] * o.ex[0] - o.ez[0] * o.ex[2];
-    o.ey[2] = o.ez[0] * o.ex[1] - o.ez[1] * o.ex[0];
-    double x[4], y[4], um[4][2], dp[4][3]; // local coordinates (of X as given: the caller translates), local (u, v) and (w, tx, ty) of the nodes
+    double um[4][2], dp[4][3]; // local (u, v) and (w, tx, ty) of the nodes
 #pragma unroll
     for (int n = 0; n < 4; n++) {
-        x[n] = o.ex[0] * X[3 * n] + o.ex[1] * X[3 * n + 1] + o.ex[2] * X[3 * n + 2];
-        y[n] = o.ey[0] * X[3 * n] + o.ey[1] * X[3 * n + 1] + o.ey[2] * X[3 * n + 2];
         double ul[3], rl[2];
         to_local(o, U[n], ul, rl);
         um[n][0] = ul[0];
@@ -165,66 +121,40 @@ __device__ __forceinline__ bool quad4_means(const double X[12], const double U[4
         dp[n][1] = rl[0];
         dp[n][2] = rl[1];
     }
-    double a2 = 0.0;
-#pragma unroll
-    for (int n = 0; n < 4; n++) a2 += x[n] * y[(n + 1) % 4] - x[(n + 1) % 4] * y[n];
-    ok = ok && fabs(a2) > 0.0;
-    // DKQ side coefficients (SA:613-621), side s from node s to node s + 1
     DkqSide sd[4];
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const double dx = x[s] - x[(s + 1) % 4], dy = y[s] - y[(s + 1) % 4];
-        const double l2 = dx * dx + dy * dy;
-        const double l = (ok && l2 > 0.0) ? 1.0 / l2 : 0.0;
-        sd[s].a = -dx * l;
-        sd[s].b = 0.75 * dx * dy * l;
-        sd[s].c = (0.25 * dx * dx - 0.5 * dy * dy) * l;
-        sd[s].d = -dy * l;
-        sd[s].e = (0.25 * dy * dy - 0.5 * dx * dx) * l;
-    }
-    const double x12 = x[0] - x[1], y12 = y[0] - y[1], x23 = x[1] - x[2], y23 = y[1] - y[2];
-    const double x34 = x[2] - x[3], y34 = y[2] - y[3], x41 = x[3] - x[0], y41 = y[3] - y[0];
-    const double root = 0.57735026918962576451; // sqrt(1/3)
+    dkq_sides(q, ok, sd);
     double es[3] = {0.0, 0.0, 0.0}, ks[3] = {0.0, 0.0, 0.0}, dsum = 0.0;
 #pragma unroll 1 // (one copy of the Gauss-point code: the register budget, as in quad4_block_add_rec)
     for (int gp = 0; gp < 4; gp++) {
-        const double r = (gp & 2) ? -root : root, s = (gp & 1) ? -root : root; // SA:482-487 order
-        const double J00 = 0.25 * ((x12 + x34) * s - x12 + x34), J01 = 0.25 * ((y12 + y34) * s - y12 + y34);
-        const double J10 = 0.25 * ((x12 + x34) * r - x23 + x41), J11 = 0.25 * ((y12 + y34) * r - y23 + y41);
-        const double det = J00 * J11 - J01 * J10, idet = (ok && det != 0.0) ? 1.0 / det : 0.0;
-        const double Ji[4] = {J11 * idet, -J01 * idet, -J10 * idet, J00 * idet};
-        auto corner_x = [&](double rr, double ss) { return 0.25 * rr * (1.0 + s * ss) * (2.0 * r * rr + s * ss); };
-        auto corner_e = [&](double rr, double ss) { return 0.25 * ss * (1.0 + r * rr) * (2.0 * s * ss + r * rr); };
-        // mid-side functions of side 0..3 (SA:906-923)
-        const double mid_x[4] = {-r * (1.0 - s), 0.5 * (1.0 - s * s), -r * (1.0 + s), -0.5 * (1.0 - s * s)};
-        const double mid_e[4] = {-0.5 * (1.0 - r * r), -s * (1.0 + r), 0.5 * (1.0 - r * r), -s * (1.0 - r)};
+        const QuadGauss g = quad4_gauss(q, gp, ok);
         double eg[3] = {0.0, 0.0, 0.0}, kg[3] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int n = 0; n < 4; n++) {
-            const double rn = (n == 1 || n == 2) ? 1.0 : -1.0, sn = (n >= 2) ? 1.0 : -1.0;
-            const double dr = 0.25 * rn * (1.0 + sn * s), ds = 0.25 * sn * (1.0 + rn * r);
-            const double bx = Ji[0] * dr + Ji[1] * ds, by = Ji[2] * dr + Ji[3] * ds; // dN/dx, dN/dy
+            double bx, by; // dN/dx, dN/dy
+            bilinear_grad(n, g.r, g.s, g.Ji, bx, by);
             eg[0] += bx * um[n][0];
             eg[1] += by * um[n][1];
             eg[2] += by * um[n][0] + bx * um[n][1];
             const int np = (n + 3) & 3;
+            const double rn = quad_corner_r(n), sn = quad_corner_s(n);
             double B[3][3];
-            dkq_node_block(sd[n], sd[np], corner_x(rn, sn), corner_e(rn, sn), mid_x[n], mid_e[n], mid_x[np], mid_e[np], Ji, B);
+            dkq_node_block(sd[n], sd[np], dkq_corner_x(g.r, g.s, rn, sn), dkq_corner_e(g.r, g.s, rn, sn), dkq_mid_x(g.r, g.s, n),
+                           dkq_mid_e(g.r, g.s, n), dkq_mid_x(g.r, g.s, np), dkq_mid_e(g.r, g.s, np), g.Ji, B);
 #pragma unroll
-            for (int q = 0; q < 3; q++) kg[q] += B[q][0] * dp[n][0] + B[q][1] * dp[n][1] + B[q][2] * dp[n][2];
+            for (int c = 0; c < 3; c++) kg[c] += B[c][0] * dp[n][0] + B[c][1] * dp[n][1] + B[c][2] * dp[n][2];
         }
 #pragma unroll
-        for (int q = 0; q < 3; q++) {
-            es[q] += det * eg[q];
-            ks[q] += det * kg[q];
+        for (int c = 0; c < 3; c++) {
+            es[c] += g.det * eg[c];
+            ks[c] += g.det * kg[c];
         }
-        dsum += det;
+        dsum += g.det;
     }
     const double iw = (ok && dsum != 0.0) ? 1.0 / dsum : 0.0;
 #pragma unroll
-    for (int q = 0; q < 3; q++) {
-        o.eps[q] = es[q] * iw;
-        o.kap[q] = -ks[q] * iw; // the DKQ operator is in beta = -grad w
+    for (int c = 0; c < 3; c++) {
+        o.eps[c] = es[c] * iw;
+        o.kap[c] = -ks[c] * iw; // the DKQ operator is in beta = -grad w
     }
     return ok;
 }
@@ -270,10 +200,13 @@ __device__ __forceinline__ void gather_u(const double *u, const double *up, int 
 } // namespace
 
 // out: (n_ltri + n_lquad) x 14, local element order.  u, up: (n_pad + n_ghost) x 6, up may be nullptr.  sec_t: thickness per section
-// (kSections only: the table in HBM keeps products of it).
-template <bool kHasQuads, bool kSections>
+// (kSections only: the table in HBM keeps products of it).  kThermal: temperatures are in force -- the element means
+// lose the free thermal state before the material is applied, N_loc = t Dm (eps - eps0), M_loc = -Dp (kappa - kappa0), from the
+// element's (Tm, Tg) and the expansion of its section (tv).  Without, tv is not looked at: those instantiations are the only ones
+// launched when nothing is set.
+template <bool kHasQuads, bool kSections, bool kThermal>
 __global__ __launch_bounds__(kErThreads) void k_element_resultants(DeviceMatrix m, MatConst mc, DeviceSections ds, const double *__restrict__ sec_t,
-                                                                  const double *__restrict__ u, const double *__restrict__ up,
+                                                                  const double *__restrict__ u, const double *__restrict__ up, ThermalView tv,
                                                                   double *__restrict__ out)
 {
     __shared__ __attribute__((aligned(16))) double s_out[kErThreads * kErWords];
@@ -290,33 +223,18 @@ __global__ __launch_bounds__(kErThreads) void k_element_resultants(DeviceMatrix 
             const int32_t *c = m.tri + 3 * (int64_t)e;
             const int nid[3] = {c[0], c[1], c[2]};
             double X[9], U[3][6];
+            load_xyz<3>(m.xyz, nid, X);
 #pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const double *pt = m.xyz + 3 * (int64_t)nid[i];
-                X[3 * i + 0] = pt[0];
-                X[3 * i + 1] = pt[1];
-                X[3 * i + 2] = pt[2];
-                gather_u(u, up, nid[i], U[i]);
-            }
+            for (int i = 0; i < 3; i++) gather_u(u, up, nid[i], U[i]);
             ok = tri3_means(X, U, mc.flags, f);
         } else {
             const int4 c = reinterpret_cast<const int4 *>(m.quad)[e - m.n_ltri];
             const int nid[4] = {c.x, c.y, c.z, c.w};
             double X[12], U[4][6];
+            load_xyz<4>(m.xyz, nid, X);
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const double *pt = m.xyz + 3 * (int64_t)nid[i];
-                X[3 * i + 0] = pt[0];
-                X[3 * i + 1] = pt[1];
-                X[3 * i + 2] = pt[2];
-                gather_u(u, up, nid[i], U[i]);
-            }
-            // coordinates relative to the first node, each difference rounded once: quad4_means projects the coordinates it is
-            // given onto the frame and differences the projections, which at a distance D from the origin costs D / size digits
-#pragma unroll
-            for (int i = 3; i >= 0; i--)
-#pragma unroll
-                for (int d = 0; d < 3; d++) X[3 * i + d] -= X[d];
+            for (int i = 0; i < 4; i++) gather_u(u, up, nid[i], U[i]);
+            relative_to_first(X);
             ok = quad4_means(X, U, f);
         }
         double tcm = mc.t * mc.cm, cp = mc.cp, nu = mc.nu, g = mc.g, t = mc.t;
@@ -329,94 +247,7 @@ __global__ __launch_bounds__(kErThreads) void k_element_resultants(DeviceMatrix 
             g = sc.g;
             t = sec_t[si];
         }
-        double val[kErWords];
-        finish_element(f, tcm, cp, nu, g, t, val);
-#pragma unroll
-        for (int q = 0; q < kErWords; q++) res[q] = ok ? val[q] : 0.0; // (selects: a degenerate element's values may be Inf / NaN)
-        if (!ok) report_status(m.status, kStatusDirect + e);
-    }
-    // the lane's row into LDS, then the wave's rows out as contiguous 16-byte words
-    {
-        double2 *row = reinterpret_cast<double2 *>(s_out + (size_t)threadIdx.x * kErWords);
-#pragma unroll
-        for (int q = 0; q < kErWords / 2; q++) row[q] = make_double2(res[2 * q], res[2 * q + 1]);
-    }
-    __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int64_t first = (int64_t)blockIdx.x * kErThreads + 64 * wave; // first element of this wave
-    const int64_t left = (int64_t)n - first;
-    const int words = (int)(left < 0 ? 0 : (left > 64 ? 64 : left)) * (kErWords / 2); // 16-byte words of the wave's valid rows
-    const double2 *src = reinterpret_cast<const double2 *>(s_out + (size_t)wave * 64 * kErWords);
-    double2 *dst = reinterpret_cast<double2 *>(out + first * kErWords);
-#pragma unroll
-    for (int q = 0; q < kErWords / 2; q++) {
-        const int w = 64 * q + lane;
-        if (w < words) dst[w] = src[w];
-    }
-}
-
-// The same kernel while temperatures are in force: the element means lose the free thermal state before the material
-// is applied, N_loc = t Dm (eps - eps0), M_loc = -Dp (kappa - kappa0), from the element's (Tm, Tg) and the expansion of its section
-// (tv).  A kernel of its own, so that k_element_resultants above stays the code it was -- the only one launched when nothing is set.
-template <bool kHasQuads, bool kSections>
-__global__ __launch_bounds__(kErThreads) void k_element_resultants_thermal(DeviceMatrix m, MatConst mc, DeviceSections ds,
-                                                                          const double *__restrict__ sec_t, const double *__restrict__ u,
-                                                                          const double *__restrict__ up, ThermalView tv, double *__restrict__ out)
-{
-    __shared__ __attribute__((aligned(16))) double s_out[kErThreads * kErWords];
-    const int n = m.n_ltri + (kHasQuads ? m.n_lquad : 0);
-    const int64_t e64 = (int64_t)blockIdx.x * kErThreads + threadIdx.x;
-    double res[kErWords];
-#pragma unroll
-    for (int q = 0; q < kErWords; q++) res[q] = 0.0;
-    if (e64 < n) {
-        const int e = (int)e64;
-        ElemMeans f;
-        bool ok;
-        if (!kHasQuads || e < m.n_ltri) {
-            const int32_t *c = m.tri + 3 * (int64_t)e;
-            const int nid[3] = {c[0], c[1], c[2]};
-            double X[9], U[3][6];
-#pragma unroll
-            for (int i = 0; i < 3; i++) {
-                const double *pt = m.xyz + 3 * (int64_t)nid[i];
-                X[3 * i + 0] = pt[0];
-                X[3 * i + 1] = pt[1];
-                X[3 * i + 2] = pt[2];
-                gather_u(u, up, nid[i], U[i]);
-            }
-            ok = tri3_means(X, U, mc.flags, f);
-        } else {
-            const int4 c = reinterpret_cast<const int4 *>(m.quad)[e - m.n_ltri];
-            const int nid[4] = {c.x, c.y, c.z, c.w};
-            double X[12], U[4][6];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const double *pt = m.xyz + 3 * (int64_t)nid[i];
-                X[3 * i + 0] = pt[0];
-                X[3 * i + 1] = pt[1];
-                X[3 * i + 2] = pt[2];
-                gather_u(u, up, nid[i], U[i]);
-            }
-            // coordinates relative to the first node, each difference rounded once: quad4_means projects the coordinates it is
-            // given onto the frame and differences the projections, which at a distance D from the origin costs D / size digits
-#pragma unroll
-            for (int i = 3; i >= 0; i--)
-#pragma unroll
-                for (int d = 0; d < 3; d++) X[3 * i + d] -= X[d];
-            ok = quad4_means(X, U, f);
-        }
-        double tcm = mc.t * mc.cm, cp = mc.cp, nu = mc.nu, g = mc.g, t = mc.t;
-        if (kSections) { // the element's own material
-            const int si = ds.elem_section[e];
-            const SecConst sc = fetch_section(ds.table, si);
-            tcm = sc.tcm;
-            cp = sc.cp;
-            nu = sc.nu;
-            g = sc.g;
-            t = sec_t[si];
-        }
-        { // the free thermal state leaves: eps0 = alpha Tm (1,1,0), kappa0 = -(alpha Tg / t) (1,1,0)
+        if (kThermal) { // the free thermal state leaves: eps0 = alpha Tm (1,1,0), kappa0 = -(alpha Tg / t) (1,1,0)
             const double2 tmp = tv.elem_temp[e];
             double2 al = make_double2(tv.uni.alpha, tv.uni.alpha_t);
             if (kSections) al = reinterpret_cast<const double2 *>(tv.sec + ds.elem_section[e])[1];
@@ -458,29 +289,18 @@ void launch_element_resultants(const DeviceMatrix &m, const MatConst &mc, const 
     const int64_t n = (int64_t)m.n_ltri + m.n_lquad;
     if (n == 0) return;
     const DeviceSections ds = sections ? *sections : DeviceSections();
+    const ThermalView tv = thermal ? *thermal : ThermalView();
     const unsigned g = (unsigned)((n + kErThreads - 1) / kErThreads);
-    if (thermal) {
-        const ThermalView tv = *thermal;
-        auto launch_t = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(g), dim3(kErThreads), 0, st, m, mc, ds, sec_t, u, up, tv, out); };
-        if (sections) {
-            if (m.n_lquad > 0) launch_t(k_element_resultants_thermal<true, true>);
-            else launch_t(k_element_resultants_thermal<false, true>);
-        } else if (m.n_lquad > 0) {
-            launch_t(k_element_resultants_thermal<true, false>);
-        } else {
-            launch_t(k_element_resultants_thermal<false, false>);
-        }
-        return;
-    }
-    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(g), dim3(kErThreads), 0, st, m, mc, ds, sec_t, u, up, out); };
-    if (sections) { // (the instantiations with sections: contexts without never launch them)
-        if (m.n_lquad > 0) launch(k_element_resultants<true, true>);
-        else launch(k_element_resultants<false, true>);
-    } else if (m.n_lquad > 0) {
-        launch(k_element_resultants<true, false>);
-    } else {
-        launch(k_element_resultants<false, false>);
-    }
+    // one instantiation per (quadrilaterals, sections, temperatures): a context launches only those of what it holds
+    auto with = [](bool on, auto f) { on ? f(std::true_type()) : f(std::false_type()); };
+    with(m.n_lquad > 0, [&](auto quads) {
+        with(sections != nullptr, [&](auto sec) {
+            with(thermal != nullptr, [&](auto th) {
+                hipLaunchKernelGGL((k_element_resultants<decltype(quads)::value, decltype(sec)::value, decltype(th)::value>), dim3(g),
+                                   dim3(kErThreads), 0, st, m, mc, ds, sec_t, u, up, tv, out);
+            });
+        });
+    });
 }
 
 } // namespace femshell

@@ -41,23 +41,6 @@ static_assert(kThTile * 25 * 8 + kThTile * 4 + (kThTile / 64) * kSliceNodes * 8 
 
 namespace {
 
-// sum over the three Gauss points of Specht's tables (as element_resultants.hip): sQ_n[r] = a[n][r] + mu_{(n+2)%3} b[n][r]
-struct SpechtSumsT {
-    double a[3][3], b[3][3];
-};
-constexpr SpechtSumsT specht_sums_t()
-{
-    constexpr double QA[3][3][3] = SPECHT_QA_INIT;
-    constexpr double QB[3][3][3] = SPECHT_QB_INIT;
-    SpechtSumsT s{};
-    for (int n = 0; n < 3; n++)
-        for (int r = 0; r < 3; r++) {
-            s.a[n][r] = QA[n][0][r] + QA[n][1][r] + QA[n][2][r];
-            s.b[n][r] = QB[n][0][r] + QB[n][1][r] + QB[n][2][r];
-        }
-    return s;
-}
-
 // global 6-vector of one node from its local (fu, fv, fw) and (ftx, fty)
 __device__ __forceinline__ void put_node(double *dst, const double ex[3], const double ey[3], const double ez[3], double fu, double fv, double fw,
                                          double ftx, double fty)
@@ -74,19 +57,12 @@ __device__ __forceinline__ void put_node(double *dst, const double ex[3], const 
 __device__ __forceinline__ void tri3_thermal(const double X[9], double nt, double mt, double *dst)
 {
 #pragma clang fp reassociate(on) contract(fast) // element math only; parity bar is 1e-12, not bitwise
-    constexpr SpechtSumsT kS = specht_sums_t();
+    constexpr SpechtSums kS = specht_sums();
     constexpr double kC[3][3] = SPECHT_C456_INIT;
     TriFrame f;
     const bool ok = tri3_frame(X, f); // degenerate: zero scale factors, everything below is a finite zero
-    double C[3], mu[3];
-#pragma unroll
-    for (int e = 0; e < 3; e++) C[e] = f.xs[e] * f.xs[e] + f.ys[e] * f.ys[e];
-    {
-        const double c01 = C[0] * C[1], rall = ok ? 1.0 / (c01 * C[2]) : 0.0; // as tri3_record
-        mu[0] = (C[0] - C[1]) * (c01 * rall);
-        mu[1] = (C[2] - C[0]) * (C[0] * C[2] * rall);
-        mu[2] = (C[1] - C[2]) * (C[1] * C[2] * rall);
-    }
+    double mu[3];
+    specht_mu(f, ok, mu);
     // -M_T A Y^T (1,1,0): rows 0 and 1 of Y (SA:578-588), A / (4 A^2) = inv2a / 2
     const double x31 = f.xs[1], y31 = f.ys[1], x23 = f.xs[2], y23 = f.ys[2];
     const double sp = -mt * (0.5 * f.inv2a);
@@ -104,9 +80,8 @@ __device__ __forceinline__ void tri3_thermal(const double X[9], double nt, doubl
     }
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        constexpr int kPrev[3] = {2, 0, 1}, kRowKi[3] = {1, 0, 2}, kRowJi[3] = {0, 2, 1};
-        const int k = kPrev[i];
-        const double xki = f.xs[kRowKi[i]], yki = f.ys[kRowKi[i]], xji = -f.xs[kRowJi[i]], yji = -f.ys[kRowJi[i]];
+        const int k = tri_prev(i);
+        const double xki = f.xs[tri_row_ki(i)], yki = f.ys[tri_row_ki(i)], xji = -f.xs[tri_row_ji(i)], yji = -f.ys[tri_row_ji(i)];
         // the transposes of u_i = (2, y_ji, -x_ji), v_i = (-2, -y_ki, x_ki), e0 + w_i = (1, y_ki, -x_ki), -e0
         const double a = aQ[i], b = aQ[k], ck = aC[k], ci = aC[i];
         const double fw = 2.0 * (a - b) + (ck - ci);
@@ -121,58 +96,10 @@ __device__ __forceinline__ void tri3_thermal(const double X[9], double nt, doubl
 __device__ __forceinline__ void quad4_thermal(const double X[12], double nt, double mt, double *dst)
 {
 #pragma clang fp reassociate(on) contract(fast) // element math only; parity bar is 1e-12, not bitwise
-    // frame from the mid-side points (SA:342-375), as quad4_record
-    double ex[3], ey[3], ez[3], vr[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const double mI = X[d] + 0.5 * (X[3 + d] - X[d]);
-        const double mJ = X[3 + d] + 0.5 * (X[6 + d] - X[3 + d]);
-        const double mK = X[6 + d] + 0.5 * (X[9 + d] - X[6 + d]);
-        const double mL = X[9 + d] + 0.5 * (X[d] - X[9 + d]);
-        ex[d] = mJ - mL;
-        vr[d] = mK - mI;
-    }
-    const double lx2 = ex[0] * ex[0] + ex[1] * ex[1] + ex[2] * ex[2];
-    bool ok = lx2 > 0.0;
-    const double ilx = ok ? 1.0 / sqrt(lx2) : 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) ex[d] *= ilx;
-    ez[0] = ex[1] * vr[2] - ex[2] * vr[1];
-    ez[1] = ex[2] * vr[0] - ex[0] * vr[2];
-    ez[2] = ex[0] * vr[1] - ex[1] * vr[0];
-    const double lz2 = ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2];
-    ok = ok && lz2 > 0.0;
-    const double ilz = ok ? 1.0 / sqrt(lz2) : 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) ez[d] *= ilz;
-    ey[0] = ez[1] * ex[2] - ez[2] * ex[1];
-    ey[1] = ez[2] * ex[0] - ez[0] * ex[2];
-    ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
-    double x[4], y[4];
-#pragma unroll
-    for (int n = 0; n < 4; n++) {
-        x[n] = ex[0] * X[3 * n] + ex[1] * X[3 * n + 1] + ex[2] * X[3 * n + 2];
-        y[n] = ey[0] * X[3 * n] + ey[1] * X[3 * n + 1] + ey[2] * X[3 * n + 2];
-    }
-    double a2 = 0.0;
-#pragma unroll
-    for (int n = 0; n < 4; n++) a2 += x[n] * y[(n + 1) % 4] - x[(n + 1) % 4] * y[n];
-    ok = ok && fabs(a2) > 0.0;
-    DkqSide sd[4]; // SA:613-621, side s from node s to node s + 1
-#pragma unroll
-    for (int s = 0; s < 4; s++) {
-        const double dx = x[s] - x[(s + 1) % 4], dy = y[s] - y[(s + 1) % 4];
-        const double l2 = dx * dx + dy * dy;
-        const double l = (ok && l2 > 0.0) ? 1.0 / l2 : 0.0;
-        sd[s].a = -dx * l;
-        sd[s].b = 0.75 * dx * dy * l;
-        sd[s].c = (0.25 * dx * dx - 0.5 * dy * dy) * l;
-        sd[s].d = -dy * l;
-        sd[s].e = (0.25 * dy * dy - 0.5 * dx * dx) * l;
-    }
-    const double x12 = x[0] - x[1], y12 = y[0] - y[1], x23 = x[1] - x[2], y23 = y[1] - y[2];
-    const double x34 = x[2] - x[3], y34 = y[2] - y[3], x41 = x[3] - x[0], y41 = y[3] - y[0];
-    const double root = 0.57735026918962576451; // sqrt(1/3)
+    QuadFrame f;
+    const bool ok = quad4_frame(X, f);
+    DkqSide sd[4];
+    dkq_sides(f, ok, sd);
     double fm[4][2], fp[4][3];
 #pragma unroll
     for (int n = 0; n < 4; n++) {
@@ -181,32 +108,26 @@ __device__ __forceinline__ void quad4_thermal(const double X[12], double nt, dou
     }
 #pragma unroll 1 // (one copy of the Gauss-point code: the register budget, as in quad4_means)
     for (int gp = 0; gp < 4; gp++) {
-        const double r = (gp & 2) ? -root : root, s = (gp & 1) ? -root : root; // SA:482-487 order
-        const double J00 = 0.25 * ((x12 + x34) * s - x12 + x34), J01 = 0.25 * ((y12 + y34) * s - y12 + y34);
-        const double J10 = 0.25 * ((x12 + x34) * r - x23 + x41), J11 = 0.25 * ((y12 + y34) * r - y23 + y41);
-        const double det = J00 * J11 - J01 * J10, idet = (ok && det != 0.0) ? 1.0 / det : 0.0;
-        const double wdet = ok ? det : 0.0;
-        const double Ji[4] = {J11 * idet, -J01 * idet, -J10 * idet, J00 * idet};
-        auto corner_x = [&](double rr, double ss) { return 0.25 * rr * (1.0 + s * ss) * (2.0 * r * rr + s * ss); };
-        auto corner_e = [&](double rr, double ss) { return 0.25 * ss * (1.0 + r * rr) * (2.0 * s * ss + r * rr); };
-        const double mid_x[4] = {-r * (1.0 - s), 0.5 * (1.0 - s * s), -r * (1.0 + s), -0.5 * (1.0 - s * s)};
-        const double mid_e[4] = {-0.5 * (1.0 - r * r), -s * (1.0 + r), 0.5 * (1.0 - r * r), -s * (1.0 - r)};
+        const QuadGauss g = quad4_gauss(f, gp, ok);
+        const double wdet = ok ? g.det : 0.0;
 #pragma unroll
         for (int n = 0; n < 4; n++) {
-            const double rn = (n == 1 || n == 2) ? 1.0 : -1.0, sn = (n >= 2) ? 1.0 : -1.0;
-            const double dr = 0.25 * rn * (1.0 + sn * s), ds = 0.25 * sn * (1.0 + rn * r);
-            fm[n][0] += wdet * (Ji[0] * dr + Ji[1] * ds); // dN/dx: Bm^T (1,1,0) = (dN/dx, dN/dy)
-            fm[n][1] += wdet * (Ji[2] * dr + Ji[3] * ds);
+            double bx, by; // Bm^T (1,1,0) = (dN/dx, dN/dy)
+            bilinear_grad(n, g.r, g.s, g.Ji, bx, by);
+            fm[n][0] += wdet * bx;
+            fm[n][1] += wdet * by;
             const int np = (n + 3) & 3;
+            const double rn = quad_corner_r(n), sn = quad_corner_s(n);
             double B[3][3];
-            dkq_node_block(sd[n], sd[np], corner_x(rn, sn), corner_e(rn, sn), mid_x[n], mid_e[n], mid_x[np], mid_e[np], Ji, B);
+            dkq_node_block(sd[n], sd[np], dkq_corner_x(g.r, g.s, rn, sn), dkq_corner_e(g.r, g.s, rn, sn), dkq_mid_x(g.r, g.s, n),
+                           dkq_mid_e(g.r, g.s, n), dkq_mid_x(g.r, g.s, np), dkq_mid_e(g.r, g.s, np), g.Ji, B);
 #pragma unroll
             for (int c = 0; c < 3; c++) fp[n][c] += wdet * (B[0][c] + B[1][c]);
         }
     }
     // f_p = -M_T sum w (-B)^T (1,1,0): the curvature operator is minus the DKQ operator
 #pragma unroll
-    for (int n = 0; n < 4; n++) put_node(dst + 6 * n, ex, ey, ez, nt * fm[n][0], nt * fm[n][1], mt * fp[n][0], mt * fp[n][1], mt * fp[n][2]);
+    for (int n = 0; n < 4; n++) put_node(dst + 6 * n, f.ex, f.ey, f.ez, nt * fm[n][0], nt * fm[n][1], mt * fp[n][0], mt * fp[n][1], mt * fp[n][2]);
 }
 
 } // namespace
@@ -248,61 +169,25 @@ __global__ __launch_bounds__(kThThreads) void k_element_thermal(DeviceMatrix m, 
                     double *dst = s_vec + i * kStride;
                     if (!kHasQuads || c.w < 0) {
                         double X[9];
-#pragma unroll
-                        for (int j = 0; j < 3; j++) {
-                            const double *pt = m.xyz + 3 * (int64_t)nid[j];
-                            X[3 * j + 0] = pt[0];
-                            X[3 * j + 1] = pt[1];
-                            X[3 * j + 2] = pt[2];
-                        }
+                        load_xyz<3>(m.xyz, nid, X);
                         tri3_thermal(X, nT, mT, dst);
                     } else {
                         double X[12];
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            const double *pt = m.xyz + 3 * (int64_t)nid[j];
-                            X[3 * j + 0] = pt[0];
-                            X[3 * j + 1] = pt[1];
-                            X[3 * j + 2] = pt[2];
-                        }
-                        // coordinates relative to the first node, each difference rounded once (as k_element_resultants)
-#pragma unroll
-                        for (int j = 3; j >= 0; j--)
-#pragma unroll
-                            for (int d = 0; d < 3; d++) X[3 * j + d] -= X[d];
+                        load_xyz<4>(m.xyz, nid, X);
+                        relative_to_first(X);
                         quad4_thermal(X, nT, mT, dst);
                     }
-                    uint32_t word = 0;
+                    uint32_t word = 0xFFFFFFFFu;
 #pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const uint32_t r = (uint32_t)(nid[j] - row0); // (a triangle's fourth node, -1, and ghosts fall outside)
-                        const bool in = r < (uint32_t)kSliceNodes;
-                        if (in) rows |= 1u << r;
-                        word |= (in ? r : 0xFFu) << (8 * j);
-                    }
+                    for (int j = 0; j < 4; j++) entry_node(j, nid[j], row0, rows, word);
                     s_node[i] = word;
                 }
-                // the wave's 64 entries are 64 consecutive entries of the list: bit b of the ballot for row r is entry i0 + b
-                for (int r = 0; r < kSliceNodes; r++) {
-                    const unsigned long long has = __ballot((rows >> r) & 1u);
-                    if (lane == r) s_rows[i0 >> 6][r] = has;
-                }
+                publish_rows(rows, lane, s_rows[i0 >> 6]);
             }
             __syncthreads();
             // ---- B: row sums in list order: waves of entries ascending, within one the set bits ascending
-            if (tid < kSliceRows) {
-                for (int c0 = 0; c0 < nt; c0 += 64) {
-                    unsigned long long has = s_rows[c0 >> 6][my_row];
-                    while (has) {
-                        const int i = c0 + __ffsll(has) - 1;
-                        const uint32_t word = s_node[i];
-                        // which node of the entry the row is (a node occurs once in an element)
-                        const int j = (word & 0xFFu) == my_row ? 0 : (((word >> 8) & 0xFFu) == my_row ? 1 : (((word >> 16) & 0xFFu) == my_row ? 2 : 3));
-                        sum += s_vec[i * kStride + 6 * j + my_v];
-                        has &= has - 1;
-                    }
-                }
-            }
+            if (tid < kSliceRows)
+                for_entries_of_row(s_rows, nt, (int)my_row, [&](int i) { sum += s_vec[i * kStride + 6 * entry_node_of_row(s_node[i], my_row) + my_v]; });
             __syncthreads(); // (the next tile overwrites the vectors)
         }
         if (tid < kSliceRows) s_sum[tid] = sum;

@@ -80,72 +80,27 @@ template <int kN> __device__ __forceinline__ bool tri3_coeff(const double X[9], 
 
 __device__ __forceinline__ bool quad4_coeff(const double X[12], const double N[6], double g[10])
 {
-    // frame from the mid-side points, as quad4_means of element_resultants.hip
-    double ex[3], ey[3], ez[3], vr[3];
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-        const double mI = X[d] + 0.5 * (X[3 + d] - X[d]);
-        const double mJ = X[3 + d] + 0.5 * (X[6 + d] - X[3 + d]);
-        const double mK = X[6 + d] + 0.5 * (X[9 + d] - X[6 + d]);
-        const double mL = X[9 + d] + 0.5 * (X[d] - X[9 + d]);
-        ex[d] = mJ - mL;
-        vr[d] = mK - mI;
-    }
-    const double lx2 = ex[0] * ex[0] + ex[1] * ex[1] + ex[2] * ex[2];
-    bool ok = lx2 > 0.0;
-    const double ilx = ok ? 1.0 / sqrt(lx2) : 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) ex[d] *= ilx;
-    ez[0] = ex[1] * vr[2] - ex[2] * vr[1];
-    ez[1] = ex[2] * vr[0] - ex[0] * vr[2];
-    ez[2] = ex[0] * vr[1] - ex[1] * vr[0];
-    const double lz2 = ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2];
-    ok = ok && lz2 > 0.0;
-    const double ilz = ok ? 1.0 / sqrt(lz2) : 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) ez[d] *= ilz;
-    ey[0] = ez[1] * ex[2] - ez[2] * ex[1];
-    ey[1] = ez[2] * ex[0] - ez[0] * ex[2];
-    ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
-    double x[4], y[4];
-#pragma unroll
-    for (int n = 0; n < 4; n++) {
-        x[n] = ex[0] * X[3 * n] + ex[1] * X[3 * n + 1] + ex[2] * X[3 * n + 2];
-        y[n] = ey[0] * X[3 * n] + ey[1] * X[3 * n + 1] + ey[2] * X[3 * n + 2];
-    }
-    double a2 = 0.0;
-#pragma unroll
-    for (int n = 0; n < 4; n++) a2 += x[n] * y[(n + 1) % 4] - x[(n + 1) % 4] * y[n];
-    ok = ok && fabs(a2) > 0.0;
+    QuadFrame f;
+    bool ok = quad4_frame(X, f);
+    const double *ex = f.ex, *ey = f.ey;
     // N in the element frame
     double Nx[3], Ny[3];
     sym_apply(N, ex, Nx);
     sym_apply(N, ey, Ny);
     const double nxx = ex[0] * Nx[0] + ex[1] * Nx[1] + ex[2] * Nx[2], nyy = ey[0] * Ny[0] + ey[1] * Ny[1] + ey[2] * Ny[2];
     const double nxy = ex[0] * Ny[0] + ex[1] * Ny[1] + ex[2] * Ny[2];
-    const double x12 = x[0] - x[1], y12 = y[0] - y[1], x23 = x[1] - x[2], y23 = y[1] - y[2];
-    const double x34 = x[2] - x[3], y34 = y[2] - y[3], x41 = x[3] - x[0], y41 = y[3] - y[0];
-    const double root = 0.57735026918962576451; // sqrt(1/3)
 #pragma unroll
     for (int q = 0; q < 10; q++) g[q] = 0.0;
 #pragma unroll
     for (int gp = 0; gp < 4; gp++) {
-        const double r = (gp & 2) ? -root : root, s = (gp & 1) ? -root : root;
-        const double J00 = 0.25 * ((x12 + x34) * s - x12 + x34), J01 = 0.25 * ((y12 + y34) * s - y12 + y34);
-        const double J10 = 0.25 * ((x12 + x34) * r - x23 + x41), J11 = 0.25 * ((y12 + y34) * r - y23 + y41);
-        const double det = J00 * J11 - J01 * J10;
-        ok = ok && det != 0.0;
-        const double idet = ok ? 1.0 / det : 0.0;
-        const double Ji[4] = {J11 * idet, -J01 * idet, -J10 * idet, J00 * idet};
+        const QuadGauss gq = quad4_gauss(f, gp, ok);
+        ok = ok && gq.det != 0.0; // (a vanishing determinant at one Gauss point rejects the element)
         double bx[4], by[4], sx[4], sy[4];
 #pragma unroll
         for (int n = 0; n < 4; n++) {
-            const double rn = (n == 1 || n == 2) ? 1.0 : -1.0, sn = (n >= 2) ? 1.0 : -1.0;
-            const double dr = 0.25 * rn * (1.0 + sn * s), ds = 0.25 * sn * (1.0 + rn * r);
-            bx[n] = Ji[0] * dr + Ji[1] * ds;
-            by[n] = Ji[2] * dr + Ji[3] * ds;
-            sx[n] = det * (nxx * bx[n] + nxy * by[n]); // w N grad phi_b
-            sy[n] = det * (nxy * bx[n] + nyy * by[n]);
+            bilinear_grad(n, gq.r, gq.s, gq.Ji, bx[n], by[n]);
+            sx[n] = gq.det * (nxx * bx[n] + nxy * by[n]); // w N grad phi_b
+            sy[n] = gq.det * (nxy * bx[n] + nyy * by[n]);
         }
 #pragma unroll
         for (int a = 0; a < 4; a++)
@@ -179,31 +134,16 @@ __global__ __launch_bounds__(kGcThreads) void k_geometric_coeff(DeviceMatrix m, 
     bool ok;
     if (!kHasQuads || e < m.n_ltri) {
         const int32_t *c = m.tri + 3 * e64;
+        const int nid[3] = {c[0], c[1], c[2]};
         double X[9];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-            const double *pt = m.xyz + 3 * (int64_t)c[i];
-            X[3 * i + 0] = pt[0];
-            X[3 * i + 1] = pt[1];
-            X[3 * i + 2] = pt[2];
-        }
+        load_xyz<3>(m.xyz, nid, X);
         ok = tri3_coeff<kN>(X, N, g);
     } else {
         const int4 c = reinterpret_cast<const int4 *>(m.quad)[e - m.n_ltri];
         const int nid[4] = {c.x, c.y, c.z, c.w};
         double X[12];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const double *pt = m.xyz + 3 * (int64_t)nid[i];
-            X[3 * i + 0] = pt[0];
-            X[3 * i + 1] = pt[1];
-            X[3 * i + 2] = pt[2];
-        }
-        // relative to the first node, as k_element_resultants hands them to quad4_means (quad4_coeff differences projections)
-#pragma unroll
-        for (int i = 3; i >= 0; i--)
-#pragma unroll
-            for (int d = 0; d < 3; d++) X[3 * i + d] -= X[d];
+        load_xyz<4>(m.xyz, nid, X);
+        relative_to_first(X);
         ok = quad4_coeff(X, N, g);
     }
     if (!ok) report_status(m.status, kStatusDirect + e);
@@ -224,7 +164,7 @@ __global__ __launch_bounds__(geo_threads(kCols)) void k_geometric_product(Device
     static_assert(kGpTile % 64 == 0 && kThreads % 64 == 0 && kThreads >= kSliceNodes * kRowItems, "whole waves; a lane per (row, translation, column)");
     __shared__ double s_y[kGpTile * kEntry];
     __shared__ unsigned long long s_rows[kGpTile / 64][kSliceNodes]; // per wave of entries and row: the entries that contain the row
-    __shared__ uint32_t s_pos[kGpTile];                              // per entry: byte j = the slice row of its node j (255: none)
+    __shared__ uint32_t s_node[kGpTile];                             // per entry: byte j = the slice row of its node j (0xFF: none)
     __shared__ double s_sum[kSliceNodes * kRowItems];
     const int tid = threadIdx.x, lane = tid & 63;
     SliceWalk w(m.n_slices);
@@ -253,16 +193,10 @@ __global__ __launch_bounds__(geo_threads(kCols)) void k_geometric_product(Device
                         g[2 * q + 1] = v.y;
                     }
                     const int nid[4] = {c.x, c.y, c.z, kHasQuads ? c.w : -1};
-                    uint32_t pos = 0xFFFFFFFFu;
+                    uint32_t word = 0xFFFFFFFFu;
 #pragma unroll
-                    for (int j = 0; j < kN; j++) {
-                        const uint32_t r = (uint32_t)(nid[j] - row0); // (a triangle's fourth node, -1, and ghosts fall outside)
-                        if (r < (uint32_t)kSliceNodes) {
-                            rows |= 1u << r;
-                            pos = (pos & ~(0xFFu << (8 * j))) | (r << (8 * j));
-                        }
-                    }
-                    s_pos[i] = pos;
+                    for (int j = 0; j < kN; j++) entry_node(j, nid[j], row0, rows, word);
+                    s_node[i] = word;
 #pragma unroll
                     for (int col = 0; col < kCols; col++) {
                         const double *xc = X + (int64_t)col * ld;
@@ -290,26 +224,14 @@ __global__ __launch_bounds__(geo_threads(kCols)) void k_geometric_product(Device
                             }
                     }
                 }
-                // the wave's 64 entries are 64 consecutive entries of the list: bit b of the ballot for row r is entry i0 + b
-                for (int r = 0; r < kSliceNodes; r++) {
-                    const unsigned long long has = __ballot((rows >> r) & 1u);
-                    if (lane == r) s_rows[i0 >> 6][r] = has;
-                }
+                publish_rows(rows, lane, s_rows[i0 >> 6]);
             }
             __syncthreads();
             // ---- B: row sums in list order: waves of entries ascending, within one the set bits ascending
-            if (tid < kSliceNodes * kRowItems) {
-                for (int c0 = 0; c0 < nt; c0 += 64) {
-                    unsigned long long has = s_rows[c0 >> 6][my_row];
-                    while (has) {
-                        const int i = c0 + __ffsll(has) - 1;
-                        const uint32_t pos = s_pos[i];
-                        const int a = (pos & 0xFFu) == (uint32_t)my_row ? 0 : ((pos >> 8) & 0xFFu) == (uint32_t)my_row ? 1 : ((pos >> 16) & 0xFFu) == (uint32_t)my_row ? 2 : 3;
-                        sum += s_y[i * kEntry + a * kRowItems + my_item];
-                        has &= has - 1;
-                    }
-                }
-            }
+            if (tid < kSliceNodes * kRowItems)
+                for_entries_of_row(s_rows, nt, my_row, [&](int i) {
+                    sum += s_y[i * kEntry + entry_node_of_row(s_node[i], (uint32_t)my_row) * kRowItems + my_item];
+                });
             __syncthreads(); // (the next tile overwrites the products)
         }
         if (tid < kSliceNodes * kRowItems) s_sum[tid] = sum;

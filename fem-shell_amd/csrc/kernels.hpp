@@ -196,7 +196,7 @@ void launch_element_product(const DeviceMatrix &m, const MatConst &mc, const Dev
 // products only), nullptr otherwise.  One lane per element, no atomics: two launches give the same bits.  A degenerate element
 // writes zeros and reports kStatusDirect + its index through m.status.
 // thermal != nullptr: temperatures are in force: N_loc = t Dm (eps - eps0), M_loc = -Dp (kappa - kappa0) with the
-// element's (Tm, Tg) and alpha -- the thermal instantiations of the kernel; nullptr launches the instantiations without, untouched.
+// element's (Tm, Tg) and alpha -- the kThermal instantiations of the kernel; nullptr launches the instantiations without.
 struct ThermalView;
 void launch_element_resultants(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const double *sec_t, const double *u,
                                const double *up, double *out, hipStream_t st, const ThermalView *thermal = nullptr);

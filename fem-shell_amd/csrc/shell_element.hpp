@@ -129,6 +129,58 @@ __device__ __forceinline__ bool tri3_frame(const double X[9], TriFrame &f)
     return ok;
 }
 
+// the coordinates of an element's kN nodes
+template <int kN> __device__ __forceinline__ void load_xyz(const double *xyz, const int nid[], double X[])
+{
+#pragma unroll
+    for (int i = 0; i < kN; i++) {
+        const double *pt = xyz + 3 * (int64_t)nid[i];
+        X[3 * i + 0] = pt[0];
+        X[3 * i + 1] = pt[1];
+        X[3 * i + 2] = pt[2];
+    }
+}
+// A quadrilateral's coordinates relative to its first node, each difference rounded once: the derived kernels' QUAD4 math
+// projects the coordinates it is given onto the frame and differences the projections, which at a distance D from the origin
+// costs D / size digits
+__device__ __forceinline__ void relative_to_first(double X[12])
+{
+#pragma unroll
+    for (int i = 3; i >= 0; i--)
+#pragma unroll
+        for (int d = 0; d < 3; d++) X[3 * i + d] -= X[d];
+}
+
+// Specht's side ratios (SA:702-704): (C0-C1)/C2, (C2-C0)/C1, (C1-C2)/C0, C_e the squared length of side e, with one division;
+// zeros for a degenerate triangle
+__device__ __forceinline__ void specht_mu(const TriFrame &f, bool ok, double mu[3])
+{
+#pragma clang fp reassociate(on) contract(fast) // element math only; parity bar is 1e-12, not bitwise
+    double C[3];
+#pragma unroll
+    for (int e = 0; e < 3; e++) C[e] = f.xs[e] * f.xs[e] + f.ys[e] * f.ys[e];
+    const double c01 = C[0] * C[1], rall = ok ? 1.0 / (c01 * C[2]) : 0.0;
+    mu[0] = (C[0] - C[1]) * (c01 * rall);
+    mu[1] = (C[2] - C[0]) * (C[0] * C[2] * rall);
+    mu[2] = (C[1] - C[2]) * (C[1] * C[2] * rall);
+}
+// sum over the three Gauss points of Specht's tables: sum_g Q_n(g)[r] = a[n][r] + mu_{(n+2)%3} b[n][r]
+struct SpechtSums {
+    double a[3][3], b[3][3];
+};
+constexpr SpechtSums specht_sums()
+{
+    constexpr double QA[3][3][3] = SPECHT_QA_INIT;
+    constexpr double QB[3][3][3] = SPECHT_QB_INIT;
+    SpechtSums s{};
+    for (int n = 0; n < 3; n++)
+        for (int r = 0; r < 3; r++) {
+            s.a[n][r] = QA[n][0][r] + QA[n][1][r] + QA[n][2][r];
+            s.b[n][r] = QB[n][0][r] + QB[n][1][r] + QB[n][2][r];
+        }
+    return s;
+}
+
 // ---- per-element record ---------------------------------------------------------------
 // Everything about a TRI3 element that does not depend on which node block is wanted.  The
 // assembly kernel computes it once per element and slice and keeps it in LDS.
@@ -225,16 +277,8 @@ __device__ __forceinline__ bool tri3_record(const double X[9], const MatConst &m
         rec[9 + d] = f.xs[d];
         rec[12 + d] = f.ys[d];
     }
-    double C[3], mu[3];
-#pragma unroll
-    for (int e = 0; e < 3; e++) C[e] = f.xs[e] * f.xs[e] + f.ys[e] * f.ys[e];
-    {
-        // SA:702-704: (C0-C1)/C2, (C2-C0)/C1, (C1-C2)/C0 with one division
-        const double c01 = C[0] * C[1], rall = ok ? 1.0 / (c01 * C[2]) : 0.0;
-        mu[0] = (C[0] - C[1]) * (c01 * rall);
-        mu[1] = (C[2] - C[0]) * (C[0] * C[2] * rall);
-        mu[2] = (C[1] - C[2]) * (C[1] * C[2] * rall);
-    }
+    double mu[3];
+    specht_mu(f, ok, mu);
     // Y (SA:578-588) and Dt = Y^T Dp Y (symmetric)
     const double A = f.area;
     const double x31 = f.xs[1], y31 = f.ys[1], x23 = f.xs[2], y23 = f.ys[2];
@@ -520,102 +564,162 @@ __device__ __forceinline__ void tri3_diag_add_rec(const double *rec, int ia, con
 struct DkqSide {
     double a, b, c, d, e;
 };
-__device__ __forceinline__ DkqSide dkq_side(double x, double y)
-{
-    const double l = 1.0 / (x * x + y * y);
-    DkqSide s;
-    s.a = -x * l;
-    s.b = 0.75 * x * y * l;
-    s.c = (0.25 * x * x - 0.5 * y * y) * l;
-    s.d = -y * l;
-    s.e = (0.25 * y * y - 0.5 * x * x) * l;
-    return s;
-}
 
-// SA:342-375: frame from the mid-side points; local coordinates are T*X without translation.
-__device__ __forceinline__ bool quad4_record(const double X[12], const MatConst &mc, double rec[kRecDoublesQuad])
+// The QUAD4 geometry every kernel with quadrilaterals shares -- the record of the assembly and of the element product, the
+// resultants, the thermal loads, the geometric coefficients.  No `#pragma clang fp` here: the functions keep the floating-point
+// mode quad4_record has always had, whatever their caller's is (the pragma is lexical), so the assembly's bits do not depend on
+// who else calls them.
+struct QuadFrame {
+    double ex[3], ey[3], ez[3]; // rows of trafo
+    double x[4], y[4];          // local coordinates of the nodes: T*X without translation
+};
+// SA:342-375: frame from the mid-side points.  Returns false for a degenerate quadrilateral (a mid-side axis of length zero, or
+// zero area: the Jacobian determinant must not vanish at the Gauss points).  No early returns (they left part of the caller's
+// record array in scratch memory, see tri3_frame): a degenerate quad gets zero scale factors.
+__device__ __forceinline__ bool quad4_frame(const double X[12], QuadFrame &f)
 {
-    (void)mc;
-#pragma unroll
-    for (int i = 0; i < kRecDoublesQuad; i++) rec[i] = 0.0;
-    double ex[3], ey[3], ez[3], vr[3];
+    double vr[3];
 #pragma unroll
     for (int d = 0; d < 3; d++) {
         const double mI = X[d] + 0.5 * (X[3 + d] - X[d]);          // mid AB
         const double mJ = X[3 + d] + 0.5 * (X[6 + d] - X[3 + d]);  // mid BC
         const double mK = X[6 + d] + 0.5 * (X[9 + d] - X[6 + d]);  // mid CD
         const double mL = X[9 + d] + 0.5 * (X[d] - X[9 + d]);      // mid DA
-        ex[d] = mJ - mL;
+        f.ex[d] = mJ - mL;
         vr[d] = mK - mI;
     }
-    // no early returns (they left part of the record array in scratch memory, see tri3_frame): a degenerate quad gets
-    // zero scale factors and kind 0, which block_add_rec treats as an all-zero triangle record
-    const double lx2 = ex[0] * ex[0] + ex[1] * ex[1] + ex[2] * ex[2];
+    const double lx2 = f.ex[0] * f.ex[0] + f.ex[1] * f.ex[1] + f.ex[2] * f.ex[2];
     bool ok = lx2 > 0.0;
     const double ilx = ok ? 1.0 / sqrt(lx2) : 0.0;
 #pragma unroll
-    for (int d = 0; d < 3; d++) ex[d] *= ilx;
-    ez[0] = ex[1] * vr[2] - ex[2] * vr[1];
-    ez[1] = ex[2] * vr[0] - ex[0] * vr[2];
-    ez[2] = ex[0] * vr[1] - ex[1] * vr[0];
-    const double lz2 = ez[0] * ez[0] + ez[1] * ez[1] + ez[2] * ez[2];
+    for (int d = 0; d < 3; d++) f.ex[d] *= ilx;
+    f.ez[0] = f.ex[1] * vr[2] - f.ex[2] * vr[1];
+    f.ez[1] = f.ex[2] * vr[0] - f.ex[0] * vr[2];
+    f.ez[2] = f.ex[0] * vr[1] - f.ex[1] * vr[0];
+    const double lz2 = f.ez[0] * f.ez[0] + f.ez[1] * f.ez[1] + f.ez[2] * f.ez[2];
     ok = ok && lz2 > 0.0;
     const double ilz = ok ? 1.0 / sqrt(lz2) : 0.0;
 #pragma unroll
-    for (int d = 0; d < 3; d++) ez[d] *= ilz;
-    ey[0] = ez[1] * ex[2] - ez[2] * ex[1];
-    ey[1] = ez[2] * ex[0] - ez[0] * ex[2];
-    ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
+    for (int d = 0; d < 3; d++) f.ez[d] *= ilz;
+    f.ey[0] = f.ez[1] * f.ex[2] - f.ez[2] * f.ex[1];
+    f.ey[1] = f.ez[2] * f.ex[0] - f.ez[0] * f.ex[2];
+    f.ey[2] = f.ez[0] * f.ex[1] - f.ez[1] * f.ex[0];
+#pragma unroll
+    for (int n = 0; n < 4; n++) {
+        f.x[n] = f.ex[0] * X[3 * n] + f.ex[1] * X[3 * n + 1] + f.ex[2] * X[3 * n + 2];
+        f.y[n] = f.ey[0] * X[3 * n] + f.ey[1] * X[3 * n + 1] + f.ey[2] * X[3 * n + 2];
+    }
+    double a2 = 0.0;
+#pragma unroll
+    for (int n = 0; n < 4; n++) a2 += f.x[n] * f.y[(n + 1) % 4] - f.x[(n + 1) % 4] * f.y[n];
+    return ok && fabs(a2) > 0.0;
+}
+// Gauss point gp of the 2 x 2 rule (SA:482-487 order): natural coordinates, the Jacobian of the bilinear map (SA:489-538 and
+// SA:641-684 use the same four numbers), its determinant and its inverse -- zero where the element is degenerate or det is
+struct QuadGauss {
+    double r, s;
+    double Ji[4];
+    double det;
+};
+__device__ __forceinline__ QuadGauss quad4_gauss(const QuadFrame &f, int gp, bool ok)
+{
+    const double *x = f.x, *y = f.y;
+    const double x12 = x[0] - x[1], y12 = y[0] - y[1], x23 = x[1] - x[2], y23 = y[1] - y[2];
+    const double x34 = x[2] - x[3], y34 = y[2] - y[3], x41 = x[3] - x[0], y41 = y[3] - y[0];
+    const double root = 0.57735026918962576451; // sqrt(1/3)
+    QuadGauss g;
+    g.r = (gp & 2) ? -root : root;
+    g.s = (gp & 1) ? -root : root;
+    const double J00 = 0.25 * ((x12 + x34) * g.s - x12 + x34), J01 = 0.25 * ((y12 + y34) * g.s - y12 + y34);
+    const double J10 = 0.25 * ((x12 + x34) * g.r - x23 + x41), J11 = 0.25 * ((y12 + y34) * g.r - y23 + y41);
+    g.det = J00 * J11 - J01 * J10;
+    const double idet = (ok && g.det != 0.0) ? 1.0 / g.det : 0.0;
+    g.Ji[0] = J11 * idet;
+    g.Ji[1] = -J01 * idet;
+    g.Ji[2] = -J10 * idet;
+    g.Ji[3] = J00 * idet;
+    return g;
+}
+// natural coordinates of corner n: (-1,-1), (1,-1), (1,1), (-1,1)
+__device__ __forceinline__ double quad_corner_r(int n) { return (n == 1 || n == 2) ? 1.0 : -1.0; }
+__device__ __forceinline__ double quad_corner_s(int n) { return (n >= 2) ? 1.0 : -1.0; }
+// (dN/dx, dN/dy) of the bilinear shape function of corner n at the natural point (r, s)
+__device__ __forceinline__ void bilinear_grad(int n, double r, double s, const double Ji[4], double &bx, double &by)
+{
+    const double rn = quad_corner_r(n), sn = quad_corner_s(n);
+    const double dr = 0.25 * rn * (1.0 + sn * s), ds = 0.25 * sn * (1.0 + rn * r);
+    bx = Ji[0] * dr + Ji[1] * ds;
+    by = Ji[2] * dr + Ji[3] * ds;
+}
+// side coefficients of the plate part (they do not depend on the Gauss point nor on the block): side s from node s to node
+// s+1, differences as in SA:413-424; zeros for a degenerate element or a side of length zero
+__device__ __forceinline__ void dkq_sides(const QuadFrame &f, bool ok, DkqSide sd[4])
+{
+#pragma unroll
+    for (int s = 0; s < 4; s++) {
+        const double dx = f.x[s] - f.x[(s + 1) % 4], dy = f.y[s] - f.y[(s + 1) % 4];
+        const double l2 = dx * dx + dy * dy;
+        const double l = (ok && l2 > 0.0) ? 1.0 / l2 : 0.0;
+        sd[s].a = -dx * l;
+        sd[s].b = 0.75 * dx * dy * l;
+        sd[s].c = (0.25 * dx * dx - 0.5 * dy * dy) * l;
+        sd[s].d = -dy * l;
+        sd[s].e = (0.25 * dy * dy - 0.5 * dx * dx) * l;
+    }
+}
+// serendipity derivatives (SA:906-923) at (r, s), xi then eta: of the corner with natural coordinates (rr, ss), and of the
+// mid-side node of side sd (nodes 5..8)
+__device__ __forceinline__ double dkq_corner_x(double r, double s, double rr, double ss) { return 0.25 * rr * (1.0 + s * ss) * (2.0 * r * rr + s * ss); }
+__device__ __forceinline__ double dkq_corner_e(double r, double s, double rr, double ss) { return 0.25 * ss * (1.0 + r * rr) * (2.0 * s * ss + r * rr); }
+__device__ __forceinline__ double dkq_mid_x(double r, double s, int sd)
+{
+    return sd == 0 ? -r * (1.0 - s) : (sd == 1 ? 0.5 * (1.0 - s * s) : (sd == 2 ? -r * (1.0 + s) : -0.5 * (1.0 - s * s)));
+}
+__device__ __forceinline__ double dkq_mid_e(double r, double s, int sd)
+{
+    return sd == 0 ? -0.5 * (1.0 - r * r) : (sd == 1 ? -s * (1.0 + r) : (sd == 2 ? 0.5 * (1.0 - r * r) : -s * (1.0 - r)));
+}
+
+// The QUAD4 record: frame, local coordinates, per Gauss point the inverse Jacobian and its determinant, the side coefficients.
+// A degenerate quad gets kind 0 and an all-zero record, which block_add_rec treats as an all-zero triangle record.
+__device__ __forceinline__ bool quad4_record(const double X[12], const MatConst &mc, double rec[kRecDoublesQuad])
+{
+    (void)mc;
+#pragma unroll
+    for (int i = 0; i < kRecDoublesQuad; i++) rec[i] = 0.0;
+    QuadFrame f;
+    const bool ok = quad4_frame(X, f);
 #pragma unroll
     for (int d = 0; d < 3; d++) {
-        rec[d] = ex[d];
-        rec[3 + d] = ey[d];
-        rec[6 + d] = ez[d];
+        rec[d] = f.ex[d];
+        rec[3 + d] = f.ey[d];
+        rec[6 + d] = f.ez[d];
     }
 #pragma unroll
     for (int n = 0; n < 4; n++) {
-        rec[kQuadX + n] = ex[0] * X[3 * n] + ex[1] * X[3 * n + 1] + ex[2] * X[3 * n + 2];
-        rec[kQuadY + n] = ey[0] * X[3 * n] + ey[1] * X[3 * n + 1] + ey[2] * X[3 * n + 2];
+        rec[kQuadX + n] = f.x[n];
+        rec[kQuadY + n] = f.y[n];
     }
-    // the Jacobian determinant must not vanish at the Gauss points; a zero-area quad is rejected here
-    double a2 = 0.0;
 #pragma unroll
-    for (int n = 0; n < 4; n++) a2 += rec[kQuadX + n] * rec[kQuadY + (n + 1) % 4] - rec[kQuadX + (n + 1) % 4] * rec[kQuadY + n];
-    ok = ok && fabs(a2) > 0.0;
-    // Jacobian of the bilinear map at the four Gauss points (SA:482-487 order; SA:489-538 and SA:641-684 use the
-    // same four numbers), its inverse and determinant
-    {
-        const double *x = rec + kQuadX, *y = rec + kQuadY;
-        const double x12 = x[0] - x[1], y12 = y[0] - y[1], x23 = x[1] - x[2], y23 = y[1] - y[2];
-        const double x34 = x[2] - x[3], y34 = y[2] - y[3], x41 = x[3] - x[0], y41 = y[3] - y[0];
-        const double root = 0.57735026918962576451; // sqrt(1/3)
-#pragma unroll
-        for (int gp = 0; gp < 4; gp++) {
-            const double r = (gp & 2) ? -root : root, s = (gp & 1) ? -root : root;
-            const double J00 = 0.25 * ((x12 + x34) * s - x12 + x34), J01 = 0.25 * ((y12 + y34) * s - y12 + y34);
-            const double J10 = 0.25 * ((x12 + x34) * r - x23 + x41), J11 = 0.25 * ((y12 + y34) * r - y23 + y41);
-            const double det = J00 * J11 - J01 * J10, idet = (ok && det != 0.0) ? 1.0 / det : 0.0;
-            double *g = rec + kQuadGp + 5 * gp;
-            g[0] = J11 * idet;
-            g[1] = -J01 * idet;
-            g[2] = -J10 * idet;
-            g[3] = J00 * idet;
-            g[4] = det;
-        }
+    for (int gp = 0; gp < 4; gp++) {
+        const QuadGauss g = quad4_gauss(f, gp, ok);
+        double *q = rec + kQuadGp + 5 * gp;
+        q[0] = g.Ji[0];
+        q[1] = g.Ji[1];
+        q[2] = g.Ji[2];
+        q[3] = g.Ji[3];
+        q[4] = g.det;
     }
-    // side coefficients of the plate part (they do not depend on the Gauss point nor on the block): side s from node s
-    // to node s+1, differences as in SA:413-424
+    DkqSide sd[4];
+    dkq_sides(f, ok, sd);
 #pragma unroll
-    for (int sd = 0; sd < 4; sd++) {
-        const double dx = rec[kQuadX + sd] - rec[kQuadX + (sd + 1) % 4], dy = rec[kQuadY + sd] - rec[kQuadY + (sd + 1) % 4];
-        const double l2 = dx * dx + dy * dy;
-        const double l = (ok && l2 > 0.0) ? 1.0 / l2 : 0.0;
-        double *q = rec + kQuadSide + 5 * sd;
-        q[0] = -dx * l;
-        q[1] = 0.75 * dx * dy * l;
-        q[2] = (0.25 * dx * dx - 0.5 * dy * dy) * l;
-        q[3] = -dy * l;
-        q[4] = (0.25 * dy * dy - 0.5 * dx * dx) * l;
+    for (int s = 0; s < 4; s++) {
+        double *q = rec + kQuadSide + 5 * s;
+        q[0] = sd[s].a;
+        q[1] = sd[s].b;
+        q[2] = sd[s].c;
+        q[3] = sd[s].d;
+        q[4] = sd[s].e;
     }
     rec[kRecKind] = ok ? 2.0 : 0.0;
     if (!ok) {
@@ -652,9 +756,7 @@ __device__ __forceinline__ void quad4_block_add_rec(const double *rec, int ia, i
 {
     // node data by dynamic index straight from the record (LDS or registers), no selects
     const int ia_p = (ia + 3) & 3, ib_p = (ib + 3) & 3; // side s runs from node s to node s+1: a node sees sides s and s-1
-    // natural coordinates of the corner nodes: (-1,-1), (1,-1), (1,1), (-1,1)
-    const double ri = (ia == 1 || ia == 2) ? 1.0 : -1.0, si = (ia >= 2) ? 1.0 : -1.0;
-    const double rj = (ib == 1 || ib == 2) ? 1.0 : -1.0, sj = (ib >= 2) ? 1.0 : -1.0;
+    const double ri = quad_corner_r(ia), si = quad_corner_s(ia), rj = quad_corner_r(ib), sj = quad_corner_s(ib);
     auto side = [&](int sd) {
         const double *q = rec + kQuadSide + 5 * sd;
         DkqSide r;
@@ -687,19 +789,12 @@ __device__ __forceinline__ void quad4_block_add_rec(const double *rec, int ia, i
         }
         // ---- plate
         {
-            // serendipity derivatives (SA:906-923): corner n, mid-side of side s (nodes 5..8)
-            auto corner_x = [&](double rr, double ss) { return 0.25 * rr * (1.0 + s * ss) * (2.0 * r * rr + s * ss); };
-            auto corner_e = [&](double rr, double ss) { return 0.25 * ss * (1.0 + r * rr) * (2.0 * s * ss + r * rr); };
-            auto mid_x = [&](int sd) {
-                return sd == 0 ? -r * (1.0 - s) : (sd == 1 ? 0.5 * (1.0 - s * s) : (sd == 2 ? -r * (1.0 + s) : -0.5 * (1.0 - s * s)));
-            };
-            auto mid_e = [&](int sd) {
-                return sd == 0 ? -0.5 * (1.0 - r * r) : (sd == 1 ? -s * (1.0 + r) : (sd == 2 ? 0.5 * (1.0 - r * r) : -s * (1.0 - r)));
-            };
             double Bi[3][3], Bj[3][3];
-            dkq_node_block(sa_i, sb_i, corner_x(ri, si), corner_e(ri, si), mid_x(ia), mid_e(ia), mid_x(ia_p), mid_e(ia_p), Ji, Bi);
+            dkq_node_block(sa_i, sb_i, dkq_corner_x(r, s, ri, si), dkq_corner_e(r, s, ri, si), dkq_mid_x(r, s, ia), dkq_mid_e(r, s, ia),
+                           dkq_mid_x(r, s, ia_p), dkq_mid_e(r, s, ia_p), Ji, Bi);
             if (ia != ib) { // (the work items of the diagonal slots sit together in the first wave: it skips this as a whole)
-                dkq_node_block(sa_j, sb_j, corner_x(rj, sj), corner_e(rj, sj), mid_x(ib), mid_e(ib), mid_x(ib_p), mid_e(ib_p), Ji, Bj);
+                dkq_node_block(sa_j, sb_j, dkq_corner_x(r, s, rj, sj), dkq_corner_e(r, s, rj, sj), dkq_mid_x(r, s, ib), dkq_mid_e(r, s, ib),
+                               dkq_mid_x(r, s, ib_p), dkq_mid_e(r, s, ib_p), Ji, Bj);
             } else {
 #pragma unroll
                 for (int a = 0; a < 3; a++)
