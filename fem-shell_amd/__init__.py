@@ -20,6 +20,8 @@ from .binding import (  # noqa: F401
     KERNEL_ELEMENT_RESULTANTS,
     KERNEL_ELEMENT_THERMAL,
     KERNEL_GEOMETRIC_PRODUCT,
+    KERNEL_NODAL_RECOVERY,
+    KERNEL_RECOVERY_ERROR,
     KERNEL_SPMV,
     REASSEMBLE_EACH_SOLVE,
     REF_DEFAULT,
@@ -38,6 +40,7 @@ from .binding import (  # noqa: F401
     build_plan,
     plan_node_normals,
     reorder_host,
+    relative_error,
     DERIVED_PRODUCTS,
     STATE_CHANGES,
     stale_after,

@@ -23,6 +23,8 @@ KERNEL_ELEMENT_RESULTANTS = 12
 KERNEL_ELEMENT_LOADS = 13
 KERNEL_GEOMETRIC_PRODUCT = 14
 KERNEL_ELEMENT_THERMAL = 15
+KERNEL_NODAL_RECOVERY = 16
+KERNEL_RECOVERY_ERROR = 17
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -38,6 +40,7 @@ SYMBOLS = [
     "femshell_dynamics_accept", "femshell_dynamics_state", "femshell_dynamics_energy", "femshell_dynamics_end",
     "femshell_modal_defaults", "femshell_modes", "femshell_spmm", "femshell_modal_gram",
     "femshell_set_prescribed", "femshell_reactions", "femshell_element_product", "femshell_element_resultants",
+    "femshell_nodal_resultants",
     "femshell_set_element_loads", "femshell_element_load_vector",
     "femshell_set_expansion", "femshell_set_thermal", "femshell_thermal_load_vector",
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
@@ -46,6 +49,17 @@ SYMBOLS = [
     "femshell_krylov_grid", "femshell_krylov_set", "femshell_krylov_get", "femshell_krylov_launch", "femshell_cg_reduce",
     "femshell_modal_combine", "femshell_modal_residual", "femshell_modal_block_jacobi", "femshell_modal_mask", "femshell_modal_start",
 ]
+
+
+def relative_error(elems):
+    """sqrt(sum eta^2 / (sum e2 + sum eta^2)) of the element rows FemShell.nodal_resultants returns, summed in their order (0 for
+    a mesh that carries nothing)"""
+    elems = np.asarray(elems, dtype=np.float64).reshape(-1, 2)
+    e2 = eta2 = 0.0
+    for a, b in elems:
+        e2 += a
+        eta2 += b
+    return float(np.sqrt(eta2 / (e2 + eta2))) if e2 + eta2 > 0.0 else 0.0
 
 
 class FemShellError(RuntimeError):
@@ -230,6 +244,7 @@ def load_library():
     L.femshell_reactions.argtypes = [vp, dp, dp]
     L.femshell_element_product.argtypes = [vp, dp, dp]
     L.femshell_element_resultants.argtypes = [vp, dp, dp]
+    L.femshell_nodal_resultants.argtypes = [vp, dp, dp, dp]
     L.femshell_set_element_loads.argtypes = [vp, dp, dp]
     L.femshell_element_load_vector.argtypes = [vp, dp]
     L.femshell_set_expansion.argtypes = [vp, C.c_double, C.c_int32, dp]
@@ -378,6 +393,19 @@ class FemShell:
         out = np.zeros((self.n_tri + self.n_quad, 14))
         _check(self._L.femshell_element_resultants(self._h, _d(self._node_vector(u, "u")), _d(out)))
         return out
+
+    def nodal_resultants(self, u=None):
+        """The element tensors averaged to the nodes and the Zienkiewicz-Zhu indicator of the difference (femshell_nodal_resultants):
+        (nodes (n_nodes, 14), elems (n_tri + n_quad, 2)).  nodes: N* [0:6] and M* [6:12], the area-weighted averages of the rows of
+        element_resultants over the elements at the node, W = sum A_e [12] and the fold measure 1 - |sum a_e| / W [13] (0 on a flat,
+        consistently oriented neighbourhood: where it is not, the average of M means little).  elems: e2 [0], twice the complementary
+        energy of the element means, and eta^2 [1], the energy of the difference between the recovered field and the element's own
+        value; relative_error(elems) is the mesh's figure.  At folds and section changes the jump is physical and counts as error.
+        u None: the solution of the last solve, prescribed part included."""
+        nodes = np.zeros((self.n_nodes, 14))
+        elems = np.zeros((self.n_tri + self.n_quad, 2))
+        _check(self._L.femshell_nodal_resultants(self._h, _d(self._node_vector(u, "u")), _d(nodes), _d(elems)))
+        return nodes, elems
 
     def set_element_loads(self, tri_load=None, quad_load=None):
         """Pressure and traction per element (femshell_set_element_loads): tri_load is (n_tri, 4), quad_load (n_quad, 4), rows

@@ -68,6 +68,9 @@ double bytes_geometric_product(const femshell_ctx *c, int cols);
 int time_geometric_product(femshell_ctx *c, int32_t reps, double *mean_ms_out);
 int geometric_coefficients(femshell_ctx *c, const double *u, DevBuf<double> *coeff, const char *what);
 int upload_section_thickness(femshell_ctx *c, DevBuf<double> *buf, const double **sec_t);
+double bytes_nodal_recovery(const femshell_ctx *c);
+double bytes_recovery_error(const femshell_ctx *c);
+int time_recovery(femshell_ctx *c, bool error_kernel, int32_t reps, double *mean_ms_out);
 
 } // namespace femshell
 #pragma GCC visibility pop

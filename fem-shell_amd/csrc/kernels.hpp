@@ -230,6 +230,26 @@ void launch_element_thermal(const DeviceMatrix &m, const int32_t *slice_elem_loc
 void launch_element_loads(const DeviceMatrix &m, const int32_t *slice_elem_local, const double *elem_load, const double *base, double *out,
                           hipStream_t st);
 
+// Nodal stress recovery and the Zienkiewicz-Zhu indicator (nodal_recovery.hip).  res: the rows launch_element_resultants
+// left, (n_ltri + n_lquad) x 14 in the LOCAL element order.
+// launch_nodal_recovery: nodes[n_slices * 32][14] = per owned row the area-weighted averages N* (words 0-5) and M* (6-11) of the
+// elements that contain it, W = sum A_e (12) and the fold measure 1 - |sum a_e| / W (13); zeros on padding rows and where W = 0.
+// The additions of a row run in the order of its slice's list from zero, no atomics: two launches give the same bits at every
+// grid size.  slice_elem_local as for launch_element_loads.
+void launch_nodal_recovery(const DeviceMatrix &m, const int32_t *slice_elem_local, const double *res, double *nodes, hipStream_t st);
+// what k_recovery_error takes from a material: the factors of the complementary energy.  32 bytes: two 16-byte loads per section.
+struct RecoveryMat {
+    double cn;  // 1 / (E t)
+    double cm;  // 12 / (E t^3)
+    double nu;
+    double pad;
+};
+// out[(n_ltri + n_lquad)][2], LOCAL element order: e2 = A_e c(sigma_e, sigma_e) and eta^2 = A_e sum_ij w_ij c(d_i, d_j), d_i the
+// difference of the recovered field at corner i and the element's own value.  sec_mat / elem_section: a RecoveryMat per section and
+// the section of every local element, or nullptr twice: `mat` for every element.  One lane per element, no sums across lanes.
+void launch_recovery_error(const DeviceMatrix &m, const RecoveryMat &mat, const RecoveryMat *sec_mat, const int32_t *elem_section,
+                           const double *res, const double *nodes, double *out, hipStream_t st);
+
 // ---- sparse products (spmv_kernels.hip) ----
 // What a product does with its result besides storing it: what the callers fill and what k_spmv receives.
 struct SpmvEpilogue {

@@ -311,8 +311,8 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
         out << "Read command-line arguments.......FAILED" << std::endl;
         return -1;
     }
-    if (p.prescribed_requested() || p.reactions || p.stress) {
-        err << "ERROR: -prescribed / -reactions / -stress are options of the stand-alone program FEM-shell!\n";
+    if (p.prescribed_requested() || p.reactions || p.stress || p.stress_nodes) {
+        err << "ERROR: -prescribed / -reactions / -stress / -stress_nodes are options of the stand-alone program FEM-shell!\n";
         out << "Read command-line arguments.......FAILED" << std::endl;
         return -1;
     }

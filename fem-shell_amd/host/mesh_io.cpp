@@ -640,7 +640,7 @@ void write_meshgen_files(const MeshGenArgs &a, const std::string &name)
 }
 
 void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::string &path, const std::vector<PointVectors> *point_vectors,
-               const std::vector<CellArray> *cell_arrays)
+               const std::vector<CellArray> *cell_arrays, const std::vector<CellArray> *point_arrays)
 {
     std::ofstream os(path);
     if (!os) throw std::runtime_error("cannot write " + path);
@@ -676,23 +676,18 @@ void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::stri
                 os << line;
             }
         }
-    const bool cells = cell_arrays && !cell_arrays->empty();
-    if (m.sections_in_use || cells) os << "CELL_DATA " << ne << "\n";
-    if (m.sections_in_use) { // (runs with -sections / -section_ids only: everything above is the file of a run without)
-        os << "SCALARS section int 1\nLOOKUP_TABLE default\n";
-        for (long e = 0; e < ne; e++) os << m.tag_of((int32_t)e) << "\n";
-    }
-    if (cells) {
+    // arrays of one tuple per node or per element, every digit: one component as SCALARS, more as arrays of a FIELD
+    auto write_arrays = [&os](const std::vector<CellArray> &arrays, long count, const char *field) {
         char word[40];
         auto rows = [&](const CellArray &a) {
-            for (long e = 0; e < ne; e++)
+            for (long e = 0; e < count; e++)
                 for (int v = 0; v < a.components; v++) {
                     snprintf(word, sizeof word, "%.17g%c", a.values[(size_t)e * (size_t)a.components + v], v + 1 < a.components ? ' ' : '\n');
                     os << word;
                 }
         };
         int wide = 0;
-        for (const CellArray &a : *cell_arrays) {
+        for (const CellArray &a : arrays) {
             if (a.components != 1) {
                 wide++;
                 continue;
@@ -701,14 +696,22 @@ void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::stri
             rows(a);
         }
         if (wide) {
-            os << "FIELD cell_fields " << wide << "\n";
-            for (const CellArray &a : *cell_arrays) {
+            os << "FIELD " << field << " " << wide << "\n";
+            for (const CellArray &a : arrays) {
                 if (a.components == 1) continue;
-                os << a.name << " " << a.components << " " << ne << " double\n";
+                os << a.name << " " << a.components << " " << count << " double\n";
                 rows(a);
             }
         }
+    };
+    if (point_arrays && !point_arrays->empty()) write_arrays(*point_arrays, nn, "point_fields");
+    const bool cells = cell_arrays && !cell_arrays->empty();
+    if (m.sections_in_use || cells) os << "CELL_DATA " << ne << "\n";
+    if (m.sections_in_use) { // (runs with -sections / -section_ids only: everything above is the file of a run without)
+        os << "SCALARS section int 1\nLOOKUP_TABLE default\n";
+        for (long e = 0; e < ne; e++) os << m.tag_of((int32_t)e) << "\n";
     }
+    if (cells) write_arrays(*cell_arrays, ne, "cell_fields");
 }
 
 // VTK XML output as libMesh's VTKIO names it (fem-shell_precice.cpp:1552-1559: <out>_NNN.pvtu per converged time step of a

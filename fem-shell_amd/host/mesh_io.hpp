@@ -106,8 +106,10 @@ struct CellArray {
     int components = 1;
     std::vector<double> values; // n_elements x components
 };
+// point_arrays: the same for the nodes (the recovered tensors and the fold measure of FEM-shell -stress_nodes), one tuple per node,
+// behind the point vectors
 void write_vtk(const ShellMesh &m, const std::vector<double> &u6, const std::string &path, const std::vector<PointVectors> *point_vectors = nullptr,
-               const std::vector<CellArray> *cell_arrays = nullptr);
+               const std::vector<CellArray> *cell_arrays = nullptr, const std::vector<CellArray> *point_arrays = nullptr);
 // <stem>.pvtu + <stem>_0.vtu: the VTK XML pair libMesh's VTKIO writes per time step of a serial coupled run
 // (fem-shell_precice.cpp:1552-1559); path must end in .pvtu
 void write_pvtu(const ShellMesh &m, const std::vector<double> &u6, const std::string &path);

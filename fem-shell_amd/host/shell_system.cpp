@@ -280,6 +280,11 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-stress:\t writes <out>_stress.txt, a line per element with the membrane force tensor N, the moment tensor M (global axes,\n"
             << "\t xx yy zz xy yz zx) and the von Mises stress at the top and the bottom surface (element means), and the cell arrays\n"
             << "\t membrane_force, moment, von_mises_top, von_mises_bottom of <out>.vtk (optional)\n"
+            << "-stress_nodes:\t writes <out>_stress_nodes.txt, a line per node with the element tensors averaged to the node (N*, M*), the\n"
+            << "\t area W it was averaged over and the fold measure, and <out>_error.txt, the Zienkiewicz-Zhu indicator (e2, eta2) per\n"
+            << "\t element under a header with the sums and the relative error of the mesh; point arrays membrane_force_nodes,\n"
+            << "\t moment_nodes, fold and the cell array error_indicator of <out>.vtk (optional; with or without -stress; jumps at\n"
+            << "\t folds and section changes count as error)\n"
             << "-pressure:\t uniform pressure P on every element, along the element's own normal (optional; dead load, lumped to the nodes)\n"
             << "-element_loads:\t file of lines 'elem p qx qy qz': pressure and traction per area (global axes) of the element with that index\n"
             << "\t in mesh-file order, the index of <out>_stress.txt; elements not listed get zero (optional)\n"
@@ -515,6 +520,13 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
         p.stress = true;
         if (has_flag(argc, argv, "-modes") || has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps")) {
             err << "ERROR: -stress belongs to the static solve: not with -modes or the time stepping options -dt / -steps!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-stress_nodes")) {
+        p.stress_nodes = true;
+        if (has_flag(argc, argv, "-modes") || has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps")) {
+            err << "ERROR: -stress_nodes belongs to the static solve: not with -modes or the time stepping options -dt / -steps!\n";
             failed = true;
         }
     }
@@ -809,6 +821,13 @@ std::vector<double> ShellSystem::reactions()
     return r;
 }
 
+void ShellSystem::nodal_resultants(std::vector<double> &nodes, std::vector<double> &elems)
+{
+    nodes.assign((size_t)n_nodes_ * 14, 0.0);
+    elems.assign((size_t)n_elems_ * 2, 0.0);
+    check(femshell_nodal_resultants(ctx_, nullptr, nodes.data(), elems.data()), "femshell_nodal_resultants");
+}
+
 std::vector<double> ShellSystem::element_resultants()
 {
     std::vector<double> s((size_t)n_elems_ * 14, 0.0);
@@ -1054,6 +1073,7 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         if (p.thermal_requested()) system.set_thermal(p, thermal_loads); // (on top of all other loads; after the sections: alpha belongs to them)
         if (p.reactions && launch.world_size != 1) throw std::runtime_error("-reactions runs on one rank");
         if (p.stress && launch.world_size != 1) throw std::runtime_error("-stress runs on one rank");
+        if (p.stress_nodes && launch.world_size != 1) throw std::runtime_error("-stress_nodes runs on one rank");
         if (p.buckling_requested() && launch.world_size != 1) throw std::runtime_error("-buckling runs on one rank");
         clock.done("symbolic phase, boundary conditions, loads");
         if (p.modes_requested()) {
@@ -1237,6 +1257,69 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
             }
             out << "Element resultants: largest surface von Mises stress = " << worst << ", in " << stem << "_stress.txt" << std::endl;
         }
+        std::vector<CellArray> node_arrays;
+        if (p.stress_nodes) {
+            // the element tensors averaged to the nodes, and how far every element lies from the average: node lines in the mesh's
+            // numbering, element lines in the order of the mesh file
+            std::vector<double> nodes, elems;
+            system.nodal_resultants(nodes, elems);
+            const std::string stem = p.isOutfileSet ? p.out_filename : std::string("out");
+            std::ofstream nf(stem + "_stress_nodes.txt");
+            if (!nf) throw std::runtime_error("cannot write " + stem + "_stress_nodes.txt");
+            nf << "# node Nxx Nyy Nzz Nxy Nyz Nzx Mxx Myy Mzz Mxy Myz Mzx W fold\n"
+               << "# N, M: the element means averaged over the elements at the node with their areas, global axes; W: the sum of those areas;\n"
+               << "# fold: 1 - |sum of the vector areas| / W (0: flat and consistently oriented; elsewhere the average means little)\n";
+            static const char *nnames[3] = {"membrane_force_nodes", "moment_nodes", "fold"};
+            static const int nfirst[3] = {0, 6, 13}, ncomps[3] = {6, 6, 1};
+            const size_t nn = (size_t)mesh.n_nodes();
+            for (int a = 0; a < 3; a++) {
+                CellArray c;
+                c.name = nnames[a];
+                c.components = ncomps[a];
+                c.values.resize(nn * (size_t)ncomps[a]);
+                node_arrays.push_back(std::move(c));
+            }
+            char word[40];
+            for (size_t n = 0; n < nn; n++) {
+                const double *q = &nodes[14 * n];
+                nf << n;
+                for (int v = 0; v < 14; v++) {
+                    snprintf(word, sizeof word, " %.15e", q[v]);
+                    nf << word;
+                }
+                nf << "\n";
+                for (int a = 0; a < 3; a++)
+                    for (int v = 0; v < ncomps[a]; v++) node_arrays[(size_t)a].values[n * (size_t)ncomps[a] + v] = q[nfirst[a] + v];
+            }
+            const size_t ne = mesh.order.size();
+            CellArray eta;
+            eta.name = "error_indicator";
+            eta.components = 1;
+            eta.values.resize(ne);
+            double se2 = 0.0, seta2 = 0.0; // summed in the order of the library's rows: triangles, then quadrilaterals
+            for (size_t r = 0; r < ne; r++) {
+                se2 += elems[2 * r];
+                seta2 += elems[2 * r + 1];
+            }
+            const double rel = se2 + seta2 > 0.0 ? std::sqrt(seta2 / (se2 + seta2)) : 0.0;
+            std::ofstream ef(stem + "_error.txt");
+            if (!ef) throw std::runtime_error("cannot write " + stem + "_error.txt");
+            char line[200];
+            snprintf(line, sizeof line, "# sum_e2 %.15e sum_eta2 %.15e relative_error %.15e\n", se2, seta2, rel);
+            ef << "# element e2 eta2\n"
+               << "# e2: twice the complementary energy of the element means; eta2: the energy of the recovered field minus the element's value\n"
+               << line;
+            for (size_t e = 0; e < ne; e++) {
+                const size_t row = mesh.order[e].first == 't' ? (size_t)mesh.order[e].second : (size_t)mesh.n_tri() + (size_t)mesh.order[e].second;
+                snprintf(line, sizeof line, "%zu %.15e %.15e\n", e, elems[2 * row], elems[2 * row + 1]);
+                ef << line;
+                eta.values[e] = std::sqrt(elems[2 * row + 1]);
+            }
+            stress_arrays.push_back(std::move(eta));
+            snprintf(line, sizeof line, "%.6e", rel);
+            out << "Nodal resultants: relative error of the mesh = " << line << ", in " << stem << "_stress_nodes.txt and " << stem << "_error.txt"
+                << std::endl;
+        }
         bool buckling_converged = true;
         if (p.buckling_requested()) {
             // at what multiple of the solved load case the shell buckles, and in which shapes: the prestress is the solution's
@@ -1272,7 +1355,8 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         }
         if (p.isOutfileSet) {
             write_exodus(mesh, sols, p.out_filename + ".e"); // the reference's file (fem-shell.cpp:1249)
-            write_vtk(mesh, sols, p.out_filename + ".vtk", reaction_arrays.empty() ? nullptr : &reaction_arrays, p.stress ? &stress_arrays : nullptr);
+            write_vtk(mesh, sols, p.out_filename + ".vtk", reaction_arrays.empty() ? nullptr : &reaction_arrays, stress_arrays.empty() ? nullptr : &stress_arrays,
+                      node_arrays.empty() ? nullptr : &node_arrays);
             clock.done("output files");
         }
         out << "All done :)\n";

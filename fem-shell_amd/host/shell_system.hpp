@@ -86,6 +86,14 @@ struct Parameters {
     // file -- and the cell arrays membrane_force, moment (6 components), von_mises_top, von_mises_bottom of <out>.vtk
     // (femshell_element_resultants).
     bool stress = false;
+    // nodal stress recovery and the error indicator (extension, stand-alone program only).  -stress_nodes, with or without -stress:
+    // after the static solve writes <out>_stress_nodes.txt -- a '#' header, then a line "node N*(6) M*(6) W fold" (%.15e) per node --
+    // and <out>_error.txt -- a '#' header with sum e2, sum eta^2 and the relative error sqrt(sum eta^2 / (sum e2 + sum eta^2)), then a
+    // line "element e2 eta2" per element in the order of the mesh file --, adds the point arrays membrane_force_nodes, moment_nodes
+    // (6 components) and fold and the cell array error_indicator (eta) to <out>.vtk and prints the relative error
+    // (femshell_nodal_resultants).  At folds and section changes the jump of N and M is physical and counts as error: the fold
+    // column and the section ids let a reader mask those nodes.
+    bool stress_nodes = false;
     bool prescribed_requested() const { return !prescribed_file.empty(); }
     // element loads (extension, stand-alone program only; the reference's loads are the nodal forces of the `_f` file): pressure and
     // traction per element (femshell_set_element_loads).  -pressure P: p = P on every element, along the element's own normal.
@@ -218,6 +226,9 @@ class ShellSystem {
     std::vector<double> reactions();
     // -stress: the element resultants of the last solve's solution, (n_tri + n_quad) x 14, triangles then quadrilaterals
     std::vector<double> element_resultants();
+    // -stress_nodes: the recovered node rows (n_nodes x 14) and the element rows (e2, eta^2; triangles then quadrilaterals) of the
+    // last solve's solution
+    void nodal_resultants(std::vector<double> &nodes, std::vector<double> &elems);
     // per node: the Dirichlet mask in force (what set_mesh derived from the boundary ids)
     const std::vector<uint8_t> &dirichlet_mask() const { return mask_; }
     // the assembly callback (SA:1160-1233); the name argument is checked like SA:1163

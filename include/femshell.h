@@ -549,6 +549,37 @@ int femshell_reactions(femshell_ctx *ctx, const double *u /* n_nodes x 6, or NUL
  * (world_size != 1); FEMSHELL_ERR_INVALID while dynamics is active, without a mesh, for the NULL form before any solve, for a
  * non-finite u.  The context stays usable after every refusal. */
 int femshell_element_resultants(femshell_ctx *ctx, const double *u /* n_nodes x 6, or NULL */, double *out /* (n_tri + n_quad) x 14 */);
+/* extends: the element means above, averaged to the nodes, and how far each element lies from that average in the energy norm
+ * (the Zienkiewicz-Zhu indicator).  Tensors are six words xx, yy, zz, xy, yz, zx in global axes, as above.
+ *     T:T = xx^2 + yy^2 + zz^2 + 2 (xy^2 + yz^2 + zx^2),  tr T = xx + yy + zz
+ *     q_nu(S, T) = (1 + nu) S:T - nu tr S tr T        (frame-free; for tangent tensors the plane-stress compliance times E)
+ *     cN(S, T) = q_nu(S, T) / (E t),  cM(S, T) = 12 q_nu(S, T) / (E t^3)       (E, nu, t the element's own: its section's)
+ *     a_e: the vector area of the element, TRI3 (b-a) x (c-a) / 2, QUAD4 d1 x d2 / 2 (d1 = c-a, d2 = d-b);  A_e = |a_e|, the
+ *     area of femshell_lumped_mass and of the element loads
+ * nodes_out, per node 14 doubles, rows in the caller's numbering (FEMSHELL_REORDER too):
+ *     [0..5]   N* = sum_e A_e N_e / W,  [6..11]  M* = sum_e A_e M_e / W  over the elements e that contain the node, N_e and M_e
+ *              the words 0..11 of the element's row of femshell_element_resultants (prescribed values and temperatures in force
+ *              included)
+ *     [12]     W = sum_e A_e
+ *     [13]     the fold measure 1 - |sum_e a_e| / W: 0 where the neighbourhood is flat and consistently oriented, 1 - cos(phi/2)
+ *              on a fold of angle phi between equal areas, 1 where orientations cancel.  M changes sign with an element's node
+ *              order: the measure tells where the average means nothing.
+ *     W = 0: fourteen zeros.
+ * elems_out, per element 2 doubles, rows in the caller's order (triangles, then quadrilaterals), with
+ * d_i = (N*_i - N_e, M*_i - M_e) at the element's corners and c(d_i, d_j) = cN(.,.) + cM(.,.):
+ *     [0]      e2 = A_e c(sigma_e, sigma_e): twice the complementary energy of the element means
+ *     [1]      eta^2 = A_e sum_ij w_ij c(d_i, d_j), the exact integral of the interpolated difference: TRI3 w_ij = (1 + delta_ij) / 12;
+ *              QUAD4 w = 4/36 for the same corner, 2/36 for corners that share a side, 1/36 for the diagonal (the bilinear mass
+ *              of a parallelogram, used as the definition on any quadrilateral)
+ * The relative error of a mesh is sqrt(sum eta^2 / (sum e2 + sum eta^2)), summed by the caller.
+ * KNOWN LIMIT: at folds and where the section changes the jump of N and M is physical; the indicator reports it as error.  The
+ * fold measure and the section ids let a caller mask those nodes (smoothing groups are an open end).
+ * Either output may be NULL, not both.  u as for femshell_element_resultants, and the same refusals: FEMSHELL_ERR_UNSUPPORTED on a
+ * row-partitioned context; FEMSHELL_ERR_INVALID while dynamics is active, without a mesh, for the NULL form before any solve, for
+ * a non-finite u, for two NULL outputs; a degenerate element: FEMSHELL_ERR_MESH.  The sums of a node run over its elements in a
+ * fixed order without atomics: two calls give the same bits.  Nothing is kept: the context is as it was. */
+int femshell_nodal_resultants(femshell_ctx *ctx, const double *u /* n_nodes x 6, or NULL */, double *nodes_out /* n_nodes x 14, or NULL */,
+                              double *elems_out /* (n_tri + n_quad) x 2, or NULL */);
 /* The NEXT femshell_solve of this context starts from u0 (n_nodes x 6, the caller's numbering; every rank passes the whole vector
  * and keeps its own rows) instead of from zero; u0 == NULL: from the solution of the context's previous solve, where it lies in
  * HBM (no transfer).  Consumed by that solve; femshell_set_mesh forgets it.
@@ -817,7 +848,15 @@ typedef enum femshell_kernel {
      * a mesh only, the loads in force are not disturbed.  bytes_out: 16 bytes of node ids, 4 of element index and 16 of
      * temperatures per entry of the slices' element lists (4 more of a section index where the context has sections), 24 bytes
      * of coordinates per node, 48 bytes of base read and 48 written per owned row -- all six components carry a sum */
-    FEMSHELL_KERNEL_ELEMENT_THERMAL = 15
+    FEMSHELL_KERNEL_ELEMENT_THERMAL = 15,
+    /* k_nodal_recovery back to back on the element rows of a hashed displacement vector; needs a mesh only.  bytes_out: 16 bytes
+     * of node ids, 4 of element index and 96 of tensor words per entry of the slices' element lists, 24 bytes of coordinates per
+     * node, 112 bytes written per row of the slices (padding rows included) */
+    FEMSHELL_KERNEL_NODAL_RECOVERY = 16,
+    /* k_recovery_error back to back on the same rows and their nodal averages; needs a mesh only.  bytes_out: 12 / 16 bytes of
+     * node ids, 96 of tensor words and 16 of output per element (4 more of a section index where the context has sections),
+     * coordinates and recovered tensors (24 + 96 bytes) once per node */
+    FEMSHELL_KERNEL_RECOVERY_ERROR = 17
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
