@@ -15,6 +15,7 @@ from .binding import (  # noqa: F401
     KERNEL_ASSEMBLE,
     KERNEL_CG_DIRECTION,
     KERNEL_CG_UPDATE,
+    KERNEL_ELASTIC_SUPPORT,
     KERNEL_ELEMENT_LOADS,
     KERNEL_ELEMENT_PRODUCT,
     KERNEL_ELEMENT_RESULTANTS,

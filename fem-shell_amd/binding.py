@@ -25,6 +25,7 @@ KERNEL_GEOMETRIC_PRODUCT = 14
 KERNEL_ELEMENT_THERMAL = 15
 KERNEL_NODAL_RECOVERY = 16
 KERNEL_RECOVERY_ERROR = 17
+KERNEL_ELASTIC_SUPPORT = 18
 
 SYMBOLS = [
     "femshell_create", "femshell_destroy", "femshell_last_error", "femshell_set_mesh",
@@ -43,6 +44,7 @@ SYMBOLS = [
     "femshell_nodal_resultants",
     "femshell_set_element_loads", "femshell_element_load_vector",
     "femshell_set_expansion", "femshell_set_thermal", "femshell_thermal_load_vector",
+    "femshell_set_foundation", "femshell_set_springs", "femshell_support_stiffness", "femshell_support_forces",
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
     "femshell_pool_stats", "femshell_amg_device_dense_inverse", "femshell_amg_dense_apply",
     "femshell_amg_device_block_jacobi", "femshell_block_jacobi_export", "femshell_block_jacobi_apply",
@@ -250,6 +252,10 @@ def load_library():
     L.femshell_set_expansion.argtypes = [vp, C.c_double, C.c_int32, dp]
     L.femshell_set_thermal.argtypes = [vp, dp, dp]
     L.femshell_thermal_load_vector.argtypes = [vp, dp]
+    L.femshell_set_foundation.argtypes = [vp, dp, dp]
+    L.femshell_set_springs.argtypes = [vp, C.c_int32, ip, dp]
+    L.femshell_support_stiffness.argtypes = [vp, dp]
+    L.femshell_support_forces.argtypes = [vp, dp, dp]
     L.femshell_geometric_product.argtypes = [vp, dp, C.c_int32, dp, dp]
     L.femshell_buckling_defaults.argtypes = [C.POINTER(BucklingOptions)]
     L.femshell_buckling.argtypes = [vp, C.POINTER(BucklingOptions), dp, dp, dp, dp, C.POINTER(BucklingInfo)]
@@ -455,6 +461,55 @@ class FemShell:
         zeros when none are set (femshell_thermal_load_vector)."""
         f = np.zeros((self.n_nodes, 6))
         _check(self._L.femshell_thermal_load_vector(self._h, _d(f)))
+        return f
+
+    def set_foundation(self, tri_k=None, quad_k=None):
+        """Elastic foundation per element (femshell_set_foundation): tri_k is (n_tri, 2), quad_k (n_quad, 2), rows (kn, kt) >= 0 in
+        the element order of set_mesh -- force per volume, kn along the element's own normal, kt in its plane.  None for one kind
+        leaves it without a foundation, both None clears.  K in HBM is K + mask(K_sup) after the next assembly, which the next
+        use makes."""
+        tk = None if tri_k is None else np.ascontiguousarray(tri_k, dtype=np.float64).reshape(-1, 2)
+        qk = None if quad_k is None else np.ascontiguousarray(quad_k, dtype=np.float64).reshape(-1, 2)
+        if tk is not None and len(tk) != self.n_tri:
+            raise ValueError("tri_k needs one row per triangle (%d), got %d" % (self.n_tri, len(tk)))
+        if qk is not None and len(qk) != self.n_quad:
+            raise ValueError("quad_k needs one row per quadrilateral (%d), got %d" % (self.n_quad, len(qk)))
+        _check(self._L.femshell_set_foundation(self._h, _d(tk), _d(qk)))
+
+    def set_springs(self, *args):
+        """Nodal springs (femshell_set_springs): set_springs(k6) with one row (kx, ky, kz, krx, kry, krz) >= 0 per node, or
+        set_springs(ids, k6) with one row per listed node (the others get none); global axes.  set_springs(None) (or an empty
+        array) clears them."""
+        if len(args) == 1:
+            ids, k6 = None, args[0]
+        elif len(args) == 2:
+            ids, k6 = args
+        else:
+            raise TypeError("set_springs(k6) or set_springs(ids, k6)")
+        if k6 is None:
+            _check(self._L.femshell_set_springs(self._h, 0, None, None))
+            return
+        k6 = np.ascontiguousarray(k6, dtype=np.float64).reshape(-1, 6)
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        if ids is not None and len(ids) != len(k6):
+            raise ValueError("k6 needs one row per entry of ids (%d), got %d" % (len(ids), len(k6)))
+        if ids is None and len(k6) not in (0, self.n_nodes):
+            raise ValueError("k6 needs one row per node (%d), got %d" % (self.n_nodes, len(k6)))
+        _check(self._L.femshell_set_springs(self._h, len(k6), _i(ids), _d(k6)))
+
+    def support_stiffness(self):
+        """The support table in force, (n_nodes, 9), in the caller's numbering, not masked: the summed foundation tensor (xx, yy,
+        zz, xy, yz, zx) with the translational springs on its first three words, then the three rotational springs; zeros when
+        nothing is set (femshell_support_stiffness)."""
+        s = np.zeros((self.n_nodes, 9))
+        _check(self._L.femshell_support_stiffness(self._h, _d(s)))
+        return s
+
+    def support_forces(self, u=None):
+        """-K_sup u, (n_nodes, 6): the force and moment the elastic supports exert on the shell (femshell_support_forces).  u None:
+        the solution of the last solve, prescribed part included."""
+        f = np.zeros((self.n_nodes, 6))
+        _check(self._L.femshell_support_forces(self._h, _d(self._node_vector(u, "u")), _d(f)))
         return f
 
     def set_sections(self, sections, tri_section=None, quad_section=None):

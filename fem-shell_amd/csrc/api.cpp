@@ -751,6 +751,7 @@ static int set_mesh_on_this_rank(femshell_ctx *c, int32_t n_nodes, const double 
     forget_density(c);
     forget_element_loads(c); // (per element of the previous mesh; kNodeCleared below zeroes the loads)
     forget_thermal(c);       // (... and the temperatures and alpha with them)
+    forget_supports(c);      // (... and the foundation, the springs and their table)
     c->dyn.reset(); // (a new mesh ends dynamics)
     c->have_prescribed = c->ubar_nonzero = false; // (... and forgets the prescribed displacements)
     c->prescribed_global.clear();
@@ -1764,8 +1765,15 @@ int femshell_reactions(femshell_ctx *c, const double *u, double *r6_out)
         if (rc) return rc;
         if (c->ubar_nonzero) xp = c->ubar.p;
     }
-    // r = K_unc u - loads, the loads as set (not masked)
-    launch_element_product(c->dm, c->mc, c->sections_or_null(), x, xp, c->loads.p, b.y.p, false, c->stream);
+    // r = K_unc u - loads, the loads as set (not masked); elastic supports in force: r = K_unc u - (loads - K_sup u)
+    const double *sub = c->loads.p;
+    DevBuf<double> sup;
+    if (c->have_supports()) {
+        FS_HIP(sup.alloc((size_t)p.n_pad * 6));
+        launch_support_apply(c->dm, c->support.p, x, xp, c->loads.p, -1.0, sup.p, c->stream);
+        sub = sup.p;
+    }
+    launch_element_product(c->dm, c->mc, c->sections_or_null(), x, xp, sub, b.y.p, false, c->stream);
     FS_HIP(hipGetLastError());
     rc = check_status(c, "femshell_reactions");
     if (rc) return rc;

@@ -1,6 +1,6 @@
 // api_internal.hpp -- what the files of the C ABI share: api.cpp (context, mesh and its data, solve, export, products), api_state.cpp
 // (what of the context's derived state is valid, and the functions that make it so), api_dynamics.cpp, api_modal.cpp,
-// api_resultants.cpp, api_element_loads.cpp, api_thermal.cpp, api_timing.cpp.  Not for the rest of the library.  Each function is described where it is defined: api.cpp, but
+// api_resultants.cpp, api_element_loads.cpp, api_thermal.cpp, api_elastic_support.cpp, api_timing.cpp.  Not for the rest of the library.  Each function is described where it is defined: api.cpp, but
 // for the block from invalidate to timed_assembly_done (api_state.cpp), the byte models of the hot-path kernels (api_timing.cpp)
 // and what api_resultants.cpp shares with the timing hook.
 #pragma once
@@ -53,6 +53,12 @@ int thermal_apply(femshell_ctx *c, const RawVec<double> &rows);
 int thermal_clear(femshell_ctx *c);
 ThermalView thermal_view(const femshell_ctx *c);
 const ThermalView *thermal_view_or_null(const femshell_ctx *c, ThermalView *store);
+// elastic supports (api_state.cpp): c->support holds the table of the foundation and the springs in force; every assembly adds it
+void forget_supports(femshell_ctx *c);
+int foundation_apply(femshell_ctx *c, const RawVec<double> &rows);
+int foundation_clear(femshell_ctx *c);
+int springs_apply(femshell_ctx *c, const RawVec<double> &rows);
+int springs_clear(femshell_ctx *c);
 
 double bytes_assemble(const femshell_ctx *c);
 double bytes_spmv(const femshell_ctx *c);
@@ -62,6 +68,8 @@ double bytes_update_single_reduction(const femshell_ctx *c);
 double bytes_element_resultants(const femshell_ctx *c);
 double bytes_element_loads(const femshell_ctx *c);
 int time_element_loads(femshell_ctx *c, int32_t reps, double *mean_ms_out);
+double bytes_elastic_support(const femshell_ctx *c);
+int time_elastic_support(femshell_ctx *c, int32_t reps, double *mean_ms_out);
 double bytes_element_thermal(const femshell_ctx *c);
 int time_element_thermal(femshell_ctx *c, int32_t reps, double *mean_ms_out);
 double bytes_geometric_product(const femshell_ctx *c, int cols);

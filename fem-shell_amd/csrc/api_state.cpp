@@ -1,7 +1,7 @@
 // api_state.cpp -- the derived state of a context (derived.hpp): the one place that says what is valid.
 // invalidate() applies the table of derived.hpp after a change, the functions below it make a product valid, ensure() brings
 // what an entry point needs up to date, have() answers for the entry points that refuse instead.  No other file assigns to
-// matrix_valid, rhs_valid, jacobi_valid, mass_valid, ubar_valid, have_element_loads, have_alpha, have_thermal or amg_fp64_only or drops the hierarchy; have_solution and
+// matrix_valid, rhs_valid, jacobi_valid, mass_valid, ubar_valid, have_element_loads, have_alpha, have_thermal, have_foundation, have_springs or amg_fp64_only or drops the hierarchy; have_solution and
 // warm_next are set where a solve and a hand-over produce them (api.cpp, api_dynamics.cpp) and cleared here only.
 #include "api_internal.hpp"
 
@@ -287,6 +287,88 @@ int thermal_forget_and_restore(femshell_ctx *c)
     return FEMSHELL_OK;
 }
 
+// ---- elastic supports (femshell_set_foundation, femshell_set_springs, api_elastic_support.cpp).  The invariant:
+// while a foundation or springs are in force c->support holds the table k_support_rows made of them, and every assembly adds it
+// to the diagonal blocks of K behind the assembly kernel (support_add below).  A change of either set is a change of K that the
+// table of derived.hpp has no row of its own for: it is reported as Change::matrix_spoiled -- K, F, block-Jacobi and the
+// hierarchy, exactly what is stale -- and the next use assembles again.  (No subtraction in place: K + S - S is not K bit for bit.)
+
+// femshell_set_mesh forgets both sets, their buffers and the table
+void forget_supports(femshell_ctx *c)
+{
+    c->have_foundation = c->have_springs = false;
+    c->elem_found.release();
+    c->spring.release();
+    c->support.release();
+    c->sup_scratch.release();
+}
+
+// the table of what is in force, once per change of its inputs; with nothing in force its buffers go back.  Synchronises.
+static int supports_changed(femshell_ctx *c)
+{
+    hipStream_t st = c->stream;
+    if (!c->have_supports()) {
+        FS_HIP(hipStreamSynchronize(st));
+        c->support.release();
+        c->sup_scratch.release();
+    } else {
+        if (c->have_foundation) {
+            const int rc = ensure_slice_elem_local(c);
+            if (rc) return rc;
+        }
+        FS_HIP(c->support.alloc((size_t)std::max(c->dm.n_slices * kSliceNodes, c->plan.n_pad) * 9));
+        launch_support_rows(c->dm, c->slice_elem_local.p, c->have_foundation ? c->elem_found.p : nullptr, c->have_springs ? c->spring.p : nullptr,
+                            c->support.p, st);
+        FS_HIP(hipGetLastError());
+        FS_HIP(hipStreamSynchronize(st)); // (the caller's host rows go out of scope)
+    }
+    invalidate(c, Change::matrix_spoiled);
+    return FEMSHELL_OK;
+}
+
+// rows: (kn, kt) per local element, which take force in place of the previous set
+int foundation_apply(femshell_ctx *c, const RawVec<double> &rows)
+{
+    FS_HIP(hipStreamSynchronize(c->stream)); // (a launch in flight may read the rows that are replaced)
+    FS_HIP(c->elem_found.upload(rows, c->stream));
+    c->have_foundation = true;
+    return supports_changed(c);
+}
+
+int foundation_clear(femshell_ctx *c)
+{
+    if (!c->have_foundation) return FEMSHELL_OK;
+    c->have_foundation = false;
+    const int rc = supports_changed(c);
+    c->elem_found.release();
+    return rc;
+}
+
+// rows: six doubles per row of the rank (n_pad x 6, zero on the padding rows), which take force in place of the previous set
+int springs_apply(femshell_ctx *c, const RawVec<double> &rows)
+{
+    FS_HIP(hipStreamSynchronize(c->stream));
+    FS_HIP(c->spring.upload(rows, c->stream));
+    c->have_springs = true;
+    return supports_changed(c);
+}
+
+int springs_clear(femshell_ctx *c)
+{
+    if (!c->have_springs) return FEMSHELL_OK;
+    c->have_springs = false;
+    const int rc = supports_changed(c);
+    c->spring.release();
+    return rc;
+}
+
+// K in HBM becomes K + mask(K_sup): behind the assembly kernel, in front of the mass shift of an active dynamics.  Nothing
+// without supports.
+static void support_add(femshell_ctx *c)
+{
+    if (c->have_supports()) launch_support_add(c->dm, c->support.p, c->stream);
+}
+
 // u_bar of the prescribed values and the Dirichlet set in force (femshell_set_prescribed): the entries at fixed dofs, zero
 // elsewhere, on the host and in HBM.  Single-rank contexts only: the owned rows are all rows.
 int resolve_prescribed(femshell_ctx *c)
@@ -321,7 +403,13 @@ static int do_rhs(femshell_ctx *c)
         const int rc = resolve_prescribed(c);
         if (rc) return rc;
         if (c->ubar_nonzero) {
-            launch_element_product(c->dm, c->mc, c->sections_or_null(), c->ubar.p, nullptr, c->loads.p, c->F.p, true, c->stream);
+            const double *sub = c->loads.p;
+            if (c->have_supports()) { // F = mask((loads - K_sup u_bar) - K_unc u_bar): the supports' part first, into a scratch vector
+                FS_HIP(c->sup_scratch.alloc((size_t)c->plan.n_pad * 6));
+                launch_support_apply(c->dm, c->support.p, c->ubar.p, nullptr, c->loads.p, -1.0, c->sup_scratch.p, c->stream);
+                sub = c->sup_scratch.p;
+            }
+            launch_element_product(c->dm, c->mc, c->sections_or_null(), c->ubar.p, nullptr, sub, c->F.p, true, c->stream);
             FS_HIP(hipGetLastError());
             c->rhs_valid = true;
             return FEMSHELL_OK;
@@ -356,6 +444,7 @@ int do_assemble(femshell_ctx *c, bool wait)
     c->dm.rhs_F = c->F.p;
     if (!launch_assemble(c->dm, c->mc, c->stream, c->sections_or_null())) // K and F (k_rhs alone serves changes of the loads)
         return set_err(FEMSHELL_ERR_INVALID, "femshell_assemble: the context's sections have no table in HBM");
+    support_add(c); // (elastic supports in force: K + mask(K_sup), inside the event pair)
     // (dynamics is active: the matrix in HBM is K_eff = K + shift M, also when K is built again -- FEMSHELL_REASSEMBLE_EACH_SOLVE)
     if (c->dyn.active) launch_mass_shift(c->dm, c->mass.p, c->dyn.k.shift, c->stream);
     if (events) FS_HIP(hipEventRecord(c->ev1, c->stream));
@@ -388,10 +477,9 @@ int do_assemble(femshell_ctx *c, bool wait)
 // was (the kernel rewrites the masked loads) unless prescribed values are in force, which that overwrites.
 int timed_assembly_done(femshell_ctx *c)
 {
-    if (c->dyn.active) {
-        launch_mass_shift(c->dm, c->mass.p, c->dyn.k.shift, c->stream);
-        FS_HIP(hipGetLastError());
-    }
+    support_add(c); // (once behind the last of the timed launches, as behind every assembly)
+    if (c->dyn.active) launch_mass_shift(c->dm, c->mass.p, c->dyn.k.shift, c->stream);
+    if (c->dyn.active || c->have_supports()) FS_HIP(hipGetLastError());
     const int rc = check_status(c, "femshell_time_kernel");
     if (rc) return rc;
     invalidate(c, Change::assembled);

@@ -213,6 +213,13 @@ int femshell_time_kernel(femshell_ctx *c, femshell_kernel which, int32_t reps, d
         if (bytes_out) *bytes_out = bytes_element_thermal(c);
         return FEMSHELL_OK;
     }
+    if (which == FEMSHELL_KERNEL_ELASTIC_SUPPORT) {
+        // hashed moduli into a scratch table (api_elastic_support.cpp): every rank times its own rows
+        rc = time_elastic_support(c, reps, mean_ms_out);
+        if (rc) return rc;
+        if (bytes_out) *bytes_out = bytes_elastic_support(c);
+        return FEMSHELL_OK;
+    }
     if (which == FEMSHELL_KERNEL_NODAL_RECOVERY || which == FEMSHELL_KERNEL_RECOVERY_ERROR) {
         // the element rows of a hashed displacement vector, averaged to the nodes / compared with the average (api_resultants.cpp)
         if (c->cfg.world_size != 1) return set_err(FEMSHELL_ERR_UNSUPPORTED, "femshell_time_kernel: the nodal recovery runs on single-rank contexts");

@@ -179,6 +179,14 @@ struct femshell_ctx {
     std::vector<double> sec_alpha;
     femshell::DevBuf<double> elem_temp, loads_mech;
     femshell::DevBuf<femshell::ThermalSec> sec_thermal;
+    // elastic supports (femshell_set_foundation, femshell_set_springs): elem_found, (kn, kt) per LOCAL element, and
+    // spring, six doubles per owned row, while the one or the other is in force; support, the table of nine words per slice row
+    // that k_support_rows makes of them once per change (kernels.hpp), which every assembly adds to K's diagonal blocks.
+    // sup_scratch: loads - K_sup u_bar of a right-hand side with prescribed values.  With neither in force no buffer exists and
+    // no launch is made.  (have_foundation and have_springs are written by api_state.cpp only.)
+    bool have_foundation = false, have_springs = false;
+    bool have_supports() const { return have_foundation || have_springs; }
+    femshell::DevBuf<double> elem_found, spring, support, sup_scratch;
     // CG state
     femshell::DevBuf<double> x, r, z, p, q, sv, partials, hist, sendbuf, ufull;
     femshell::DevBuf<double> xacc, rres; // iterative refinement of the multigrid-preconditioned solve: accumulated solution, residual

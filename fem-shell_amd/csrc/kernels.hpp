@@ -230,6 +230,24 @@ void launch_element_thermal(const DeviceMatrix &m, const int32_t *slice_elem_loc
 void launch_element_loads(const DeviceMatrix &m, const int32_t *slice_elem_local, const double *elem_load, const double *base, double *out,
                           hipStream_t st);
 
+// Elastic supports (elastic_support.hip).  The support table: nine doubles per row of the slices (n_slices * 32
+// rows) -- the tensor sum of the element foundations, xx yy zz xy yz zx, with the translational springs added to its first three
+// words, then the three rotational springs; zeros on padding rows.
+// launch_support_rows: elem_found, (kn, kt) per LOCAL element (triangles, then quadrilaterals), 16-byte aligned, or nullptr: no
+// foundation (the lists are not walked); spring[n_pad][6] in global axes, or nullptr: no springs.  The additions of a row run in
+// the order of its slice's list from zero, no atomics: two launches give the same bits at every grid size.  slice_elem_local as
+// for launch_element_loads.
+void launch_support_rows(const DeviceMatrix &m, const int32_t *slice_elem_local, const double *elem_found, const double *spring, double *table,
+                         hipStream_t st);
+// vals(diagonal slot of row a)(i, j) += K_sup(i, j) where neither dof i nor dof j of the node is fixed, one addition per entry
+// and image: behind the assembly kernel, in front of launch_mass_shift
+void launch_support_add(const DeviceMatrix &m, const double *table, hipStream_t st);
+// y[n_pad][6] = base + s K_sup (x + xp) on the owned rows (not masked), zero on padding rows; xp and base may be nullptr
+void launch_support_apply(const DeviceMatrix &m, const double *table, const double *x, const double *xp, const double *base, double s,
+                          double *y, hipStream_t st);
+// the table as two node vectors: lo[n_pad][6] = words 0-5, hi[n_pad][6] = words 6-8 and three zeros
+void launch_support_words(const DeviceMatrix &m, const double *table, double *lo, double *hi, hipStream_t st);
+
 // Nodal stress recovery and the Zienkiewicz-Zhu indicator (nodal_recovery.hip).  res: the rows launch_element_resultants
 // left, (n_ltri + n_lquad) x 14 in the LOCAL element order.
 // launch_nodal_recovery: nodes[n_slices * 32][14] = per owned row the area-weighted averages N* (words 0-5) and M* (6-11) of the

@@ -148,6 +148,82 @@ static void read_thermal(Parameters &p)
     }
 }
 
+// lines 'index v1 .. vN' of stiffnesses (finite, >= 0) into (ids, lines, values): the conventions of the -element_loads reader;
+// `expected`: the line's form for the message
+static void read_stiffness_rows(const std::string &file, int n_values, const char *expected, std::vector<int32_t> &ids, std::vector<int> &lines,
+                                std::vector<double> &values)
+{
+    std::ifstream in(file);
+    if (!in) throw std::runtime_error("cannot open " + file);
+    ids.clear();
+    lines.clear();
+    values.clear();
+    std::string line;
+    for (int no = 1; std::getline(in, line); no++) {
+        const size_t h = line.find('#');
+        if (h != std::string::npos) line.erase(h);
+        std::istringstream is(line);
+        std::string first;
+        if (!(is >> first)) continue; // blank or comment
+        const std::string where = file + ": line " + std::to_string(no) + ": ";
+        char *end = nullptr;
+        const long id = std::strtol(first.c_str(), &end, 10);
+        double v[6];
+        bool ok = *end == '\0';
+        for (int k = 0; ok && k < n_values; k++) ok = bool(is >> v[k]);
+        std::string rest;
+        if (!ok || (is >> rest)) throw std::runtime_error(where + "expected '" + expected + "'");
+        for (int k = 0; k < n_values; k++) {
+            if (!std::isfinite(v[k])) throw std::runtime_error(where + "a value is not finite");
+            if (v[k] < 0.0) throw std::runtime_error(where + "a stiffness is negative");
+        }
+        if (id < 0 || id > 2147483647L) throw std::runtime_error(where + "index " + first + " is out of range");
+        ids.push_back((int32_t)id);
+        lines.push_back(no);
+        values.insert(values.end(), v, v + n_values);
+    }
+}
+
+ElasticSupports build_elastic_supports(const Parameters &p, const ShellMesh &mesh)
+{
+    ElasticSupports s;
+    if (p.foundation_requested()) {
+        const size_t ne = mesh.order.size();
+        std::vector<double> rows(2 * ne, 0.0); // mesh-file order
+        std::vector<uint8_t> listed(ne, 0);
+        for (size_t i = 0; i < p.foundation_elems.size(); i++) {
+            const std::string where = p.element_foundation_file + ": line " + std::to_string(p.foundation_lines[i]) + ": ";
+            const size_t e = (size_t)p.foundation_elems[i];
+            if (e >= ne)
+                throw std::runtime_error(where + "element index " + std::to_string(e) + " is out of range (the mesh has " + std::to_string(ne) + " elements)");
+            if (listed[e]) throw std::runtime_error(where + "element " + std::to_string(e) + " is listed twice");
+            listed[e] = 1;
+            for (int v = 0; v < 2; v++) rows[2 * e + v] = p.foundation_values[2 * i + v];
+        }
+        s.tri_k.assign(2 * (size_t)mesh.n_tri(), 0.0);
+        s.quad_k.assign(2 * (size_t)mesh.n_quad(), 0.0);
+        for (size_t e = 0; e < ne; e++) {
+            const bool tri = mesh.order[e].first == 't';
+            const size_t k = (size_t)mesh.order[e].second;
+            double *dst = tri ? &s.tri_k[2 * k] : &s.quad_k[2 * k];
+            dst[0] = rows[2 * e] + (p.foundation_set ? p.foundation : 0.0);
+            dst[1] = rows[2 * e + 1] + (p.foundation_shear_set ? p.foundation_shear : 0.0);
+        }
+    }
+    std::vector<uint8_t> listed((size_t)mesh.n_nodes(), 0);
+    for (size_t i = 0; i < p.spring_nodes.size(); i++) {
+        const std::string where = p.springs_file + ": line " + std::to_string(p.spring_lines[i]) + ": ";
+        const size_t a = (size_t)p.spring_nodes[i];
+        if (a >= (size_t)mesh.n_nodes())
+            throw std::runtime_error(where + "node id " + std::to_string(a) + " is out of range (the mesh has " + std::to_string(mesh.n_nodes()) + " nodes)");
+        if (listed[a]) throw std::runtime_error(where + "node " + std::to_string(a) + " is listed twice");
+        listed[a] = 1;
+    }
+    s.spring_nodes = p.spring_nodes;
+    s.spring_values = p.spring_values;
+    return s;
+}
+
 // -section_alpha FILE into p.section_alpha_*: lines 'tag alpha'
 static void read_section_alpha(Parameters &p)
 {
@@ -299,6 +375,15 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-thermal:\t file of lines 'elem Tm Tg': temperatures of the element with that index in mesh-file order (optional)\n"
             << "\t -temperature, -temperature_gradient and -thermal add up; the work-equivalent loads come on top of all other loads, and\n"
             << "\t -stress, -reactions and -buckling work on the heated shell; not with -modes\n"
+            << "-foundation:\t elastic foundation modulus KN >= 0 of every element along its own normal, force per volume (optional)\n"
+            << "-foundation_shear:\t ... and KT >= 0 in the element's plane (optional)\n"
+            << "-element_foundation:\t file of lines 'elem kn kt': moduli of the element with that index in mesh-file order, added on top of\n"
+            << "\t the uniform values (optional)\n"
+            << "-springs:\t file of lines 'node kx ky kz krx kry krz': springs >= 0 in global axes at the node with that id (optional)\n"
+            << "\t the supports are part of K: the solve, -dt / -steps, -modes, -buckling, -reactions and -stress see the supported shell\n"
+            << "-support_forces:\t after the static solve: writes <out>_support.txt, lines 'node fx fy fz mx my mz', the force and moment the\n"
+            << "\t elastic supports exert on the shell, and the point arrays support_f / support_m of <out>.vtk (optional; not with\n"
+            << "\t -modes or -dt / -steps)\n"
             << "-buckling:\t after the static solve: the N load factors of smallest magnitude (signed) at which the solved load case\n"
             << "\t buckles, N in 1 .. 28; writes <out>_buckling.txt, lines 'index lambda rho', and the shapes as point arrays\n"
             << "\t buckling_<k>_u / buckling_<k>_r of <out>.vtk (optional; not with -modes or -dt / -steps)\n"
@@ -638,6 +723,58 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
         err << "ERROR: -alpha / -section_alpha / -temperature / -temperature_gradient / -thermal do not go together with -modes (a modal analysis has no loads)!\n";
         failed = true;
     }
+    // elastic supports: refused here in the same way
+    if (has_flag(argc, argv, "-foundation")) {
+        p.foundation_set = true;
+        if (!number(arg_after(argc, argv, "-foundation"), &p.foundation) || p.foundation < 0.0) {
+            err << "ERROR: -foundation needs a finite number >= 0!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-foundation_shear")) {
+        p.foundation_shear_set = true;
+        if (!number(arg_after(argc, argv, "-foundation_shear"), &p.foundation_shear) || p.foundation_shear < 0.0) {
+            err << "ERROR: -foundation_shear needs a finite number >= 0!\n";
+            failed = true;
+        }
+    }
+    if (has_flag(argc, argv, "-element_foundation")) {
+        const char *v = arg_after(argc, argv, "-element_foundation");
+        p.element_foundation_file = v ? v : "";
+        if (!v) {
+            err << "ERROR: -element_foundation needs a file!\n";
+            failed = true;
+        } else {
+            try {
+                read_stiffness_rows(p.element_foundation_file, 2, "elem kn kt", p.foundation_elems, p.foundation_lines, p.foundation_values);
+            } catch (const std::exception &e) {
+                err << "ERROR: " << e.what() << "\n";
+                failed = true;
+            }
+        }
+    }
+    if (has_flag(argc, argv, "-springs")) {
+        const char *v = arg_after(argc, argv, "-springs");
+        p.springs_file = v ? v : "";
+        if (!v) {
+            err << "ERROR: -springs needs a file!\n";
+            failed = true;
+        } else {
+            try {
+                read_stiffness_rows(p.springs_file, 6, "node kx ky kz krx kry krz", p.spring_nodes, p.spring_lines, p.spring_values);
+            } catch (const std::exception &e) {
+                err << "ERROR: " << e.what() << "\n";
+                failed = true;
+            }
+        }
+    }
+    if (has_flag(argc, argv, "-support_forces")) {
+        p.support_forces = true;
+        if (has_flag(argc, argv, "-modes") || has_flag(argc, argv, "-dt") || has_flag(argc, argv, "-steps")) {
+            err << "ERROR: -support_forces belongs to the static solve: not with -modes or the time stepping options -dt / -steps!\n";
+            failed = true;
+        }
+    }
     if (p.element_loads_requested() && has_flag(argc, argv, "-modes")) {
         err << "ERROR: -pressure / -element_loads / -gravity do not go together with -modes (a modal analysis has no loads)!\n";
         failed = true;
@@ -812,6 +949,22 @@ void ShellSystem::set_thermal(const Parameters &p, const ThermalLoads &l)
           "femshell_set_expansion");
     check(femshell_set_thermal(ctx_, l.tri_temp.empty() ? nullptr : l.tri_temp.data(), l.quad_temp.empty() ? nullptr : l.quad_temp.data()),
           "femshell_set_thermal");
+}
+
+void ShellSystem::set_supports(const ElasticSupports &s)
+{
+    if (!s.tri_k.empty() || !s.quad_k.empty())
+        check(femshell_set_foundation(ctx_, s.tri_k.empty() ? nullptr : s.tri_k.data(), s.quad_k.empty() ? nullptr : s.quad_k.data()),
+              "femshell_set_foundation");
+    if (!s.spring_nodes.empty())
+        check(femshell_set_springs(ctx_, (int32_t)s.spring_nodes.size(), s.spring_nodes.data(), s.spring_values.data()), "femshell_set_springs");
+}
+
+std::vector<double> ShellSystem::support_forces()
+{
+    std::vector<double> f((size_t)n_nodes_ * 6, 0.0);
+    check(femshell_support_forces(ctx_, nullptr, f.data()), "femshell_support_forces");
+    return f;
 }
 
 std::vector<double> ShellSystem::reactions()
@@ -1059,6 +1212,8 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         if (p.element_loads_requested()) element_loads = build_element_loads(p, mesh, p.sections_requested() ? &section_table : nullptr); // (likewise)
         ThermalLoads thermal_loads;
         if (p.thermal_requested()) thermal_loads = build_thermal_loads(p, mesh, p.sections_requested() ? &section_table : nullptr); // (likewise)
+        ElasticSupports supports;
+        if (p.supports_requested()) supports = build_elastic_supports(p, mesh); // (likewise)
         clock.done("read mesh and loads");
         const Launch launch = Launch::from_environment();
         ShellSystem system(p, launch);
@@ -1071,6 +1226,8 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         }
         if (p.element_loads_requested()) system.set_element_loads(element_loads); // (on top of the force file's nodal loads)
         if (p.thermal_requested()) system.set_thermal(p, thermal_loads); // (on top of all other loads; after the sections: alpha belongs to them)
+        if (p.supports_requested()) system.set_supports(supports); // (K + mask(K_sup) from the first assembly on: solve, time stepping, modes, buckling)
+        if (p.support_forces && launch.world_size != 1) throw std::runtime_error("-support_forces runs on one rank");
         if (p.reactions && launch.world_size != 1) throw std::runtime_error("-reactions runs on one rank");
         if (p.stress && launch.world_size != 1) throw std::runtime_error("-stress runs on one rank");
         if (p.stress_nodes && launch.world_size != 1) throw std::runtime_error("-stress_nodes runs on one rank");
@@ -1217,6 +1374,31 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
                 a.xyz.resize((size_t)mesh.n_nodes() * 3);
                 for (int32_t n = 0; n < mesh.n_nodes(); n++)
                     for (int d = 0; d < 3; d++) a.xyz[3 * (size_t)n + d] = r[6 * (size_t)n + 3 * part + d];
+                reaction_arrays.push_back(std::move(a));
+            }
+        }
+        if (p.support_forces) {
+            // what the elastic supports exert on the shell, -K_sup u: a line per node, then the column sums
+            const std::vector<double> f = system.support_forces();
+            const std::string stem = p.isOutfileSet ? p.out_filename : std::string("out");
+            std::ofstream sf(stem + "_support.txt");
+            if (!sf) throw std::runtime_error("cannot write " + stem + "_support.txt");
+            double sum[3] = {0.0, 0.0, 0.0};
+            char line[240];
+            for (int32_t n = 0; n < mesh.n_nodes(); n++) {
+                const double *q = &f[6 * (size_t)n];
+                for (int v = 0; v < 3; v++) sum[v] += q[v];
+                snprintf(line, sizeof line, "%d %.15e %.15e %.15e %.15e %.15e %.15e\n", n, q[0], q[1], q[2], q[3], q[4], q[5]);
+                sf << line;
+            }
+            out << "Elastic supports: sum of the forces on the shell = (" << sum[0] << ", " << sum[1] << ", " << sum[2] << "), in " << stem
+                << "_support.txt" << std::endl;
+            for (int part = 0; part < 2; part++) {
+                PointVectors a;
+                a.name = part == 0 ? "support_f" : "support_m";
+                a.xyz.resize((size_t)mesh.n_nodes() * 3);
+                for (int32_t n = 0; n < mesh.n_nodes(); n++)
+                    for (int d = 0; d < 3; d++) a.xyz[3 * (size_t)n + d] = f[6 * (size_t)n + 3 * part + d];
                 reaction_arrays.push_back(std::move(a));
             }
         }

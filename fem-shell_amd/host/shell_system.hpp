@@ -124,6 +124,25 @@ struct Parameters {
     std::vector<int> thermal_lines;          // ... and its line number
     std::vector<double> thermal_values;      // ... and its two values
     bool thermal_requested() const { return temperature_set || temperature_gradient_set || !thermal_file.empty(); }
+    // elastic supports (extension, stand-alone program only; every support of the reference is rigid): femshell_set_foundation and
+    // femshell_set_springs.  -foundation KN and -foundation_shear KT: the moduli (kn, kt) of every element.  -element_foundation
+    // FILE: lines "elem kn kt" with the conventions of -element_loads, added on top of the uniform values.  -springs FILE: lines
+    // "node kx ky kz krx kry krz", node in mesh-file numbering; nodes not listed get no spring.  All values >= 0.  -support_forces,
+    // after the static solve: writes <out>_support.txt -- a line "node fx fy fz mx my mz" (%.15e) per node, the force and moment
+    // the elastic supports exert on the shell -- and the point arrays support_f / support_m of <out>.vtk; not with -modes or
+    // -dt / -steps.  The files are read with the command line; the indices are held against the mesh before any device is touched.
+    bool foundation_set = false, foundation_shear_set = false, support_forces = false;
+    double foundation = 0.0, foundation_shear = 0.0;
+    std::string element_foundation_file, springs_file;
+    std::vector<int32_t> foundation_elems;  // element of every line of the -element_foundation file
+    std::vector<int> foundation_lines;      // ... and its line number
+    std::vector<double> foundation_values;  // ... and its two values
+    std::vector<int32_t> spring_nodes;      // node of every line of the -springs file
+    std::vector<int> spring_lines;          // ... and its line number
+    std::vector<double> spring_values;      // ... and its six values
+    bool foundation_requested() const { return foundation_set || foundation_shear_set || !element_foundation_file.empty(); }
+    bool springs_requested() const { return !springs_file.empty(); }
+    bool supports_requested() const { return foundation_requested() || springs_requested(); }
     // linear buckling (extension, stand-alone program only; the reference has no stability analysis): -buckling N [-buckling_tol T],
     // after the static solve, computes the N load factors of smallest magnitude of (K + lambda K_G(u)) x = 0 with the prestress of
     // the solution (femshell_buckling); writes <out>_buckling.txt -- a '#' header, then a line "index lambda rho" (%.15e) per mode
@@ -142,6 +161,17 @@ struct SectionTable;
 // -pressure, -element_loads and -gravity added up per element (sections: the table -gravity takes the thicknesses from, or nullptr);
 // throws std::runtime_error with file name and line number on an element the mesh does not have or one listed twice
 ElementLoads build_element_loads(const Parameters &p, const ShellMesh &mesh, const SectionTable *sections);
+
+// what femshell_set_foundation and femshell_set_springs take: rows (kn, kt) of the triangles and of the quadrilaterals (empty: no
+// foundation), the nodes of the -springs file and their six values
+struct ElasticSupports {
+    std::vector<double> tri_k, quad_k;
+    std::vector<int32_t> spring_nodes;
+    std::vector<double> spring_values;
+};
+// -foundation, -foundation_shear and -element_foundation added up per element, the -springs file held against the mesh; throws
+// std::runtime_error with file name and line number on an element or a node the mesh does not have or one listed twice
+ElasticSupports build_elastic_supports(const Parameters &p, const ShellMesh &mesh);
 
 // what femshell_set_sections takes, from the files above: section 0 is the command line's material, the listed ones follow
 struct SectionTable {
@@ -222,8 +252,12 @@ class ShellSystem {
     void set_element_loads(const ElementLoads &l);
     // -alpha / -temperature / -temperature_gradient / -thermal: the rows of build_thermal_loads (after set_mesh and set_sections)
     void set_thermal(const Parameters &p, const ThermalLoads &l);
+    // -foundation / -foundation_shear / -element_foundation / -springs: the rows of build_elastic_supports (after set_mesh)
+    void set_supports(const ElasticSupports &s);
     // -reactions: r = K_unc u - loads of the last solve's solution, n_nodes x 6
     std::vector<double> reactions();
+    // -support_forces: -K_sup u of the last solve's solution, n_nodes x 6
+    std::vector<double> support_forces();
     // -stress: the element resultants of the last solve's solution, (n_tri + n_quad) x 14, triangles then quadrilaterals
     std::vector<double> element_resultants();
     // -stress_nodes: the recovered node rows (n_nodes x 14) and the element rows (e2, eta^2; triangles then quadrilaterals) of the

@@ -217,6 +217,64 @@ int femshell_set_thermal(femshell_ctx *ctx, const double *tri_temp /* n_tri x 2,
  * are set.  Two calls give the same bits. */
 int femshell_thermal_load_vector(femshell_ctx *ctx, double *f6_out /* n_nodes x 6 */);
 
+/* extends: every support the reference knows is rigid (a dof is fixed or free).  ELASTIC SUPPORTS: a plate on soil (a Winkler
+ * foundation), a panel on elastomer pads, a bolt or a neighbouring structure as a spring at a node, a free-floating shell made
+ * solvable without inventing Dirichlet nodes.
+ *
+ * Foundation, per element.  Each element gets two doubles (kn, kt), both >= 0, in force per volume (pressure per unit
+ * deflection).
+ *   kn acts along the element's own +ez.  This is the normal of femshell_set_element_loads: TRI3 c = (b-a) x (c-a), QUAD4
+ *      c = d1 x d2.
+ *   kt acts in the element's plane.
+ * The foundation is lumped with the shares of femshell_lumped_mass.  Every node of element e gets the 3 x 3 block
+ *     B_e = share_e [ kt I + (kn - kt) n n^T ],   share_e = A_e/3 (TRI3), A_e/4 (QUAD4),
+ *     A_e = |c|/2,   n = c/|c|
+ * A degenerate element (|c| = 0) contributes zero and reports nothing, as in the element loads.  The rotational rows get nothing.
+ * T_a = sum over the elements e that contain node a of B_e is taken in the order of the slice's element list, from zero.  It is
+ * stored as six words xx, yy, zz, xy, yz, zx, the project's tensor order.
+ *
+ * Springs, per node.  Each node gets six doubles (kx, ky, kz, krx, kry, krz), all >= 0, in global axes.
+ *
+ * Support table.  Per node nine doubles:
+ *   words 0-5: T_a with kx, ky, kz added to its three diagonal words (one addition each, after the row sum);
+ *   words 6-8: krx, kry, krz.
+ * K_sup is the block-diagonal matrix of these.
+ *
+ * The matrix in HBM.  After every assembly, K in HBM is K + mask(K_sup).  Entry (i, j) of a node's diagonal block receives one
+ * addition, fl(K_ij + S_ij), where neither dof i nor dof j of that node is fixed.  Nothing is added at fixed dofs, which keep the
+ * assembly's identity rows.  All other blocks are untouched, bit for bit.
+ *
+ * What follows from it: femshell_solve solves the supported shell, with either preconditioner; femshell_spmv / spmm / residual /
+ * export_bsr give products and blocks of K + mask(K_sup); dynamics steps with K + K_sup + c M; femshell_modes and
+ * femshell_buckling see the supported shell; with non-zero prescribed values F = mask(loads - K_unc u_bar - K_sup u_bar);
+ * femshell_reactions gives r = K_unc u + K_sup u - loads -- the negative residual at free dofs, the rigid support's reaction at
+ * fixed ones: over all nodes the force columns of r + femshell_support_forces + loads sum to zero.  femshell_element_product,
+ * femshell_element_matrices, femshell_geometric_product, femshell_element_resultants and femshell_nodal_resultants are the
+ * shell's own: supports carry no shell stress.
+ *
+ * femshell_set_foundation: tri_k[n_tri][2] / quad_k[n_quad][2], rows (kn, kt) in the caller's element order; every rank passes
+ * the full arrays.  NULL for one kind leaves that kind without a foundation; both NULL clears the foundation.  The call replaces
+ * the previous set.
+ * femshell_set_springs: the conventions of femshell_set_loads (node_ids == NULL: one row per node, n == n_nodes); unlisted nodes
+ * get no spring; n == 0 clears the springs.  The call replaces the previous set.
+ * Both work on row-partitioned contexts.  A changed or cleared set makes K, F, block-Jacobi and the multigrid hierarchy stale:
+ * the next use assembles again (nothing is subtracted in place).  FEMSHELL_ERR_INVALID: a negative or non-finite value, no mesh,
+ * an id out of range or listed twice, a call while dynamics is active (K_eff lies in HBM).  Every refusal leaves what was in
+ * force untouched and the context usable.  femshell_set_mesh forgets both sets; femshell_set_sections, femshell_set_dirichlet
+ * and femshell_set_density keep them (the moduli are the caller's numbers, and the mask is applied at the next assembly).  With
+ * nothing set every buffer, every launch and every bit is what it is without these functions.
+ * Kernels: csrc/elastic_support.hip. */
+int femshell_set_foundation(femshell_ctx *ctx, const double *tri_k /* n_tri x 2, or NULL */, const double *quad_k /* n_quad x 2, or NULL */);
+int femshell_set_springs(femshell_ctx *ctx, int32_t n, const int32_t *node_ids, const double *k6);
+/* out[n_nodes][9]: the support table in force, in the caller's numbering, NOT masked by the Dirichlet set; on a row-partitioned
+ * context every rank receives all rows (gathered like femshell_lumped_mass).  Zeros when nothing is set.  Two calls give the
+ * same bits, at every grid size. */
+int femshell_support_stiffness(femshell_ctx *ctx, double *out /* n_nodes x 9 */);
+/* f6_out[n_nodes][6] = -K_sup u, the force and moment the elastic supports exert on the shell, in the caller's numbering; u ==
+ * NULL: the last solution (with the prescribed values in force added).  Needs a mesh, not an assembled K.  Zeros when nothing is
+ * set.  FEMSHELL_ERR_UNSUPPORTED on a row-partitioned context, like femshell_reactions. */
+int femshell_support_forces(femshell_ctx *ctx, const double *u /* n_nodes x 6, or NULL */, double *f6_out /* n_nodes x 6 */);
+
 /* replaces: assemble_elasticity (SA:1160-1233): element stiffness (initElement, calcPlane,
  * calcPlate, constructStiffnessMatrix, localToGlobalTrafo), constraint handling, add_matrix /
  * add_vector.  K and F stay in HBM. */
@@ -856,7 +914,11 @@ typedef enum femshell_kernel {
     /* k_recovery_error back to back on the same rows and their nodal averages; needs a mesh only.  bytes_out: 12 / 16 bytes of
      * node ids, 96 of tensor words and 16 of output per element (4 more of a section index where the context has sections),
      * coordinates and recovered tensors (24 + 96 bytes) once per node */
-    FEMSHELL_KERNEL_RECOVERY_ERROR = 17
+    FEMSHELL_KERNEL_RECOVERY_ERROR = 17,
+    /* k_support_rows back to back on hashed moduli into a scratch table; needs a mesh only, the table in force is not disturbed.
+     * bytes_out: 16 bytes of node ids, 4 of element index and 16 of moduli per entry of the slices' element lists, 24 bytes of
+     * coordinates per node, 72 bytes written per row of the slices (padding rows included) */
+    FEMSHELL_KERNEL_ELASTIC_SUPPORT = 18
 } femshell_kernel;
 
 /* mean duration of one launch of the kernel from HIP events on the library's stream, over `reps` launches:
