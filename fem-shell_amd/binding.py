@@ -46,6 +46,7 @@ SYMBOLS = [
     "femshell_set_expansion", "femshell_set_thermal", "femshell_thermal_load_vector",
     "femshell_set_foundation", "femshell_set_springs", "femshell_support_stiffness", "femshell_support_forces",
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
+    "femshell_solve_cases",
     "femshell_pool_stats", "femshell_amg_device_dense_inverse", "femshell_amg_dense_apply",
     "femshell_amg_device_block_jacobi", "femshell_block_jacobi_export", "femshell_block_jacobi_apply",
     "femshell_krylov_grid", "femshell_krylov_set", "femshell_krylov_get", "femshell_krylov_launch", "femshell_cg_reduce",
@@ -121,6 +122,15 @@ class BucklingInfo(C.Structure):
                 ("inner_iterations", C.c_int64), ("rho_max", C.c_double),
                 ("seconds_total", C.c_double), ("seconds_solves", C.c_double), ("seconds_products", C.c_double),
                 ("seconds_gram", C.c_double), ("seconds_update", C.c_double)]
+
+
+class CaseInfo(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("converged", C.c_int32), ("rel_residual", C.c_double)]
+
+
+class CasesInfo(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("fused_product", C.c_int32), ("pc_type", C.c_int32), ("reserved", C.c_int32),
+                ("solve_seconds", C.c_double), ("bytes_per_iteration", C.c_double)]
 
 
 class KrylovScalars(C.Structure):
@@ -259,6 +269,7 @@ def load_library():
     L.femshell_geometric_product.argtypes = [vp, dp, C.c_int32, dp, dp]
     L.femshell_buckling_defaults.argtypes = [C.POINTER(BucklingOptions)]
     L.femshell_buckling.argtypes = [vp, C.POINTER(BucklingOptions), dp, dp, dp, dp, C.POINTER(BucklingInfo)]
+    L.femshell_solve_cases.argtypes = [vp, C.c_int32, dp, C.c_double, C.c_int32, dp, C.POINTER(CaseInfo), C.POINTER(CasesInfo)]
     L.femshell_pool_stats.argtypes = [dp]
     L.femshell_amg_device_dense_inverse.argtypes = [vp, C.c_int32, ip, ip, dp, C.c_int32, dp, dp]
     L.femshell_amg_dense_apply.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, dp, dp]
@@ -631,6 +642,30 @@ class FemShell:
         d = {f[0]: getattr(info, f[0]) for f in BucklingInfo._fields_}
         d["rho"] = rho
         return lam, modes, d
+
+    def solve_cases(self, loads, rtol=1e-10, max_it=10000):
+        """Several load cases on the K of this context (femshell_solve_cases): loads is (n_cases, n_nodes, 6) or (n_cases,
+        n_nodes * 6), or one vector of n_nodes x 6 entries; a case's vector is its whole load -- the context's own loads are not
+        added, the Dirichlet set applies with zero values.  Returns (u (n_cases, n_nodes, 6), a list of per-case dicts with
+        iterations, converged (1, 0, -1: breakdown) and rel_residual, an info dict).  Every case is bit for bit what it is when
+        solved alone.  After a breakdown in a case the FemShellError carries u, cases and info as attributes."""
+        loads = np.ascontiguousarray(loads, dtype=np.float64)
+        n6 = 6 * self.n_nodes
+        if loads.size == 0 or loads.size % n6 != 0:
+            raise ValueError("loads needs n_nodes x 6 entries per case")
+        loads = loads.reshape(-1, n6)
+        n_cases = loads.shape[0]
+        u = np.zeros((n_cases, self.n_nodes, 6))
+        ci = (CaseInfo * n_cases)()
+        info = CasesInfo()
+        rc = self._L.femshell_solve_cases(self._h, n_cases, _d(loads), float(rtol), int(max_it), _d(u), ci, C.byref(info))
+        cases = [{f[0]: getattr(ci[j], f[0]) for f in CaseInfo._fields_} for j in range(n_cases)]
+        d = {f[0]: getattr(info, f[0]) for f in CasesInfo._fields_ if f[0] != "reserved"}
+        if rc != 0:
+            err = FemShellError(rc, load_library().femshell_last_error().decode())
+            err.u, err.cases, err.info = u, cases, d
+            raise err
+        return u, cases, d
 
     def modal_gram(self, A, B, weighted):
         """A^T diag(w) B by the Gram kernel of modes(): A (qa, n_nodes * 6), B (qb, n_nodes * 6), columns as rows of the arrays;

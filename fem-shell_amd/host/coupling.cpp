@@ -331,6 +331,11 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
         out << "Read command-line arguments.......FAILED" << std::endl;
         return -1;
     }
+    if (p.load_cases_requested()) {
+        err << "ERROR: -load_cases is an option of the stand-alone program FEM-shell!\n";
+        out << "Read command-line arguments.......FAILED" << std::endl;
+        return -1;
+    }
     const char *config = arg_after(argc, argv, "-config");
     const char *dtv = arg_after(argc, argv, "-dt");
     if (!config) err << "ERROR: preCICE configuration file not specified!\n";

@@ -1,5 +1,6 @@
 // shell_system.cpp -- see shell_system.hpp
 #include "shell_system.hpp"
+#include "load_cases.hpp"
 
 #include <chrono>
 #include <cmath>
@@ -387,7 +388,12 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "-buckling:\t after the static solve: the N load factors of smallest magnitude (signed) at which the solved load case\n"
             << "\t buckles, N in 1 .. 28; writes <out>_buckling.txt, lines 'index lambda rho', and the shapes as point arrays\n"
             << "\t buckling_<k>_u / buckling_<k>_r of <out>.vtk (optional; not with -modes or -dt / -steps)\n"
-            << "-buckling_tol:\t tolerance of the pairs' convergence measure rho (with -buckling, default 1e-8)\n";
+            << "-buckling_tol:\t tolerance of the pairs' convergence measure rho (with -buckling, default 1e-8)\n"
+            << "-load_cases:\t file that lists one force file per line (at most 32; '#' comments; paths relative to the list): every file\n"
+            << "\t is the whole load of one case on the same model, all solved in one call in place of the single solve; writes\n"
+            << "\t <out>_case<k>.vtk and <out>_cases.txt, lines 'k file iterations converged rel_residual' (optional; the mesh's own\n"
+            << "\t force file is not read; not with -modes, -buckling, -dt / -steps, -prescribed, -reactions, -stress, -stress_nodes,\n"
+            << "\t -support_forces, nor with -pressure, -element_loads, -gravity or the thermal options)\n";
         return false;
     }
     bool failed = false;
@@ -775,6 +781,29 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             failed = true;
         }
     }
+    // load cases: the list is read here, so that a missing list, a missing listed file, an empty or too long list and an option
+    // that does not go together with it are refused like any other option
+    if (has_flag(argc, argv, "-load_cases")) {
+        const char *v = arg_after(argc, argv, "-load_cases");
+        p.load_cases_file = v ? v : "";
+        if (!v) {
+            err << "ERROR: -load_cases needs a file!\n";
+            failed = true;
+        } else {
+            try {
+                p.load_case_files = read_load_cases_list(p.load_cases_file, &p.load_case_names);
+            } catch (const std::exception &e) {
+                err << "ERROR: " << e.what() << "\n";
+                failed = true;
+            }
+        }
+        const std::string conflicts = load_cases_conflicts(argc, argv);
+        if (!conflicts.empty()) {
+            err << "ERROR: -load_cases does not go together with " << conflicts
+                << ": a case is its force file and nothing else, solved in place of the single static solve!\n";
+            failed = true;
+        }
+    }
     if (p.element_loads_requested() && has_flag(argc, argv, "-modes")) {
         err << "ERROR: -pressure / -element_loads / -gravity do not go together with -modes (a modal analysis has no loads)!\n";
         failed = true;
@@ -1064,6 +1093,18 @@ void ShellSystem::assemble_elasticity(const std::string &system_name)
     check(femshell_assemble(ctx_), "femshell_assemble");
 }
 
+femshell_cases_info ShellSystem::solve_cases(const std::vector<double> &loads, int n_cases, double tol, int max_it, std::vector<double> &u,
+                                             std::vector<femshell_case_info> &cases)
+{
+    if (n_cases < 1 || loads.size() != (size_t)n_cases * (size_t)n_nodes_ * 6)
+        throw std::runtime_error("solve_cases: need one row of 6 per mesh node and case");
+    u.assign(loads.size(), 0.0);
+    cases.assign((size_t)n_cases, femshell_case_info{});
+    femshell_cases_info info{};
+    check(femshell_solve_cases(ctx_, n_cases, loads.data(), tol, max_it, u.data(), cases.data(), &info), "femshell_solve_cases");
+    return info;
+}
+
 SolveResult ShellSystem::solve(double tol, int max_it)
 {
     SolveResult r;
@@ -1205,6 +1246,17 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         } catch (const std::exception &) {
             mesh.loads.assign((size_t)mesh.n_nodes() * 6, 0.0);
         }
+        // -load_cases: every listed file is the whole load of its case (read before any device is touched)
+        std::vector<double> case_loads;
+        if (p.load_cases_requested()) {
+            const size_t n6 = (size_t)mesh.n_nodes() * 6;
+            for (const std::string &file : p.load_case_files) {
+                const std::vector<double> f = read_forces(file, mesh.n_nodes());
+                if (f.size() != n6) throw std::runtime_error(file + ": expected " + std::to_string(mesh.n_nodes()) + " rows of 6");
+                case_loads.insert(case_loads.end(), f.begin(), f.end());
+            }
+            mesh.loads.assign(n6, 0.0); // (the context's own loads play no part)
+        }
         SectionTable section_table;
         if (p.sections_requested()) section_table = read_sections(p, mesh);
         if (p.prescribed_requested()) check_prescribed_nodes(p, mesh.n_nodes()); // (before any device is touched)
@@ -1233,6 +1285,47 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
         if (p.stress_nodes && launch.world_size != 1) throw std::runtime_error("-stress_nodes runs on one rank");
         if (p.buckling_requested() && launch.world_size != 1) throw std::runtime_error("-buckling runs on one rank");
         clock.done("symbolic phase, boundary conditions, loads");
+        if (p.load_cases_requested()) {
+            // the listed load cases in one call instead of the single solve
+            if (launch.world_size != 1) throw std::runtime_error("-load_cases runs on one rank");
+            const int n_cases = (int)p.load_case_files.size();
+            std::vector<double> u;
+            std::vector<femshell_case_info> cases;
+            const femshell_cases_info ci = system.solve_cases(case_loads, n_cases, p.tol, p.max_it, u, cases);
+            clock.done("assembly, preconditioner setup, load cases");
+            const std::string stem = p.isOutfileSet ? p.out_filename : std::string("out");
+            std::ofstream cf(stem + "_cases.txt");
+            if (!cf) throw std::runtime_error("cannot write " + stem + "_cases.txt");
+            const size_t n6 = (size_t)mesh.n_nodes() * 6;
+            bool all_converged = true;
+            for (int k = 0; k < n_cases; k++) {
+                const femshell_case_info &c = cases[(size_t)k];
+                char tail[96];
+                snprintf(tail, sizeof tail, " %d %d %.15e\n", c.iterations, c.converged, c.rel_residual);
+                cf << k + 1 << " " << p.load_case_names[(size_t)k] << tail;
+                all_converged = all_converged && c.converged == 1;
+                const std::vector<double> uk(u.begin() + (std::ptrdiff_t)((size_t)k * n6), u.begin() + (std::ptrdiff_t)((size_t)(k + 1) * n6));
+                std::vector<PointVectors> arrays(2);
+                for (int part = 0; part < 2; part++) {
+                    arrays[(size_t)part].name = part == 0 ? "displacement" : "rotation";
+                    arrays[(size_t)part].xyz.resize((size_t)mesh.n_nodes() * 3);
+                    for (int32_t n = 0; n < mesh.n_nodes(); n++)
+                        for (int d = 0; d < 3; d++) arrays[(size_t)part].xyz[3 * (size_t)n + d] = uk[6 * (size_t)n + 3 * part + d];
+                }
+                write_vtk(mesh, uk, stem + "_case" + std::to_string(k + 1) + ".vtk", &arrays);
+                out << " case " << k + 1 << " (" << p.load_case_names[(size_t)k] << "): " << c.iterations << " iterations, ||r||/||b|| = " << c.rel_residual
+                    << (c.converged == 1 ? "" : " (NOT converged)") << std::endl;
+            }
+            out << "Load cases: " << n_cases << " cases in " << ci.passes << (ci.passes == 1 ? " pass" : " passes") << " ("
+                << (ci.pc_type == FEMSHELL_PC_AMG ? "multigrid-preconditioned CG, one case after another"
+                                                  : (ci.fused_product ? "6x6 block-Jacobi CG in lockstep, one pass over K for the cases of a pass"
+                                                                      : "6x6 block-Jacobi CG in lockstep"))
+                << "), " << ci.solve_seconds << " s; " << stem << "_cases.txt, " << stem << "_case<k>.vtk" << std::endl;
+            clock.done("output files");
+            out << "All done :)\n";
+            clock.report(err);
+            return all_converged ? 0 : 2;
+        }
         if (p.modes_requested()) {
             // natural frequencies and mode shapes instead of a solve
             if (launch.world_size != 1) throw std::runtime_error("-modes runs on one rank");

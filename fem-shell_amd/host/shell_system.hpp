@@ -151,6 +151,16 @@ struct Parameters {
     int buckling = 0;
     double buckling_tol = 1e-8;
     bool buckling_requested() const { return buckling > 0; }
+    // load cases (extension, stand-alone program only; the reference solves the one load of its `_f` file): -load_cases FILE lists
+    // one force file per line (load_cases.hpp), each the whole load of its case; the run calls femshell_solve_cases in place of the
+    // single solve and writes <out>_case<k>.vtk (k from 1: the displaced mesh with the point vectors displacement and rotation,
+    // every digit) and <out>_cases.txt, a line "k file iterations converged rel_residual" (%.15e) per case.  The list is read with
+    // the command line.  Not with another analysis or output of the single solve (-modes, -buckling, -dt / -steps, -prescribed,
+    // -reactions, -stress, -stress_nodes, -support_forces) and not with another source of loads (-pressure, -element_loads,
+    // -gravity, the thermal flags): a case is its force file and nothing else.  The `_f` file of the mesh is not read.
+    std::string load_cases_file;
+    std::vector<std::string> load_case_files, load_case_names; // the paths as they are opened, the words of the list
+    bool load_cases_requested() const { return !load_cases_file.empty(); }
 };
 
 // what femshell_set_element_loads takes: rows (p, qx, qy, qz) of the triangles and of the quadrilaterals
@@ -283,6 +293,9 @@ class ShellSystem {
     // linear buckling under the prestress of the last solve: femshell_buckling with the library's defaults for guard and iteration
     // limit; lambda[n], shapes[n][n_nodes][6], rho[n]
     femshell_buckling_info buckling(const Parameters &p, std::vector<double> &lambda, std::vector<double> &shapes, std::vector<double> &rho);
+    // -load_cases: femshell_solve_cases for loads[n_cases][n_nodes][6]; u in the same layout, one info per case
+    femshell_cases_info solve_cases(const std::vector<double> &loads, int n_cases, double tol, int max_it, std::vector<double> &u,
+                                    std::vector<femshell_case_info> &cases);
     femshell_ctx *handle() { return ctx_; }
 
   private:

@@ -799,6 +799,46 @@ int femshell_buckling(femshell_ctx *ctx, const femshell_buckling_options *opt, c
                       double *lambda_out /* n_modes */, double *modes_out /* n_modes x n_nodes x 6, or NULL */,
                       double *rho_out /* n_modes, or NULL */, femshell_buckling_info *info);
 
+/* ---- load cases: several right-hand sides on one K ----------------------------------------------------------------------
+ * extends: the reference solves one load per run (fem-shell.cpp:138); a structural job is a list of load cases on one model.
+ *     K u_j = mask(loads_j),  j = 0 .. n_cases - 1  (1 <= n_cases <= 32),
+ * from zero, with the K the context holds: sections and elastic supports included, the Dirichlet set with ZERO values.
+ * loads: n_cases x n_nodes x 6 in the caller's numbering (FEMSHELL_REORDER too), case j at loads + j * n_nodes * 6.  A CASE'S
+ * VECTOR IS THE WHOLE LOAD OF THAT CASE: the context's own nodal, element and thermal loads are NOT added.  Compose cases from
+ * femshell_element_load_vector and femshell_thermal_load_vector, which return exactly such vectors.  u_out: the same layout.
+ *
+ * Block-Jacobi contexts (csrc/cases.cpp, cases.hip): the classic preconditioned CG of femshell_solve for every case ON ITS OWN
+ * RECURRENCE -- one alpha, beta and done flag per column; this is not block CG -- in passes of four cases (fewer where the LDS of
+ * the block product says so, and a narrower last pass).  Per iteration one pass over the stored blocks of K multiplies all
+ * columns of the pass (k_spmm_sym with symmetric storage; column by column through the single-vector kernel with full storage:
+ * info->fused_product says which), and the vector kernels read every node's D^-1 block once for all columns.  A finished case is
+ * frozen: the result of a case -- u, iterations, residual -- is bit for bit what it is when the case is solved alone, in any
+ * position of a pass, beside any company; partial sums are added in a fixed order without atomics: two calls give the same bits.
+ * The sums are grouped differently from femshell_solve's, so u agrees with femshell_solve to rounding, not to the bit.
+ * Multigrid contexts (femshell_set_preconditioner): the cases run one after another through the context's multigrid-preconditioned
+ * CG, sharing K, the hierarchy and the transfers (fused_product = 0, passes = n_cases).
+ *
+ * Stopping rule per case, femshell_solve's: ||r_j|| <= rtol ||b_j||; rtol <= 0 runs exactly max_it iterations of every case; a case
+ * with b_j = 0 returns zeros, 0 iterations, converged.  case_info[j] (or NULL): iterations, converged (1, 0: max_it reached, -1:
+ * breakdown) and the recurrence's ||r|| / ||b||.  info (or NULL): the passes, the product, the preconditioner, the seconds of the
+ * Krylov loops and the algorithmic bytes of one iteration of every case.
+ * The context is left as it was: F, the last solution and its history, a pending initial guess and the refinement statistics stay;
+ * K, block-Jacobi and, under multigrid, the hierarchy are brought up to date and kept.
+ * A breakdown (p.Kp <= 0) in a case freezes that case with converged = -1; the others finish, all of u_out is written and the call
+ * returns FEMSHELL_ERR_BREAKDOWN.
+ * FEMSHELL_ERR_UNSUPPORTED on a row-partitioned context (world_size != 1).  FEMSHELL_ERR_INVALID, u_out not written: no mesh, a
+ * NULL ctx, loads or u_out, n_cases out of 1 .. 32, max_it < 0, a non-finite load, dynamics active, prescribed displacements in
+ * force (the cases use zero values at the fixed dofs; femshell_set_prescribed with n = 0 clears them).  The context stays usable
+ * after every refusal. */
+typedef struct femshell_case_info { int32_t iterations, converged; double rel_residual; } femshell_case_info;
+typedef struct femshell_cases_info {
+    int32_t passes, fused_product /* 1: k_spmm_sym ran */, pc_type, reserved;
+    double solve_seconds, bytes_per_iteration;
+} femshell_cases_info;
+int femshell_solve_cases(femshell_ctx *ctx, int32_t n_cases, const double *loads /* n_cases x n_nodes x 6 */, double rtol, int32_t max_it,
+                         double *u_out /* n_cases x n_nodes x 6 */, femshell_case_info *case_info /* n_cases, or NULL */,
+                         femshell_cases_info *info /* or NULL */);
+
 /* test entry: G = A^T diag(w) B (qa x qb, row-major) by the solver's Gram kernel; A, B: qa / qb columns of n_nodes x 6 in the
  * caller's numbering, 1 <= qa, qb <= 96; weighted != 0: w = the lumped mass (a density must be set), else w = 1.  Partial sums
  * are added in a fixed order: two calls give the same bits. */
