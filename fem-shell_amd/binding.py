@@ -46,7 +46,7 @@ SYMBOLS = [
     "femshell_set_expansion", "femshell_set_thermal", "femshell_thermal_load_vector",
     "femshell_set_foundation", "femshell_set_springs", "femshell_support_stiffness", "femshell_support_forces",
     "femshell_geometric_product", "femshell_buckling_defaults", "femshell_buckling",
-    "femshell_solve_cases",
+    "femshell_solve_cases", "femshell_combination_envelope",
     "femshell_pool_stats", "femshell_amg_device_dense_inverse", "femshell_amg_dense_apply",
     "femshell_amg_device_block_jacobi", "femshell_block_jacobi_export", "femshell_block_jacobi_apply",
     "femshell_krylov_grid", "femshell_krylov_set", "femshell_krylov_get", "femshell_krylov_launch", "femshell_cg_reduce",
@@ -131,6 +131,10 @@ class CaseInfo(C.Structure):
 class CasesInfo(C.Structure):
     _fields_ = [("passes", C.c_int32), ("fused_product", C.c_int32), ("pc_type", C.c_int32), ("reserved", C.c_int32),
                 ("solve_seconds", C.c_double), ("bytes_per_iteration", C.c_double)]
+
+
+class EnvelopeInfo(C.Structure):
+    _fields_ = [("seconds_cases", C.c_double), ("seconds_envelope", C.c_double), ("bytes_cases", C.c_double), ("bytes_envelope", C.c_double)]
 
 
 class KrylovScalars(C.Structure):
@@ -270,6 +274,7 @@ def load_library():
     L.femshell_buckling_defaults.argtypes = [C.POINTER(BucklingOptions)]
     L.femshell_buckling.argtypes = [vp, C.POINTER(BucklingOptions), dp, dp, dp, dp, C.POINTER(BucklingInfo)]
     L.femshell_solve_cases.argtypes = [vp, C.c_int32, dp, C.c_double, C.c_int32, dp, C.POINTER(CaseInfo), C.POINTER(CasesInfo)]
+    L.femshell_combination_envelope.argtypes = [vp, C.c_int32, dp, dp, C.c_int32, dp, dp, ip, C.POINTER(EnvelopeInfo)]
     L.femshell_pool_stats.argtypes = [dp]
     L.femshell_amg_device_dense_inverse.argtypes = [vp, C.c_int32, ip, ip, dp, C.c_int32, dp, dp]
     L.femshell_amg_dense_apply.argtypes = [vp, C.c_int32, C.c_int32, dp, C.c_int32, dp, dp]
@@ -666,6 +671,36 @@ class FemShell:
             err.u, err.cases, err.info = u, cases, d
             raise err
         return u, cases, d
+
+    def combination_envelope(self, u, factors, case_thermal=None):
+        """The stress envelope of every element over load combinations (femshell_combination_envelope): u is (n_cases, n_nodes, 6)
+        as solve_cases returns it (or one vector of n_nodes x 6 entries), factors (n_combos, n_cases) -- combination c is
+        sum_j factors[c, j] (case j) --, case_thermal (n_cases,) the multiple of the free thermal state each case was loaded with
+        (None: zeros).  Returns (env (n_elements, 6): max von Mises top and bottom, max N1, min N2, max M1, min M2 over the
+        combinations; gov (n_elements, 6) int32: the lowest combination index, from 0, that attains each; an info dict).  Rows
+        are the triangles of set_mesh in their order, then the quadrilaterals."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        n6 = 6 * self.n_nodes
+        if u.size == 0 or n6 == 0 or u.size % n6 != 0:
+            raise ValueError("u needs n_nodes x 6 entries per case")
+        u = u.reshape(-1, n6)
+        n_cases = u.shape[0]
+        factors = np.ascontiguousarray(factors, dtype=np.float64)
+        if factors.ndim == 1:
+            factors = factors.reshape(1, -1)
+        if factors.ndim != 2 or factors.shape[0] == 0 or factors.shape[1] != n_cases:
+            raise ValueError("factors needs n_cases entries per combination")
+        if case_thermal is not None:
+            case_thermal = np.ascontiguousarray(case_thermal, dtype=np.float64).reshape(-1)
+            if case_thermal.size != n_cases:
+                raise ValueError("case_thermal needs one entry per case")
+        ne = self.n_tri + self.n_quad
+        env = np.zeros((ne, 6))
+        gov = np.zeros((ne, 6), dtype=np.int32)
+        info = EnvelopeInfo()
+        _check(self._L.femshell_combination_envelope(self._h, n_cases, _d(u), _d(case_thermal), factors.shape[0], _d(factors), _d(env), _i(gov),
+                                                     C.byref(info)))
+        return env, gov, {f[0]: getattr(info, f[0]) for f in EnvelopeInfo._fields_}
 
     def modal_gram(self, A, B, weighted):
         """A^T diag(w) B by the Gram kernel of modes(): A (qa, n_nodes * 6), B (qb, n_nodes * 6), columns as rows of the arrays;

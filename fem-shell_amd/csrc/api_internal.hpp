@@ -1,6 +1,6 @@
 // api_internal.hpp -- what the files of the C ABI share: api.cpp (context, mesh and its data, solve, export, products), api_state.cpp
 // (what of the context's derived state is valid, and the functions that make it so), api_dynamics.cpp, api_modal.cpp,
-// api_resultants.cpp, api_element_loads.cpp, api_thermal.cpp, api_elastic_support.cpp, api_cases.cpp, api_timing.cpp.  Not for the rest of the library.  Each function is described where it is defined: api.cpp, but
+// api_resultants.cpp, api_element_loads.cpp, api_thermal.cpp, api_elastic_support.cpp, api_cases.cpp, api_envelope.cpp, api_timing.cpp.  Not for the rest of the library.  Each function is described where it is defined: api.cpp, but
 // for the block from invalidate to timed_assembly_done (api_state.cpp), the byte models of the hot-path kernels (api_timing.cpp)
 // and what api_resultants.cpp shares with the timing hook.
 #pragma once

@@ -268,6 +268,22 @@ struct RecoveryMat {
 void launch_recovery_error(const DeviceMatrix &m, const RecoveryMat &mat, const RecoveryMat *sec_mat, const int32_t *elem_section,
                            const double *res, const double *nodes, double *out, hipStream_t st);
 
+// Load combinations (envelope.hip).
+// launch_case_resultants: table[n_cases][6][n_ltri + n_lquad] = per case and LOCAL element (Nxx, Nyy, Nxy, Mxx, Myy, Mxy) in the
+// element frame, N_loc = t Dm (eps(u_j) - tau_j eps0), M_loc = -Dp (kappa(u_j) - tau_j kappa0), from the columns u + j * ld (each
+// (n_pad + n_ghost) x 6).  thermal != nullptr: the instantiations that read case_tau[n_cases] (HBM) and the element temperatures;
+// nullptr: tau = 0 for every case, case_tau is not looked at.  A case's words do not depend on the other cases or on its index.
+// A degenerate element writes zeros and reports kStatusDirect + its index through m.status.
+// launch_envelope: per LOCAL element env[6] = (max q0, max q1, max q2, min q3, max q4, min q5) over the n_combos rows
+// sum_j factors[c][j] table[j] (summed in index order) and gov[6] = the lowest c that attains each; elem_section / sec_t: the
+// section of every local element and the thickness of every section, or nullptr twice: mc.t.  gov holds 6 (n_ltri + n_lquad) + 2
+// int32: the last wave stores whole 16-byte words.  One lane per element, no atomics: two launches give the same bits.
+constexpr int kEnvCombosPerPass = 4; // combinations k_envelope forms from one reading of the table
+void launch_case_resultants(const DeviceMatrix &m, const MatConst &mc, const DeviceSections *sections, const ThermalView *thermal, const double *u,
+                            int64_t ld, int n_cases, const double *case_tau, double *table, hipStream_t st);
+void launch_envelope(const DeviceMatrix &m, const MatConst &mc, const int32_t *elem_section, const double *sec_t, const double *table, int n_cases,
+                     const double *factors, int n_combos, double *env, int32_t *gov, hipStream_t st);
+
 // ---- sparse products (spmv_kernels.hip) ----
 // What a product does with its result besides storing it: what the callers fill and what k_spmv receives.
 struct SpmvEpilogue {

@@ -331,8 +331,8 @@ int fem_shell_precice_main(int argc, char **argv, std::ostream &out, std::ostrea
         out << "Read command-line arguments.......FAILED" << std::endl;
         return -1;
     }
-    if (p.load_cases_requested()) {
-        err << "ERROR: -load_cases is an option of the stand-alone program FEM-shell!\n";
+    if (p.load_cases_requested() || p.combinations_requested()) {
+        err << "ERROR: -load_cases / -combinations are options of the stand-alone program FEM-shell!\n";
         out << "Read command-line arguments.......FAILED" << std::endl;
         return -1;
     }

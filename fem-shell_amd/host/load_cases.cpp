@@ -1,6 +1,8 @@
 // load_cases.cpp -- see load_cases.hpp
 #include "load_cases.hpp"
 
+#include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -34,6 +36,39 @@ std::vector<std::string> read_load_cases_list(const std::string &list_file, std:
     }
     if (files.empty()) throw std::runtime_error(list_file + ": the list names no force file");
     return files;
+}
+
+std::vector<double> read_combinations(const std::string &file, int n_cases)
+{
+    std::ifstream in(file);
+    if (!in) throw std::runtime_error("cannot open " + file);
+    std::vector<double> factors;
+    int n_combos = 0;
+    std::string line;
+    for (int no = 1; std::getline(in, line); no++) {
+        const size_t h = line.find('#');
+        if (h != std::string::npos) line.erase(h);
+        std::istringstream is(line);
+        std::string word;
+        int count = 0;
+        const std::string where = file + ": line " + std::to_string(no) + ": ";
+        while (is >> word) {
+            char *end = nullptr;
+            const double v = std::strtod(word.c_str(), &end);
+            if (end == word.c_str() || *end != '\0') throw std::runtime_error(where + "'" + word + "' is not a number");
+            if (!std::isfinite(v)) throw std::runtime_error(where + "'" + word + "' is not a finite number");
+            if (count == 0 && n_combos == kMaxCombinations)
+                throw std::runtime_error(where + "more than " + std::to_string(kMaxCombinations) + " combinations");
+            factors.push_back(v);
+            count++;
+        }
+        if (count == 0) continue; // blank or comment
+        if (count != n_cases)
+            throw std::runtime_error(where + "expected " + std::to_string(n_cases) + " factors, one per load case, found " + std::to_string(count));
+        n_combos++;
+    }
+    if (n_combos == 0) throw std::runtime_error(file + ": the file holds no combination");
+    return factors;
 }
 
 std::string load_cases_conflicts(int argc, char **argv)

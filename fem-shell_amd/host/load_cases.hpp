@@ -23,4 +23,13 @@ std::vector<std::string> read_load_cases_list(const std::string &list_file, std:
 // nothing else.  Returns the offending flags, separated by blanks; empty: none.
 std::string load_cases_conflicts(int argc, char **argv);
 
+constexpr int kMaxCombinations = 256; // femshell_combination_envelope takes 1 .. 256 combinations
+
+// -combinations FILE2: one load combination per line, exactly n_cases numbers each -- the factors of the cases in the order of
+// the list of -load_cases.  The conventions of the list reader: '#' starts a comment, blank lines are skipped, every token is
+// parsed whole, every message names the file and the line.  Throws std::runtime_error for a file that cannot be opened, a line
+// with another count of numbers, a token that is no number or not finite, a file without a combination and more than
+// kMaxCombinations lines.  Returns the factors row by row, n_combos x n_cases.
+std::vector<double> read_combinations(const std::string &file, int n_cases);
+
 } // namespace femshell_host

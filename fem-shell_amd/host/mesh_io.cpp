@@ -692,8 +692,11 @@ void write_vtk(const ShellMesh &m, const std::vector<double> &u, const std::stri
                 wide++;
                 continue;
             }
-            os << "SCALARS " << a.name << " double 1\nLOOKUP_TABLE default\n";
-            rows(a);
+            os << "SCALARS " << a.name << (a.integer ? " int" : " double") << " 1\nLOOKUP_TABLE default\n";
+            if (a.integer)
+                for (long e = 0; e < count; e++) os << (long)a.values[(size_t)e] << "\n";
+            else
+                rows(a);
         }
         if (wide) {
             os << "FIELD " << field << " " << wide << "\n";

@@ -105,6 +105,7 @@ struct CellArray {
     std::string name;
     int components = 1;
     std::vector<double> values; // n_elements x components
+    bool integer = false;       // one component only: the values are whole numbers, written as SCALARS <name> int 1
 };
 // point_arrays: the same for the nodes (the recovered tensors and the fold measure of FEM-shell -stress_nodes), one tuple per node,
 // behind the point vectors

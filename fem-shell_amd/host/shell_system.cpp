@@ -393,7 +393,11 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             << "\t is the whole load of one case on the same model, all solved in one call in place of the single solve; writes\n"
             << "\t <out>_case<k>.vtk and <out>_cases.txt, lines 'k file iterations converged rel_residual' (optional; the mesh's own\n"
             << "\t force file is not read; not with -modes, -buckling, -dt / -steps, -prescribed, -reactions, -stress, -stress_nodes,\n"
-            << "\t -support_forces, nor with -pressure, -element_loads, -gravity or the thermal options)\n";
+            << "\t -support_forces, nor with -pressure, -element_loads, -gravity or the thermal options)\n"
+            << "-combinations:\t with -load_cases: file with one load combination per line, a factor per listed case (at most 256 lines;\n"
+            << "\t '#' comments); writes <out>_envelope.txt, per element the largest surface von Mises stresses, the extreme principal\n"
+            << "\t membrane forces and moments over all combinations and the combination (from 1) that governs each, and the same as\n"
+            << "\t cell arrays of <out>_envelope.vtk (optional)\n";
         return false;
     }
     bool failed = false;
@@ -804,6 +808,25 @@ bool read_parameters(int argc, char **argv, Parameters &p, std::ostream &out, st
             failed = true;
         }
     }
+    // load combinations: the factors are read here too, against the count of cases the list gave
+    if (has_flag(argc, argv, "-combinations")) {
+        const char *v = arg_after(argc, argv, "-combinations");
+        p.combinations_file = v ? v : "";
+        if (!v) {
+            err << "ERROR: -combinations needs a file!\n";
+            failed = true;
+        } else if (!has_flag(argc, argv, "-load_cases")) {
+            err << "ERROR: -combinations needs -load_cases: a combination is a row of factors, one per listed load case!\n";
+            failed = true;
+        } else if (!p.load_case_files.empty()) { // (a refused list has said so already)
+            try {
+                p.combination_factors = read_combinations(p.combinations_file, (int)p.load_case_files.size());
+            } catch (const std::exception &e) {
+                err << "ERROR: " << e.what() << "\n";
+                failed = true;
+            }
+        }
+    }
     if (p.element_loads_requested() && has_flag(argc, argv, "-modes")) {
         err << "ERROR: -pressure / -element_loads / -gravity do not go together with -modes (a modal analysis has no loads)!\n";
         failed = true;
@@ -1105,6 +1128,20 @@ femshell_cases_info ShellSystem::solve_cases(const std::vector<double> &loads, i
     return info;
 }
 
+femshell_envelope_info ShellSystem::combination_envelope(const std::vector<double> &u, int n_cases, const std::vector<double> &factors,
+                                                         std::vector<double> &env, std::vector<int32_t> &gov)
+{
+    if (n_cases < 1 || u.size() != (size_t)n_cases * (size_t)n_nodes_ * 6 || factors.empty() || factors.size() % (size_t)n_cases != 0)
+        throw std::runtime_error("combination_envelope: need one row of 6 per mesh node and case, and one factor per case and combination");
+    env.assign((size_t)n_elems_ * 6, 0.0);
+    gov.assign((size_t)n_elems_ * 6, 0);
+    femshell_envelope_info info{};
+    check(femshell_combination_envelope(ctx_, n_cases, u.data(), nullptr, (int32_t)(factors.size() / (size_t)n_cases), factors.data(), env.data(),
+                                        gov.data(), &info),
+          "femshell_combination_envelope");
+    return info;
+}
+
 SolveResult ShellSystem::solve(double tol, int max_it)
 {
     SolveResult r;
@@ -1321,6 +1358,56 @@ int fem_shell_main(int argc, char **argv, std::ostream &out, std::ostream &err)
                                                   : (ci.fused_product ? "6x6 block-Jacobi CG in lockstep, one pass over K for the cases of a pass"
                                                                       : "6x6 block-Jacobi CG in lockstep"))
                 << "), " << ci.solve_seconds << " s; " << stem << "_cases.txt, " << stem << "_case<k>.vtk" << std::endl;
+            if (p.combinations_requested()) {
+                // the envelope of the listed combinations: a line per element in the order of the mesh file (the cells of the VTK
+                // file); the library's rows are the triangles, then the quadrilaterals
+                std::vector<double> env;
+                std::vector<int32_t> gov;
+                const femshell_envelope_info ei = system.combination_envelope(u, n_cases, p.combination_factors, env, gov);
+                const size_t n_combos = p.combination_factors.size() / (size_t)n_cases;
+                std::ofstream ef(stem + "_envelope.txt");
+                if (!ef) throw std::runtime_error("cannot write " + stem + "_envelope.txt");
+                static const char *names[6] = {"von_mises_top_max", "von_mises_bottom_max", "N1_max", "N2_min", "M1_max", "M2_min"};
+                ef << "# element";
+                for (int k = 0; k < 6; k++) ef << " " << names[k];
+                for (int k = 0; k < 6; k++) ef << " governs_" << names[k];
+                ef << "\n";
+                const size_t ne = mesh.order.size();
+                std::vector<CellArray> arrays(12);
+                for (int k = 0; k < 6; k++) {
+                    arrays[(size_t)k].name = names[k];
+                    arrays[(size_t)k].values.resize(ne);
+                    arrays[6 + (size_t)k].name = std::string("governs_") + names[k];
+                    arrays[6 + (size_t)k].values.resize(ne);
+                    arrays[6 + (size_t)k].integer = true;
+                }
+                double worst = 0.0;
+                int worst_combo = 1;
+                char word[40];
+                for (size_t e = 0; e < ne; e++) {
+                    const size_t row = mesh.order[e].first == 't' ? (size_t)mesh.order[e].second : (size_t)mesh.n_tri() + (size_t)mesh.order[e].second;
+                    ef << e;
+                    for (int k = 0; k < 6; k++) {
+                        snprintf(word, sizeof word, " %.15e", env[6 * row + (size_t)k]);
+                        ef << word;
+                        arrays[(size_t)k].values[e] = env[6 * row + (size_t)k];
+                    }
+                    for (int k = 0; k < 6; k++) {
+                        ef << " " << gov[6 * row + (size_t)k] + 1;
+                        arrays[6 + (size_t)k].values[e] = (double)(gov[6 * row + (size_t)k] + 1);
+                    }
+                    ef << "\n";
+                    for (int k = 0; k < 2; k++)
+                        if (env[6 * row + (size_t)k] > worst) {
+                            worst = env[6 * row + (size_t)k];
+                            worst_combo = gov[6 * row + (size_t)k] + 1;
+                        }
+                }
+                write_vtk(mesh, std::vector<double>(n6, 0.0), stem + "_envelope.vtk", nullptr, &arrays);
+                out << "Load combinations: " << n_combos << " combinations of " << n_cases << " cases, largest surface von Mises stress = " << worst
+                    << " (combination " << worst_combo << "), " << ei.seconds_cases + ei.seconds_envelope << " s on the device; " << stem
+                    << "_envelope.txt, " << stem << "_envelope.vtk" << std::endl;
+            }
             clock.done("output files");
             out << "All done :)\n";
             clock.report(err);

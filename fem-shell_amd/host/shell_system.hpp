@@ -161,6 +161,14 @@ struct Parameters {
     std::string load_cases_file;
     std::vector<std::string> load_case_files, load_case_names; // the paths as they are opened, the words of the list
     bool load_cases_requested() const { return !load_cases_file.empty(); }
+    // load combinations (extension; with -load_cases only): -combinations FILE2 holds one combination per line, a factor per case
+    // of the list (load_cases.hpp read_combinations; read with the command line).  After the cases are solved the run calls
+    // femshell_combination_envelope and writes <out>_envelope.txt -- a header, then per element in the order of the mesh file its
+    // index, the six envelope values (%.15e) and the six governing combinations counted from 1 -- and <out>_envelope.vtk, the
+    // undeformed mesh with six double and six int cell arrays.
+    std::string combinations_file;
+    std::vector<double> combination_factors; // n_combos x n_cases
+    bool combinations_requested() const { return !combinations_file.empty(); }
 };
 
 // what femshell_set_element_loads takes: rows (p, qx, qy, qz) of the triangles and of the quadrilaterals
@@ -296,6 +304,10 @@ class ShellSystem {
     // -load_cases: femshell_solve_cases for loads[n_cases][n_nodes][6]; u in the same layout, one info per case
     femshell_cases_info solve_cases(const std::vector<double> &loads, int n_cases, double tol, int max_it, std::vector<double> &u,
                                     std::vector<femshell_case_info> &cases);
+    // -combinations: femshell_combination_envelope for u[n_cases][n_nodes][6] and factors[n_combos][n_cases] (no case carries
+    // temperatures: -load_cases refuses the thermal options); env and gov hold six values per element, triangles then quadrilaterals
+    femshell_envelope_info combination_envelope(const std::vector<double> &u, int n_cases, const std::vector<double> &factors,
+                                                std::vector<double> &env, std::vector<int32_t> &gov);
     femshell_ctx *handle() { return ctx_; }
 
   private:

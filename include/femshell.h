@@ -839,6 +839,41 @@ int femshell_solve_cases(femshell_ctx *ctx, int32_t n_cases, const double *loads
                          double *u_out /* n_cases x n_nodes x 6 */, femshell_case_info *case_info /* n_cases, or NULL */,
                          femshell_cases_info *info /* or NULL */);
 
+/* ---- load combinations: the stress envelope over factored sums of cases ----------------------------------------------------
+ * extends: the reference has no load cases; a structural check wants, per element, the worst stress and the extreme principal
+ * forces and moments over all combinations sum_j f_cj (case j), and the combination that governs.
+ * With u_j the caller's vector of case j (the layout of femshell_solve_cases' u_out), eps and kappa the element means of
+ * femshell_element_resultants (same operators, same quadrature, the element's own section), in the element frame K is built with:
+ *     T_j[e] = (Nxx, Nyy, Nxy, Mxx, Myy, Mxy),  N_loc = t Dm (eps(u_j) - tau_j eps0),  M_loc = -Dp (kappa(u_j) - tau_j kappa0)
+ *     T_c[e] = sum_j f_cj T_j[e]                 (j = 0 .. n_cases - 1, in index order)
+ * eps0, kappa0: the free thermal state of the temperatures in force (femshell_set_thermal); tau_j = case_thermal[j]: the multiple
+ * of that state case j was loaded with -- 1 for a case composed from femshell_thermal_load_vector, 0 otherwise (NULL: all zero).
+ * From T_c six values per element, none of which depends on the in-plane axes the element chooses:
+ *     q0, q1 = von Mises (plane-stress form) of N/t + 6M/t^2 (top) and N/t - 6M/t^2 (bottom)
+ *     q2, q3 = N1 >= N2, the principal membrane forces (Nxx+Nyy)/2 +- sqrt(((Nxx-Nyy)/2)^2 + Nxy^2)
+ *     q4, q5 = M1 >= M2, the principal moments, likewise (their signs follow the element's node order, as M's do)
+ *     env_out[e] = (max_c q0, max_c q1, max_c q2, min_c q3, max_c q4, min_c q5)
+ * gov_out[e][k] (or NULL): the lowest combination index, from 0, that attains env_out[e][k].  Rows are the caller's elements,
+ * triangles then quadrilaterals, under FEMSHELL_REORDER too.  A case's vector is taken whole: the context's prescribed values are
+ * not added.  factors: n_combos x n_cases, row-major.  1 <= n_cases <= 32, 1 <= n_combos <= 256.
+ * The call needs a mesh, not an assembled K; nothing is kept and nothing of the context changes.  Two calls give the same bits; a
+ * combination's values do not depend on its position or on the other combinations, a case's contribution not on its position or
+ * on the other cases; a factor of exactly 0 leaves no trace of its case.
+ * info (or NULL): the device seconds of the two kernels and their algorithmic bytes.
+ * FEMSHELL_ERR_UNSUPPORTED on a row-partitioned context.  FEMSHELL_ERR_INVALID, outputs not written: no mesh; a NULL ctx, u,
+ * factors or env_out; counts out of range; a non-finite entry in u, factors or case_thermal; a non-zero case_thermal while no
+ * temperatures are in force; dynamics active.  FEMSHELL_ERR_MESH: a degenerate element, named as femshell_element_resultants names
+ * it.  The context stays usable after every refusal. */
+typedef struct femshell_envelope_info {
+    double seconds_cases, seconds_envelope;   /* device seconds of the two kernels */
+    double bytes_cases, bytes_envelope;       /* algorithmic byte model, DESIGN.md 8n */
+} femshell_envelope_info;
+int femshell_combination_envelope(femshell_ctx *ctx, int32_t n_cases, const double *u /* n_cases x n_nodes x 6 */,
+                                  const double *case_thermal /* n_cases, or NULL: zeros */,
+                                  int32_t n_combos, const double *factors /* n_combos x n_cases, row-major */,
+                                  double *env_out /* (n_tri + n_quad) x 6 */, int32_t *gov_out /* (n_tri + n_quad) x 6, or NULL */,
+                                  femshell_envelope_info *info /* or NULL */);
+
 /* test entry: G = A^T diag(w) B (qa x qb, row-major) by the solver's Gram kernel; A, B: qa / qb columns of n_nodes x 6 in the
  * caller's numbering, 1 <= qa, qb <= 96; weighted != 0: w = the lumped mass (a density must be set), else w = 1.  Partial sums
  * are added in a fixed order: two calls give the same bits. */
